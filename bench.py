@@ -17,7 +17,7 @@ PMC bytes / algorithmic bytes.
 
 One "step" = one env.step() of all worlds = ONE launch of the family's step kernel (+ the HER reward kernel for cfg 2).
 `--stages K` steps the rank's worlds as K out-of-phase sub-batches on K streams instead (gymnasium_robotics_amd.pipeline; one "step" = one env.step() of every sub-batch): +10 - 25 % from the same
-kernels.  The plain 1-GPU line reports that mode BESIDE its value (`sub_batches`: the same worlds and timed region, K = 2, measured right after the plain region) -- `value` itself is always the
+kernels.  With --full the 1-GPU line reports that mode BESIDE its value (`sub_batches`: the same worlds and timed region, K = 2, measured right after the plain region) -- `value` itself is always the
 plain vector environment.
 --workload selects the other BASELINE configs under the same contract and the same JSON schema:
     fetch       cfg 2  FetchPickAndPlace-v4, 4096 worlds / GPU
@@ -28,7 +28,11 @@ plain vector environment.
     mixed       cfg 5  FrankaKitchen-v1 + AdroitHandHammer-v2 side by side, 2048 + 2048 worlds / GPU (32768 over 8): two streams, two host threads
     hand_reach         HandReach-v3, 16384 worlds / GPU
 
+A plain run sets up, pre-rolls and warms up, times --steps steps and prints the result line.  Everything else the line used to carry -- the CPU baseline,
+`long_window`, `north_star_share`, `sub_batches` -- runs only with --full.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
+
     python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --full     (the plain line + the extra legs above)
     python bench.py --gpus 8            (spawns 8 ranks itself when not started by torchrun)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -71,6 +75,48 @@ PROFILE_TAGS = ("r06",)      # rounds whose profiles/pmc_<tag>_*.json may be quo
 LONG_WINDOW_STEPS = 100
 NORTH_STAR_WORLDS_PER_GPU = 8192      # BASELINE.json north_star: 65 536 FetchPickAndPlace worlds on 8 GPUs
 VALU_PEAK_IPS = 256 * 4 * 2.4e9 / 2      # wave64 VALU instructions per second, whole chip (SIMD-32: 2 cycles per wave64 instruction)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all; larger outputs are cut to a fixed, seeded sample of rows
+
+
+def _flatten_outputs(prefix, x, out):
+    """name -> array for every tensor / array in a step's return value (dicts and tuples walked, None and plain scalars skipped)"""
+    if isinstance(x, dict):
+        for k, v in x.items():
+            _flatten_outputs(f"{prefix}_{k}" if prefix else str(k), v, out)
+    elif isinstance(x, (tuple, list)):
+        for k, v in enumerate(x):
+            _flatten_outputs(f"{prefix}_{k}", v, out)
+    elif isinstance(x, torch.Tensor):
+        out[prefix] = x.detach().cpu().numpy()
+    elif isinstance(x, np.ndarray):
+        out[prefix] = x
+    return out
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: DIR/<name>.npy for every array of `outputs` (name -> step return value), float64 stays float64, everything else becomes float32
+    (integers that float32 cannot hold exactly: float64).  Above DUMP_MAX_BYTES every array keeps the same fixed, seeded sample of its rows."""
+    arrays = {}
+    for name, x in outputs.items():
+        _flatten_outputs(name, x, arrays)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype == np.float64 or (a.dtype.kind in "iu" and a.size and np.abs(a).max() >= 2 ** 24):
+            conv[name] = a.astype(np.float64)
+        else:
+            conv[name] = a.astype(np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES / total
+        for name, a in conv.items():
+            if a.ndim and len(a) > 1:
+                k = max(1, int(len(a) * keep))
+                conv[name] = a[np.sort(np.random.default_rng(len(a)).choice(len(a), k, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name.replace("/", "_") + ".npy"), a)
+    return sorted(conv)
 
 
 def _set_elapsed(env, elapsed):
@@ -255,12 +301,12 @@ def run_rank_mixed(args, rank, world_size, local_rank):
 
     def one_step():
         with on(0):     # FrankaKitchen: enqueue only
-            (envs[0].step if dry else envs[0].step_launch)(act(0))
+            out0 = (envs[0].step if dry else envs[0].step_launch)(act(0))
         with on(1):     # AdroitHandHammer: its step never waits for the device
-            envs[1].step(act(1))
+            out1 = envs[1].step(act(1))
         if not dry:
             with on(0):
-                envs[0].step_finish()
+                out0 = envs[0].step_finish()
         if dist:
             for k in range(2):
                 if not dry:
@@ -269,6 +315,8 @@ def run_rank_mixed(args, rank, world_size, local_rank):
             for k in range(2):
                 if not dry:
                     streams[k].wait_stream(torch.cuda.current_stream())
+        names = ("obs", "reward", "terminated", "truncated", "info")
+        return {MIXED[0]: dict(zip(names, out0)), MIXED[1]: dict(zip(names, out1)), "gathered": gathered if dist else None}
 
     for _ in range(preroll + args.warmup):
         one_step()
@@ -280,11 +328,13 @@ def run_rank_mixed(args, rank, world_size, local_rank):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     sync()
     if dist:
         dist.barrier()
     elapsed = own_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     if dist:
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -320,7 +370,7 @@ def run_rank_mixed(args, rank, world_size, local_rank):
             line["dist"] = dist_report
         if dry:
             line["data"] = "DRY RUN: no physics, random rows on the CPU over gloo (plumbing check of the multi-rank command line)"
-        if world_size == 1 and not args.no_cpu_baseline and not dry:
+        if world_size == 1 and args.full and not args.no_cpu_baseline and not dry:
             parts = [cpu_baseline(name, seconds=5.0) for name in MIXED]
             mix = lambda key: 2.0 / sum(1.0 / p[key] for p in parts)      # a mixed batch = equal numbers of steps of both families
             line["cpu_baseline"] = {"value": mix("value"), "unit": "env-steps/s", "cores": 1, "kind": "port", "value_all_cores": mix("value_all_cores"),
@@ -384,16 +434,20 @@ def run_rank_stages(args, rank, world_size, local_rank):
     act_dim = pe.single_action_space.shape[0]
 
     def one_step():
+        outs = {}
         for k, env in enumerate(pe.stage_envs):
             with pe.on(k):
                 a = torch.rand(m, act_dim, device=device, generator=gens[k]) * 2 - 1
                 obs, r, term, trunc, info = env.step(a)
+                outs[f"stage{k}"] = {"obs": obs, "reward": r, "terminated": term, "truncated": trunc, "info": info}
                 if her:
                     replays[k].append(a, env.packed, term | trunc, final_rows=env.final_packed)
-                    replays[k].relabel(HER_K * m, k_future=HER_K)
+                    outs[f"stage{k}"]["her_batch"] = replays[k].relabel(HER_K * m, k_future=HER_K)
                 if dist:
                     rows = getattr(env, "packed", None)
                     dist.all_gather_into_tensor(gathered[k], env.obs if rows is None else rows)
+                    outs[f"stage{k}"]["gathered"] = gathered[k]
+        return outs
 
     preroll = (pe.max_episode_steps or w["horizon"]) if args.preroll < 0 else args.preroll
     if dry:
@@ -410,11 +464,13 @@ def run_rank_stages(args, rank, world_size, local_rank):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     sync()
     if dist:
         dist.barrier()
     elapsed = own_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     if dist:
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -452,7 +508,7 @@ def run_rank_stages(args, rank, world_size, local_rank):
             line["dist"] = dist_report
         if dry:
             line["data"] = "DRY RUN: no physics, random rows on the CPU over gloo (plumbing check of the multi-rank command line)"
-        if not args.no_cpu_baseline and world_size == 1 and not dry:
+        if args.full and not args.no_cpu_baseline and world_size == 1 and not dry:
             line["cpu_baseline"] = cpu_baseline(args.workload)
     if dist:
         dist.destroy_process_group()
@@ -530,13 +586,16 @@ def run_rank(args, rank, world_size, local_rank):
     def one_step():
         a = act_buf.uniform_(-1.0, 1.0, generator=gen)      # uniform random actions: one kernel
         obs, r, term, trunc, info = env.step(a)
+        outs = {"obs": obs, "reward": r, "terminated": term, "truncated": trunc, "info": info}
         if her:
             replay.append(a, env.packed, term | trunc, final_rows=env.final_packed)   # the reset kernel parked the terminal rows there: the last transition of every episode is relabelled too
-            replay.relabel(HER_K * n, k_future=HER_K)
+            outs["her_batch"] = replay.relabel(HER_K * n, k_future=HER_K)
         if dist:   # the step kernel wrote the packed [obs | achieved | desired | reward | success] rows: one collective, no pack kernels.
             # Stream-ordered, not pipelined: on one rank the collective costs 0.01 ms of the 3.3 ms step; an asynchronous gather from a staging copy, waited for two
             # steps later, measured 0.2 - 0.9 ms SLOWER per step (cross-stream dependencies in both directions every step; tools/ab_dist.sh)
             dist.all_gather_into_tensor(gathered, out_rows)
+            outs["gathered"] = gathered
+        return outs
 
     # Steady state before anything is timed: a fresh batch is not what a training run sees -- the worlds of a Fetch batch that end up with the upper arm
     # resting on the head link (the stragglers that end a launch) accumulate over an episode, and the HER ring holds fewer steps than its horizon -- so the first ~25 steps
@@ -556,11 +615,13 @@ def run_rank(args, rank, world_size, local_rank):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     sync()
     if dist:
         dist.barrier()
     elapsed = own_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     if dist:
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -605,7 +666,7 @@ def run_rank(args, rank, world_size, local_rank):
     # `long_window`: the same environment stepped on for 100 more timed steps right behind the driver's window -- a 20-step window holds 0 - 3 overflow re-runs of 1 - 3 ms each
     # and scatters by +-4 %; the long figure is the one to compare builds by.  One GPU only (no collective bookkeeping), skipped when the window already is that long.
     long_window = None
-    if not dry and world_size == 1 and not dist and args.steps < LONG_WINDOW_STEPS and args.long_window:
+    if args.full and not dry and world_size == 1 and not dist and args.steps < LONG_WINDOW_STEPS and args.long_window:
         sync()
         t1 = time.perf_counter()
         for _ in range(LONG_WINDOW_STEPS):
@@ -657,14 +718,14 @@ def run_rank(args, rank, world_size, local_rank):
     # The north star's share of one GPU (BASELINE.json: FetchPickAndPlace-v4, 65 536 worlds on 8 GPUs = 8 192 per GPU), in the driver's own line: the same workload, timed region,
     # warm-up and step count at 8 192 worlds, measured in the same process right after the plain region.  Eight ranks without a step collective would run eight of these; the
     # product of 8 is a projection and is NOT reported.
-    if line is not None and world_size == 1 and not dist and not dry and args.north_star_share and args.workload == "fetch" and n == w["worlds"] and not args.no_cpu_baseline:
+    if line is not None and args.full and world_size == 1 and not dist and not dry and args.north_star_share and args.workload == "fetch" and n == w["worlds"] and not args.no_cpu_baseline:
         try:
             import copy
 
             env = replay = None      # (the closure one_step sees the same cells: the 4 096-world buffers are released before the next leg allocates)
             torch.cuda.empty_cache()
             a3 = copy.copy(args)
-            a3.worlds_per_gpu, a3.no_cpu_baseline, a3.sub_batches, a3.north_star_share = NORTH_STAR_WORLDS_PER_GPU, True, False, False
+            a3.worlds_per_gpu, a3.no_cpu_baseline, a3.sub_batches, a3.north_star_share, a3.dump_outputs = NORTH_STAR_WORLDS_PER_GPU, True, False, False, None
             l3 = run_rank(a3, rank, world_size, local_rank)
             line["north_star_share"] = {"worlds": NORTH_STAR_WORLDS_PER_GPU, "value": l3["value"], "ms_per_step": l3["ms_per_step"], "kernel_ms": l3["roofline"]["kernel_ms"],
                                         "long_window": l3.get("long_window"), "capacity_overflow_worlds": l3["config"]["capacity_overflow_worlds"],
@@ -674,21 +735,21 @@ def run_rank(args, rank, world_size, local_rank):
             line["north_star_share"] = {"error": repr(e)}
     # The same worlds as two out-of-phase sub-batches (run_rank_stages), measured in the same process right after the plain line: reported BESIDE
     # `value`, never as it -- `value` stays env.step() over all worlds of one vector environment, the configuration BASELINE.json names.
-    if line is not None and world_size == 1 and not dist and not dry and args.sub_batches and not args.no_cpu_baseline and args.workload != "hand_touch":      # (like cpu_baseline: a reporting extra of the full line; the A/B and profiling tools pass --no-cpu-baseline)
+    if line is not None and args.full and world_size == 1 and not dist and not dry and args.sub_batches and not args.no_cpu_baseline and args.workload != "hand_touch":      # (like cpu_baseline: a reporting extra of the full line; the A/B and profiling tools pass --no-cpu-baseline)
         try:
             import copy
 
             env = replay = None
             torch.cuda.empty_cache()
             a2 = copy.copy(args)
-            a2.stages, a2.no_cpu_baseline = 2, True
+            a2.stages, a2.no_cpu_baseline, a2.dump_outputs = 2, True, None
             l2 = run_rank_stages(a2, rank, world_size, local_rank)
             line["sub_batches"] = {"stages": 2, "value": l2["value"], "ms_per_step": l2["ms_per_step"], "capacity_overflow_worlds": l2["config"]["capacity_overflow_worlds"],
                                    "note": "the same worlds, timed region and step count as `value`, stepped as 2 out-of-phase sub-batches on 2 streams (python bench.py --stages 2; "
                                            "gymnasium_robotics_amd.pipeline.PipelinedVecEnv): for callers that act on half a batch at a time"}
         except Exception as e:      # the extra leg must never cost the line
             line["sub_batches"] = {"error": repr(e)}
-    if line is not None and world_size == 1 and not args.no_cpu_baseline and not dry:      # (last: its worker processes load the host)
+    if line is not None and args.full and world_size == 1 and not args.no_cpu_baseline and not dry:      # (last: its worker processes load the host)
         line["cpu_baseline"] = cpu_baseline(args.workload)
     return line
 
@@ -716,7 +777,11 @@ def main():
     ap.add_argument("--no-long-window", dest="long_window", action="store_false", help="skip the 100 extra timed steps reported as `long_window` beside a shorter timed region")
     ap.add_argument("--stages", type=int, default=1, help="K > 1: the rank's worlds as K out-of-phase sub-batches on K streams (gymnasium_robotics_amd.pipeline; not for --workload mixed)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU, no physics: random rows on the CPU over gloo -- checks the multi-rank plumbing of this exact command line")
+    ap.add_argument("--full", action="store_true", help="also run the extra legs of the line (1 GPU): CPU baseline, long_window, north_star_share, sub_batches; a plain run only times --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (observations, rewards, flags, infos, the HER batch) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" in os.environ:   # started by torchrun: one rank per process already
         ws = int(os.environ["WORLD_SIZE"])

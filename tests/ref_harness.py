@@ -521,3 +521,165 @@ def oracle_init_qpos():
     from gymnasium_robotics_amd.envs.kitchen_spec import INIT_QPOS
 
     return INIT_QPOS.copy()
+
+
+# ---------------------------------------------------------------------------------------------- recordings of the reference's side
+# Where the reference tree is absent the tests of test_cpu_reference_task_layer.py still run: every answer the reference's code gave there -- the
+# return value of each call, each plain attribute read, the exception a call raised -- and the state it left in its physics host (the second oracle
+# env, `host`) were recorded once into tests/golden/ref_task_layer/<test>.pkl.xz (GRX_REF_RECORD=1 on a run with the reference present).  Replaying
+# hands the test those answers in the recorded order, checks that every call gets the arguments it got when recorded, and writes the recorded
+# host state back after each call, so the test's assertions against the restated task layer are the same ones, bit for bit.
+# GRX_REF_REPLAY=1 replays even where the reference is present.
+import builtins  # noqa: E402
+import copy  # noqa: E402
+import lzma  # noqa: E402
+import pickle  # noqa: E402
+
+TAPES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_task_layer")
+_SIM_FIELDS = ("qpos", "qvel", "ctrl", "mocap_pos", "mocap_quat", "act", "touch", "qacc_warmstart")
+_VALUES = (type(None), bool, int, float, str, np.generic, np.ndarray, dict, list, tuple)
+
+
+def replaying():
+    return os.environ.get("GRX_REF_REPLAY") == "1" or not available()
+
+
+def _plain(x):
+    """a copy of x with every object that is not a plain value (arrays, numbers, strings, containers of them) replaced by None"""
+    if isinstance(x, np.ndarray):
+        return x.copy()
+    if isinstance(x, (type(None), bool, int, float, str, np.generic)):
+        return x
+    if isinstance(x, dict):
+        return {k: _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_plain(v) for v in x) if type(x) in (list, tuple) else tuple(_plain(v) for v in x)
+    return None
+
+
+def _same(a, b):
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b)
+    if isinstance(a, dict) and isinstance(b, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return type(a) is type(b) and a == b
+
+
+def _snapshot(host):
+    sim = {k: getattr(host.sim, k).copy() for k in _SIM_FIELDS if isinstance(getattr(host.sim, k, None), np.ndarray)}
+    env = {k: _plain(v) for k, v in vars(host).items() if isinstance(v, (bool, int, float, np.generic)) or (isinstance(v, np.ndarray) and v.size <= 4096)}
+    return sim, env
+
+
+def _restore(host, snap):
+    sim, env = snap
+    for k, v in sim.items():
+        getattr(host.sim, k)[...] = v
+    for k, v in env.items():
+        cur = getattr(host, k, None)
+        if isinstance(cur, np.ndarray) and isinstance(v, np.ndarray) and cur.shape == v.shape and cur.dtype == v.dtype:
+            cur[...] = v
+        else:
+            setattr(host, k, copy.copy(v))
+
+
+class Tape:
+    """One test's recording.  env(host, build): the reference's environment -- build() itself (run live), build() wrapped so that its answers are
+    recorded (GRX_REF_RECORD=1), or, replaying, a stand-in that answers from the recording and never touches the reference."""
+
+    def __init__(self, name):
+        self.path = os.path.join(TAPES, name.replace("/", "_") + ".pkl.xz")
+        self.replay = replaying()
+        self.record = not self.replay and os.environ.get("GRX_REF_RECORD") == "1"
+        self.events, self.pos = [], 0
+        if self.replay:
+            with lzma.open(self.path, "rb") as f:
+                self.events = pickle.load(f)
+
+    def env(self, host, build):
+        if self.replay:
+            return _Replayed(self, "", host)
+        obj = build()
+        return _Recorded(self, "", obj, host) if self.record else obj
+
+    def close(self, passed):
+        if self.record and passed:
+            os.makedirs(TAPES, exist_ok=True)
+            with lzma.open(self.path, "wb") as f:
+                pickle.dump(self.events, f, protocol=4)
+        if self.replay and passed:
+            assert self.pos == len(self.events), f"{self.path}: {len(self.events) - self.pos} recorded answers were never asked for"
+
+    def _next(self, kind, path):
+        assert self.pos < len(self.events), f"{self.path}: the test asks for {path} after the end of the recording"
+        ev = self.events[self.pos]
+        assert ev[0] == kind and ev[1] == path, f"{self.path}: the test asks for {kind} {path}, the recording has {ev[0]} {ev[1]} next"
+        self.pos += 1
+        return ev
+
+
+class _Recorded:
+    def __init__(self, tape, path, obj, host):
+        object.__setattr__(self, "_r", (tape, path, obj, host))
+
+    def __getattr__(self, name):
+        tape, path, obj, host = object.__getattribute__(self, "_r")
+        v, p = getattr(obj, name), f"{path}.{name}" if path else name
+        if callable(v) and not isinstance(v, type):
+            def call(*args, **kw):
+                try:
+                    out = v(*args, **kw)
+                except Exception as e:
+                    tape.events.append(("call", p, _plain((args, kw)), None, (type(e).__name__, str(e)), _snapshot(host)))
+                    raise
+                tape.events.append(("call", p, _plain((args, kw)), _plain(out), None, _snapshot(host)))
+                return out
+            return call
+        if isinstance(v, _VALUES):
+            tape.events.append(("get", p, _plain(v)))
+            return v
+        return _Recorded(tape, p, v, host)
+
+    def __setattr__(self, name, value):
+        setattr(object.__getattribute__(self, "_r")[2], name, value)
+
+    def __getitem__(self, key):
+        tape, path, obj, host = object.__getattribute__(self, "_r")
+        v = obj[key]
+        tape.events.append(("get", f"{path}[{key!r}]", _plain(v)))
+        return v
+
+
+class _Replayed:
+    def __init__(self, tape, path, host):
+        object.__setattr__(self, "_r", (tape, path, host))
+
+    def __getattr__(self, name):
+        tape, path, host = object.__getattribute__(self, "_r")
+        p = f"{path}.{name}" if path else name
+        assert tape.pos < len(tape.events), f"{tape.path}: the test asks for {p} after the end of the recording"
+        kind, q = tape.events[tape.pos][:2]
+        if q == p and kind == "get":
+            return copy.deepcopy(tape._next("get", p)[2])
+        if q.startswith(p + ".") or q.startswith(p + "["):
+            return _Replayed(tape, p, host)
+        # a method is looked up before its arguments are evaluated, and they may read the recording first: the call takes its answer when it is made
+        if any(ev[0] == "call" and ev[1] == p for ev in tape.events[tape.pos:]):
+            def call(*args, **kw):
+                _, _, given, out, exc, snap = tape._next("call", p)
+                assert _same(_plain((args, kw)), given), f"{tape.path}: {p} called with other arguments than when it was recorded"
+                _restore(host, snap)
+                if exc is not None:
+                    raise getattr(builtins, exc[0], RuntimeError)(exc[1])
+                return copy.deepcopy(out)
+            return call
+        raise AssertionError(f"{tape.path}: the test asks for {p}, the recording has {kind} {q} next")
+
+    def __setattr__(self, name, value):
+        pass      # (a write into the reference's objects: its effect is in what was recorded after it)
+
+    def __getitem__(self, key):
+        tape, path, host = object.__getattribute__(self, "_r")
+        return copy.deepcopy(tape._next("get", f"{path}[{key!r}]")[2])

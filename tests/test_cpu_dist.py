@@ -117,6 +117,33 @@ def test_bench_multi_rank_command_line_dry_run(workload, ranks, extra):
     assert line["data"].startswith("DRY RUN")
 
 
+@pytest.mark.parametrize("extra", [[], ["--stages", "2"], ["--workload", "mixed"]])
+def test_bench_dump_outputs_dry_run(tmp_path, extra):
+    """--dump-outputs DIR: what the last timed step returned, one float32 / float64 .npy per array; the same arguments give the same inputs, so two runs
+    write the same files (here the rows the gather delivered, which carry the world ids); --steps sets the number of timed steps and ms_per_step is per step."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--dry-run", "--gpus", "2", "--worlds-per-gpu", "32", "--steps", "4", "--warmup", "1",
+               "--dump-outputs", str(d)] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+        files = sorted(os.listdir(d))
+        assert files and all(f.endswith(".npy") for f in files) and any("gathered" in f for f in files), files
+        dumps.append({f: np.load(d / f) for f in files})
+        assert all(a.dtype in (np.float32, np.float64) for a in dumps[-1].values())
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_bench_under_torchrun_dry_run():
     """the DRIVER's own launch line for N > 1 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`):
     bench.py must take rank / world size from the environment instead of spawning, and still print exactly one JSON line (rank 0)"""

@@ -3,17 +3,24 @@ mujoco_utils helpers (ctrl_set_action, mocap_set_action + reset_mocap2body_xpos,
 set_joint_qpos) EXECUTED on top of the oracle's physics (tests/ref_harness.py), against the oracle environment's restated task layer
 on an identical second simulation: observations, achieved goal, reward, success flag and the post-step state must be bit-identical.
 This pins SURVEY.md section 8(a) rows P1, P3-P9 of the checker against the reference code itself; what stays unpinned is the
-physics (P2).  Skips where /root/reference is not mounted."""
+physics (P2).  Where the reference tree is absent, the reference's side is replayed from its recording (ref_harness.Tape,
+tests/golden/ref_task_layer/): the same answers, arguments checked, the host simulation's state written back after every call."""
 import numpy as np
 import pytest
 
 import ref_harness
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="the reference tree is not mounted here")
+
+@pytest.fixture
+def tape(request):
+    failed = request.session.testsfailed
+    t = ref_harness.Tape(request.node.name)
+    yield t
+    t.close(passed=request.session.testsfailed == failed)
 
 
 @pytest.mark.parametrize("task,reward_type", [("FetchReach", "sparse"), ("FetchPush", "dense"), ("FetchSlide", "sparse"), ("FetchPickAndPlace", "sparse")])
-def test_reference_step_on_oracle_physics_equals_the_oracle_env(fetch_models, task, reward_type):
+def test_reference_step_on_oracle_physics_equals_the_oracle_env(fetch_models, task, reward_type, tape):
     from oracle.fetch_oracle import OracleFetchEnv
 
     a_env = OracleFetchEnv(fetch_models[task], task, reward_type=reward_type)      # restated task layer
@@ -21,7 +28,7 @@ def test_reference_step_on_oracle_physics_equals_the_oracle_env(fetch_models, ta
     oa, _ = a_env.reset(seed=11)
     ob, _ = b_env.reset(seed=11)
     assert np.array_equal(oa["observation"], ob["observation"])
-    ref = ref_harness.fetch_on_oracle(b_env, reward_type)
+    ref = tape.env(b_env, lambda: ref_harness.fetch_on_oracle(b_env, reward_type))
     # the reference's _get_obs on the freshly reset state
     o0 = ref._get_obs()
     assert np.array_equal(o0["observation"], oa["observation"]) and np.array_equal(o0["achieved_goal"], oa["achieved_goal"]) and np.array_equal(o0["desired_goal"], oa["desired_goal"])
@@ -53,7 +60,7 @@ def _same_step(a_out, b_out, a_sim, b_sim, t):
 
 
 @pytest.mark.parametrize("reward_type", ["sparse", "dense"])
-def test_reference_hand_reach_step_on_oracle_physics(reward_type):
+def test_reference_hand_reach_step_on_oracle_physics(reward_type, tape):
     """hand_env.py:42-61 (_set_action, absolute control), reach.py:92-97,398-428 (_get_obs, reward, success) executed as is."""
     from gymnasium_robotics_amd.envs.hand import load_hand_reach_model
     from oracle.hand_oracle import OracleHandReachEnv
@@ -61,7 +68,7 @@ def test_reference_hand_reach_step_on_oracle_physics(reward_type):
     model = load_hand_reach_model()
     a_env, b_env = OracleHandReachEnv(model, reward_type), OracleHandReachEnv(model, reward_type)
     a_env.reset(seed=4); b_env.reset(seed=4)
-    ref = ref_harness.hand_on_oracle(b_env, "reach", reward_type=reward_type, distance_threshold=0.01)
+    ref = tape.env(b_env, lambda: ref_harness.hand_on_oracle(b_env, "reach", reward_type=reward_type, distance_threshold=0.01))
     o0 = ref._get_obs()
     assert np.array_equal(o0["observation"], a_env._obs()["observation"])
     rng = np.random.default_rng(1)
@@ -71,7 +78,7 @@ def test_reference_hand_reach_step_on_oracle_physics(reward_type):
 
 
 @pytest.mark.parametrize("env_id", ["HandManipulateBlockRotateXYZ-v1", "HandManipulateBlockFullDense-v1", "HandManipulateEggRotate-v1", "HandManipulatePenRotateDense-v1"])
-def test_reference_manipulate_step_on_oracle_physics(env_id):
+def test_reference_manipulate_step_on_oracle_physics(env_id, tape):
     """manipulate.py:87-142,298-316 (_goal_distance incl. the pen's ignore-z path, compute_reward, _is_success, _get_obs) executed as is."""
     from gymnasium_robotics_amd.envs.hand import load_hand_block_model
     from gymnasium_robotics_amd.envs.manipulate_spec import OBJECTS, object_of, parse_block_id
@@ -82,8 +89,9 @@ def test_reference_manipulate_step_on_oracle_physics(env_id):
     model = load_hand_block_model(obj=obj)
     a_env, b_env = OracleHandBlockEnv(model, tp, tr, rt, "off", obj), OracleHandBlockEnv(model, tp, tr, rt, "off", obj)
     a_env.reset(seed=2); b_env.reset(seed=2)
-    ref = ref_harness.hand_on_oracle(b_env, "manipulate", reward_type=rt, target_position=tp, target_rotation=tr, rotation_threshold=0.1,
-                                     distance_threshold=OBJECTS[obj]["distance_threshold"], ignore_z_target_rotation=OBJECTS[obj]["ignore_z_target_rotation"])
+    ref = tape.env(b_env, lambda: ref_harness.hand_on_oracle(b_env, "manipulate", reward_type=rt, target_position=tp, target_rotation=tr, rotation_threshold=0.1,
+                                                             distance_threshold=OBJECTS[obj]["distance_threshold"],
+                                                             ignore_z_target_rotation=OBJECTS[obj]["ignore_z_target_rotation"]))
     assert np.array_equal(ref._get_obs()["observation"], a_env._obs()["observation"])
     rng = np.random.default_rng(5)
     for t in range(6):
@@ -92,12 +100,12 @@ def test_reference_manipulate_step_on_oracle_physics(env_id):
 
 
 @pytest.mark.parametrize("task", ["FetchReach", "FetchPush", "FetchSlide", "FetchPickAndPlace"])
-def test_reference_reset_on_oracle_physics(fetch_models, task):
+def test_reference_reset_on_oracle_physics(fetch_models, task, tape):
     """robot_env.py:154-186 (reset: seeding, _reset_sim loop, _sample_goal, _get_obs) with fetch_env.py:375-402 executed as is."""
     from oracle.fetch_oracle import OracleFetchEnv
 
     a_env, b_env = OracleFetchEnv(fetch_models[task], task), OracleFetchEnv(fetch_models[task], task)
-    ref = ref_harness.fetch_on_oracle(b_env)
+    ref = tape.env(b_env, lambda: ref_harness.fetch_on_oracle(b_env))
     for seed in (0, 7, 123):
         oa, _ = a_env.reset(seed=seed)
         ob, info = ref.reset(seed=seed)
@@ -109,13 +117,14 @@ def test_reference_reset_on_oracle_physics(fetch_models, task):
         assert np.array_equal(ref.step(act)[0]["observation"], a_env.step(act)[0]["observation"])      # and the episode continues identically
 
 
-def test_reference_hand_reach_reset_on_oracle_physics():
+def test_reference_hand_reach_reset_on_oracle_physics(tape):
     from gymnasium_robotics_amd.envs.hand import load_hand_reach_model
     from oracle.hand_oracle import OracleHandReachEnv
 
     model = load_hand_reach_model()
     a_env, b_env = OracleHandReachEnv(model), OracleHandReachEnv(model)
-    ref = ref_harness.hand_on_oracle(b_env, "reach", reward_type="sparse", distance_threshold=0.01, initial_goal=b_env.initial_goal.copy(), palm_xpos=b_env.palm_xpos.copy())
+    ref = tape.env(b_env, lambda: ref_harness.hand_on_oracle(b_env, "reach", reward_type="sparse", distance_threshold=0.01, initial_goal=b_env.initial_goal.copy(),
+                                                             palm_xpos=b_env.palm_xpos.copy()))
     for seed in (1, 22):
         oa, _ = a_env.reset(seed=seed)
         ob, _ = ref.reset(seed=seed)
@@ -124,7 +133,7 @@ def test_reference_hand_reach_reset_on_oracle_physics():
 
 
 @pytest.mark.parametrize("env_id", ["HandManipulateBlockRotateXYZ-v1", "HandManipulateBlockRotateParallel-v1", "HandManipulateEggFull-v1", "HandManipulatePenRotate-v1"])
-def test_reference_manipulate_reset_on_oracle_physics(env_id):
+def test_reference_manipulate_reset_on_oracle_physics(env_id, tape):
     """manipulate.py:154-224 (_reset_sim: pose randomisation, ten settle steps through _set_action + mj_step, the on-palm test) and
     :226-279 (_sample_goal from the settled pose), inside robot_env.py's reset loop, executed as is."""
     import types
@@ -138,14 +147,19 @@ def test_reference_manipulate_reset_on_oracle_physics(env_id):
     obj = object_of(env_id)
     model = load_hand_block_model(obj=obj)
     a_env, b_env = OracleHandBlockEnv(model, tp, tr, rt, "off", obj), OracleHandBlockEnv(model, tp, tr, rt, "off", obj)
-    ref = ref_harness.hand_on_oracle(b_env, "manipulate", reward_type=rt, target_position=tp, target_rotation=tr, rotation_threshold=0.1,
-                                     distance_threshold=OBJECTS[obj]["distance_threshold"], ignore_z_target_rotation=OBJECTS[obj]["ignore_z_target_rotation"],
-                                     randomize_initial_rotation=OBJECTS[obj]["randomize_initial_rotation"], randomize_initial_position=True,
-                                     target_position_range=TARGET_POSITION_RANGE, parallel_quats=list(ms.canonical_parallel_quats()))
-    # the object:center site sits at the origin of the free object body (manipulate_*.xml); the engine model tracks no site for these envs
-    ref._model_names._site_name2id = {"object:center": 0}
-    type(ref.data).site_xpos = property(lambda self: self._env.sim.qpos[self._env.qa: self._env.qa + 3].reshape(1, 3))
+
+    def build():
+        ref = ref_harness.hand_on_oracle(b_env, "manipulate", reward_type=rt, target_position=tp, target_rotation=tr, rotation_threshold=0.1,
+                                         distance_threshold=OBJECTS[obj]["distance_threshold"], ignore_z_target_rotation=OBJECTS[obj]["ignore_z_target_rotation"],
+                                         randomize_initial_rotation=OBJECTS[obj]["randomize_initial_rotation"], randomize_initial_position=True,
+                                         target_position_range=TARGET_POSITION_RANGE, parallel_quats=list(ms.canonical_parallel_quats()))
+        # the object:center site sits at the origin of the free object body (manipulate_*.xml); the engine model tracks no site for these envs
+        ref._model_names._site_name2id = {"object:center": 0}
+        type(ref.data).site_xpos = property(lambda self: self._env.sim.qpos[self._env.qa: self._env.qa + 3].reshape(1, 3))
+        return ref
+
     try:
+        ref = tape.env(b_env, build)
         for seed in (0, 3):
             oa, _ = a_env.reset(seed=seed)
             ob, _ = ref.reset(seed=seed)
@@ -153,12 +167,12 @@ def test_reference_manipulate_reset_on_oracle_physics(env_id):
                 assert np.allclose(ob[k], oa[k], rtol=0, atol=1e-15), (seed, k, np.abs(ob[k] - oa[k]).max())
             assert np.array_equal(a_env.sim.qpos, b_env.sim.qpos)
     finally:
-        type(ref.data).site_xpos = property(lambda self: self._env.sim.site_xpos.reshape(-1, 3))
+        ref_harness.HandDataProxy.site_xpos = property(lambda self: self._env.sim.site_xpos.reshape(-1, 3))
 
 
 @pytest.mark.parametrize("layout,reward_type,continuing,reset_target", [("UMaze", "sparse", True, False), ("Medium_Diverse_GR", "dense", False, False),
                                                                         ("Large_Diverse_G", "sparse", True, True)])
-def test_reference_point_maze_on_oracle_physics(layout, reward_type, continuing, reset_target):
+def test_reference_point_maze_on_oracle_physics(layout, reward_type, continuing, reset_target, tape):
     """point_maze.py:375-406 (reset / step), point.py:55-77 (PointEnv.step: action clip, velocity clip, do_simulation), maze_v4.py:148-242
     (Maze.make_maze), :278-418 (goal / reset sampling, noise, reward, termination, update_goal) executed as is; only gymnasium's MujocoEnv
     base class is a stand-in (see ref_harness)."""
@@ -174,7 +188,7 @@ def test_reference_point_maze_on_oracle_physics(layout, reward_type, continuing,
     a_env = OraclePointMazeEnv(model, maze, reward_type, continuing, reset_target=reset_target)
     b_env = OraclePointMazeEnv(model, maze, reward_type, continuing, reset_target=reset_target)
     xml = os.path.join(ref_harness.REF_ROOT, "gymnasium_robotics", "envs", "assets", "point", "point.xml")
-    ref = ref_harness.point_maze_on_oracle(b_env, maze_spec.MAPS[layout], reward_type, continuing, reset_target, xml)
+    ref = tape.env(b_env, lambda: ref_harness.point_maze_on_oracle(b_env, maze_spec.MAPS[layout], reward_type, continuing, reset_target, xml))
     # the reference's own Maze against this package's
     assert np.allclose(np.array(ref.maze.unique_goal_locations), np.array(maze.unique_goal_locations)) and np.allclose(np.array(ref.maze.unique_reset_locations), np.array(maze.unique_reset_locations))
     rng = np.random.default_rng(0)
@@ -204,7 +218,7 @@ def test_reference_point_maze_on_oracle_physics(layout, reward_type, continuing,
 
 @pytest.mark.parametrize("layout,reward_type,continuing,reset_target", [("UMaze", "sparse", True, False), ("Large_Diverse_GR", "sparse", True, False),
                                                                         ("Medium_Diverse_G", "dense", False, False), ("Large_Diverse_G", "sparse", True, True)])
-def test_reference_ant_maze_on_oracle_physics(layout, reward_type, continuing, reset_target):
+def test_reference_ant_maze_on_oracle_physics(layout, reward_type, continuing, reset_target, tape):
     """ant_maze_v5.py:282-320 (AntMazeEnv.reset / step / _get_obs / update_target_site_pos) and everything they inherit from MazeEnv
     (maze_v4.py:148-242 Maze.make_maze at scaling 4 / height 0.5, :278-418 goal / reset sampling, noise, reward, termination, update_goal) executed
     as is on the oracle's physics; gymnasium's AntEnv [3P] is the documented-behaviour stand-in of ref_harness (obs = qpos | qvel, frame_skip 5,
@@ -221,7 +235,7 @@ def test_reference_ant_maze_on_oracle_physics(layout, reward_type, continuing, r
     a_env = OracleAntMazeEnv(model, maze, reward_type, continuing, reset_target=reset_target)
     b_env = OracleAntMazeEnv(model, maze, reward_type, continuing, reset_target=reset_target)
     xml = os.path.join(ref_harness.REF_ROOT, "gymnasium_robotics", "envs", "assets", "point", "point.xml")   # make_maze only needs a worldbody to append the wall geoms to
-    ref = ref_harness.ant_maze_on_oracle(b_env, maze_spec.MAPS[layout], reward_type, continuing, reset_target, xml)
+    ref = tape.env(b_env, lambda: ref_harness.ant_maze_on_oracle(b_env, maze_spec.MAPS[layout], reward_type, continuing, reset_target, xml))
     assert np.allclose(np.array(ref.maze.unique_goal_locations), np.array(maze.unique_goal_locations)) and np.allclose(np.array(ref.maze.unique_reset_locations), np.array(maze.unique_reset_locations))
     assert ref.maze.maze_size_scaling == 4 and ref.maze.maze_height == 0.5
     rng = np.random.default_rng(0)
@@ -256,26 +270,29 @@ def test_reference_ant_maze_on_oracle_physics(layout, reward_type, continuing, r
 
 # manipulate_touch_sensors.py:113-138 (_get_obs with the 92 touch readings raw / > 0 / log(x + 1)) executed as is on the oracle's sensor
 # values; the step itself is the reference's BaseRobotEnv.step.
-def _touch_case(mode):
+def _touch_case(mode, tape):
     from gymnasium_robotics_amd.envs.hand import load_hand_block_model
     from oracle.manipulate_oracle import OracleHandBlockEnv
 
     model = load_hand_block_model(touch=True)
     a_env, b_env = OracleHandBlockEnv(model, "ignore", "xyz", "sparse", mode, "block"), OracleHandBlockEnv(model, "ignore", "xyz", "sparse", mode, "block")
     a_env.reset(seed=6); b_env.reset(seed=6)
-    ref = ref_harness.hand_on_oracle(b_env, "manipulate", reward_type="sparse", target_position="ignore", target_rotation="xyz", rotation_threshold=0.1,
-                                     distance_threshold=0.01, ignore_z_target_rotation=False, touch_get_obs=mode, _touch_sensor_id=list(range(92)))
-    from gymnasium_robotics.envs.shadow_dexterous_hand import manipulate_touch_sensors as mts
 
-    ref.__class__ = mts.MujocoManipulateTouchSensorsEnv
-    type(ref.data).sensordata = property(lambda self: self._env.sim.touch)
-    return a_env, b_env, ref
+    def build():
+        ref = ref_harness.hand_on_oracle(b_env, "manipulate", reward_type="sparse", target_position="ignore", target_rotation="xyz", rotation_threshold=0.1,
+                                         distance_threshold=0.01, ignore_z_target_rotation=False, touch_get_obs=mode, _touch_sensor_id=list(range(92)))
+        from gymnasium_robotics.envs.shadow_dexterous_hand import manipulate_touch_sensors as mts
+
+        ref.__class__ = mts.MujocoManipulateTouchSensorsEnv
+        type(ref.data).sensordata = property(lambda self: self._env.sim.touch)
+        return ref
+    return a_env, b_env, tape.env(b_env, build)
 
 
 @pytest.mark.parametrize("mode", ["sensordata", "boolean", "log"])
-def test_reference_touch_observation(mode):
+def test_reference_touch_observation(mode, tape):
     ref_harness.install()
-    a_env, b_env, ref = _touch_case(mode)
+    a_env, b_env, ref = _touch_case(mode, tape)
     rng = np.random.default_rng(2)
     fired = 0
     for t in range(5):
@@ -288,7 +305,7 @@ def test_reference_touch_observation(mode):
 
 
 @pytest.mark.parametrize("reward_type", ["dense", "sparse"])
-def test_reference_adroit_hammer_on_oracle_physics(reward_type):
+def test_reference_adroit_hammer_on_oracle_physics(reward_type, tape):
     """adroit_hammer.py:291-378 executed as is (action scaling, do_simulation(a, 5), the 46-vector observation with quat2euler and the clipped
     velocities / touch reading, dense and sparse reward, success flag, reset_model's board-height draw written to model.body_pos) on the oracle
     physics: identical to the restated task layer (oracle/adroit_oracle.py) step for step."""
@@ -298,7 +315,7 @@ def test_reference_adroit_hammer_on_oracle_physics(reward_type):
     ref_harness.install()
     model = load_adroit_hammer_model()
     a_env, b_env = OracleAdroitHammerEnv(model, reward_type), OracleAdroitHammerEnv(model, reward_type)
-    ref = ref_harness.adroit_hammer_on_oracle(b_env, reward_type)
+    ref = tape.env(b_env, lambda: ref_harness.adroit_hammer_on_oracle(b_env, reward_type))
     rng = np.random.default_rng(4)
     for seed in (0, 5):
         oa, _ = a_env.reset(seed=seed)
@@ -314,7 +331,7 @@ def test_reference_adroit_hammer_on_oracle_physics(reward_type):
 
 @pytest.mark.parametrize("task", ["door", "pen", "relocate"])
 @pytest.mark.parametrize("reward_type", ["dense", "sparse"])
-def test_reference_adroit_door_pen_relocate_on_oracle_physics(task, reward_type):
+def test_reference_adroit_door_pen_relocate_on_oracle_physics(task, reward_type, tape):
     """adroit_door.py:281-392, adroit_pen.py:288-419, adroit_relocate.py:290-410 executed as they are (action scaling, do_simulation(a, 5), the 39 /
     45 / 39-vector observations, dense and sparse rewards, success flags, reset_model's draws written to model.body_pos / body_quat / site_pos,
     get_env_state / set_env_state) on the oracle physics: identical to the restated task layer (oracle/adroit_oracle.py) step for step, bit for bit."""
@@ -324,7 +341,7 @@ def test_reference_adroit_door_pen_relocate_on_oracle_physics(task, reward_type)
     ref_harness.install()
     model = load_adroit_model(task)
     a_env, b_env = OracleAdroitEnv(model, reward_type, task), OracleAdroitEnv(model, reward_type, task)
-    ref = ref_harness.adroit_on_oracle(b_env, task, reward_type)
+    ref = tape.env(b_env, lambda: ref_harness.adroit_on_oracle(b_env, task, reward_type))
     rng = np.random.default_rng(4)
     nu = model.dim("nu")
     for seed in (0, 5):
@@ -348,7 +365,7 @@ def test_reference_adroit_door_pen_relocate_on_oracle_physics(task, reward_type)
     assert np.array_equal(ref._get_obs()[:nj], before[:nj])
 
 
-def test_reference_relocate_reset_keeps_the_components_it_does_not_redraw():
+def test_reference_relocate_reset_keeps_the_components_it_does_not_redraw(tape):
     """adroit_relocate.py:353-356: reset_model redraws model.body_pos[Object] x / y only; a z that set_env_state wrote (:405-407) persists across resets in the
     reference.  The restated task layer (adroit_spec.sample_reset_batch(current=...), used by the oracle env and by AdroitVecEnv) must do the same."""
     from gymnasium_robotics_amd.envs.adroit_spec import load_adroit_model
@@ -357,7 +374,7 @@ def test_reference_relocate_reset_keeps_the_components_it_does_not_redraw():
     ref_harness.install()
     model = load_adroit_model("relocate")
     a_env, b_env = OracleAdroitEnv(model, "dense", "relocate"), OracleAdroitEnv(model, "dense", "relocate")
-    ref = ref_harness.adroit_on_oracle(b_env, "relocate", "dense")
+    ref = tape.env(b_env, lambda: ref_harness.adroit_on_oracle(b_env, "relocate", "dense"))
     a_env.reset(seed=3); ref.reset(seed=3)
     st = ref.get_env_state()
     st["obj_pos"] = st["obj_pos"] + np.array([0.0, 0.0, 0.07])         # the ball 7 cm higher: lands in model.body_pos[Object, 2]
@@ -371,7 +388,7 @@ def test_reference_relocate_reset_keeps_the_components_it_does_not_redraw():
 
 
 @pytest.mark.parametrize("kwargs", [{}, {"tasks_to_complete": ["microwave", "kettle"], "remove_task_when_completed": False}])
-def test_reference_kitchen_on_oracle_physics(kwargs):
+def test_reference_kitchen_on_oracle_physics(kwargs, tape):
     """franka_env.py:92-171 and kitchen_env.py:340-437 executed as they are (velocity command on the previous noisy reading, position / velocity
     bounds read from franka_config.xml by the reference's own parser, do_simulation(ctrl, 40), both _get_obs with their PCG64 noise draws,
     compute_reward, task bookkeeping, termination) on the oracle physics: identical to the restated task layer (oracle/kitchen_oracle.py), bit for bit."""
@@ -381,7 +398,7 @@ def test_reference_kitchen_on_oracle_physics(kwargs):
     ref_harness.install()
     model = load_kitchen_model()
     a_env, b_env = OracleKitchenEnv(model, **kwargs), OracleKitchenEnv(model, **kwargs)
-    ref = ref_harness.kitchen_on_oracle(b_env)
+    ref = tape.env(b_env, lambda: ref_harness.kitchen_on_oracle(b_env))
     rng = np.random.default_rng(1)
     for seed in (0, 3):
         (oa, ia), (ob, ib) = a_env.reset(seed=seed), ref.reset(seed=seed)

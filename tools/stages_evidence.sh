@@ -1,6 +1,7 @@
 # bench lines of the out-of-phase sub-batch mode (bench.py --stages 2) + the families not yet measured with it:   sh tools/stages_evidence.sh   (ON the GPU box)
 mkdir -p gpurun_out
-python bench.py --stages 2 > gpurun_out/bench_r05_fetch_stages2.json 2>/dev/null
+E=${EVIDENCE_DIR:-evidence}; mkdir -p "$E"      # the bench line that carries the CPU baseline leg (--full)
+python bench.py --full --stages 2 > "$E"/bench_r05_fetch_stages2.json 2>/dev/null
 python bench.py --stages 2 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/bench_r05_fetch_stages2_driver_args.json 2>/dev/null
 python bench.py --stages 2 --worlds-per-gpu 8192 --no-cpu-baseline > gpurun_out/bench_r05_fetch_8192_stages2.json 2>/dev/null
 python bench.py --stages 2 --workload antmaze --no-cpu-baseline > gpurun_out/bench_r05_antmaze_stages2.json 2>/dev/null
