@@ -1,0 +1,221 @@
+"""Python side of the env-level C ABI of the Fetch family (include/grx_env.h, libgrx_env.so).
+
+    python -m gymnasium_robotics_amd.env_capi describe FetchPickAndPlace-v4 pick.grxenv
+
+writes the environment description file grx_env_create reads.  The file is built from the packaged model (models/*.npz) alone:
+no GPU, no asset tree.  This module also holds the ctypes loader of libgrx_env.so, struct mirrors of grx_env.h and a parser of the
+section tables both files use.
+
+Container (little endian; the description file and the state blob of grx_env_get_state share it):
+
+    header   80 bytes   magic[8] ("GRXENVD\\0" description / "GRXENVS\\0" state), u32 version, u32 n_sections, env_id[48] (NUL-padded),
+                        i64 num_envs (0 in a description), u64 total_bytes (the whole file)
+    table    n_sections x 40 bytes: name[24] (NUL-padded), u64 offset (from the start of the file), u64 bytes
+    payload  the sections, each at an 8-byte aligned offset
+
+Sections of a description (version 1):
+
+    H I F                 model.pack() of the model after FetchVecEnv.__init__'s mocap-weld eq_data edit, at FETCH_CAPACITY (int32, int32, float64)
+    H_rerun I_rerun F_rerun   the same model at RERUN_CAPACITY (the overflow re-run's tables)
+    task                  the FetchTaskStruct bytes (struct grx_fetch_task)
+    dims                  int32 [8]: nq, nv, nmocap, nu, obs_dim, obj_qadr (-1: no object), max_episode_steps, 0
+    consts                float64 [11]: has_object, block_gripper, target_in_the_air, gripper_extra_height, target_offset[3], obj_range, target_range,
+                          distance_threshold (FETCH_TASKS), dt (N_SUBSTEPS x timestep)
+    fast_caps             int32 [3]: maxefc, jpool, maxcon of the FETCH_CAPACITY tables (the overflow re-run's soft thresholds)
+    q0                    float64 [nq]: qpos0 with the task's initial_qpos applied
+    mocap0                float64 [7 nmocap]: mocap_pos0 | mocap_quat0
+"""
+import ctypes
+import os
+import struct
+import sys
+
+import numpy as np
+
+DESC_MAGIC, STATE_MAGIC = b"GRXENVD\0", b"GRXENVS\0"
+DESC_VERSION, STATE_VERSION = 1, 1
+HEADER = struct.Struct("<8sII48sqQ")       # 80 bytes
+ENTRY = struct.Struct("<24sQQ")            # 40 bytes
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "_lib", "libgrx_env.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_env.h")
+_lib = None
+
+AUTORESET = {"next_step": 0, "same_step": 1, "disabled": 2}
+
+
+# ------------------------------------------------------------------ container
+def pack_sections(magic, version, env_id, num_envs, sections):
+    """sections: list of (name, bytes-like) -> the whole file as bytes"""
+    n = len(sections)
+    off = HEADER.size + n * ENTRY.size
+    table, payload = [], []
+    for name, data in sections:
+        data = bytes(data)
+        off = -(-off // 8) * 8
+        table.append((name, off, len(data)))
+        payload.append((off, data))
+        off += len(data)
+    buf = bytearray(off)
+    HEADER.pack_into(buf, 0, magic, version, n, env_id.encode(), int(num_envs), off)
+    for k, (name, o, b) in enumerate(table):
+        ENTRY.pack_into(buf, HEADER.size + k * ENTRY.size, name.encode(), o, b)
+    for o, data in payload:
+        buf[o: o + len(data)] = data
+    return bytes(buf)
+
+
+def section_table(blob):
+    """-> (header dict, {name: (offset, bytes)}) of a description file or a state blob (no validation beyond the bounds)"""
+    blob = bytes(blob)
+    magic, version, n, env_id, num_envs, total = HEADER.unpack_from(blob, 0)
+    head = dict(magic=magic, version=version, env_id=env_id.rstrip(b"\0").decode(), num_envs=num_envs, total_bytes=total)
+    table = {}
+    for k in range(n):
+        name, off, size = ENTRY.unpack_from(blob, HEADER.size + k * ENTRY.size)
+        if off + size > len(blob):
+            raise ValueError(f"section {name!r} runs past the end of the blob")
+        table[name.rstrip(b"\0").decode()] = (off, size)
+    return head, table
+
+
+def parse_sections(blob):
+    """-> (header dict, {name: bytes})"""
+    blob = bytes(blob)
+    head, table = section_table(blob)
+    return head, {k: blob[o: o + b] for k, (o, b) in table.items()}
+
+
+def state_arrays(blob, obs_dim=None):
+    """the sections of a grx_env_get_state blob as numpy arrays (float32 rows, int32 / uint8 / int64 / uint64 where the state holds those)"""
+    head, sec = parse_sections(blob)
+    n = head["num_envs"]
+    dtypes = {"success": np.uint8, "status": np.int32, "cost": np.int32, "order": np.int32, "rng": np.uint64, "elapsed": np.int64, "needs_reset": np.uint8, "has_reset": np.uint8}
+    out = {}
+    for k, v in sec.items():
+        a = np.frombuffer(v, dtype=dtypes.get(k, np.float32))
+        out[k] = a if k == "has_reset" else a.reshape(n, -1)
+    return head, out
+
+
+# ------------------------------------------------------------------ description file
+def describe(env_id):
+    """the description file of `env_id` as bytes (packaged model; no GPU)"""
+    from .core import RERUN_CAPACITY
+    from .envs.fetch import FETCH_CAPACITY, load_fetch_model
+    from .envs.fetch_spec import DISTANCE_THRESHOLD, FETCH_TASKS, MAX_EPISODE_STEPS, make_fetch_task, parse_env_id
+
+    task, reward_type = parse_env_id(env_id)
+    cfg = FETCH_TASKS[task]
+    model = load_fetch_model(task).copy()
+    eq = model.tables["eq_data"]      # reset_mocap_welds, as FetchVecEnv.__init__
+    eq[model.tables["eq_type"] == 1, :7] = [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]
+    t = make_fetch_task(model, task, reward_type)
+    T, names = model.tables, model.names
+    jq = T["jnt_qposadr"].ravel()
+    q0 = T["qpos0"].astype(np.float64).copy()      # FetchVecEnv._env_setup
+    for name, v in cfg["initial_qpos"].items():
+        v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        a = int(jq[names["joint"][name]])
+        q0[a: a + len(v)] = v
+    mocap0 = np.concatenate([T["mocap_pos0"].ravel(), T["mocap_quat0"].ravel()]).astype(np.float64)
+    obj_qadr = int(jq[names["joint"]["object0:joint"]]) if cfg["has_object"] else -1
+    H, I, F = model.pack()
+    Hr, Ir, Fr = model.with_capacity(**RERUN_CAPACITY).pack()
+    toff = np.broadcast_to(np.asarray(cfg["target_offset"], dtype=np.float64), (3,))
+    dims = np.array([model.dim("nq"), model.dim("nv"), model.dim("nmocap"), model.dim("nu"), int(t.obs_dim), obj_qadr, MAX_EPISODE_STEPS, 0], np.int32)
+    consts = np.array([cfg["has_object"], cfg["block_gripper"], cfg["target_in_the_air"], cfg["gripper_extra_height"], *toff, cfg["obj_range"], cfg["target_range"],
+                       DISTANCE_THRESHOLD, float(t.n_substeps) * model.opt("timestep")], np.float64)
+    caps = np.array([FETCH_CAPACITY["maxefc"], FETCH_CAPACITY["jpool"], FETCH_CAPACITY["maxcon"]], np.int32)
+    f = lambda a, dt: np.ascontiguousarray(a, dtype=dt).tobytes()
+    sections = [("H", f(H, np.int32)), ("I", f(I, np.int32)), ("F", f(F, np.float64)), ("H_rerun", f(Hr, np.int32)), ("I_rerun", f(Ir, np.int32)), ("F_rerun", f(Fr, np.float64)),
+                ("task", bytes(t)), ("dims", dims.tobytes()), ("consts", consts.tobytes()), ("fast_caps", caps.tobytes()), ("q0", f(q0, np.float64)),
+                ("mocap0", f(mocap0, np.float64))]
+    return pack_sections(DESC_MAGIC, DESC_VERSION, env_id, 0, sections)
+
+
+def write_env_desc(env_id, path):
+    blob = describe(env_id)
+    with open(path, "wb") as fh:
+        fh.write(blob)
+    return path
+
+
+def read_env_desc(path):
+    """-> (header, dict of numpy arrays / bytes) of a description file"""
+    with open(path, "rb") as fh:
+        head, sec = parse_sections(fh.read())
+    out = {k: np.frombuffer(sec[k], np.int32) for k in ("H", "I", "H_rerun", "I_rerun", "dims", "fast_caps")}
+    out.update({k: np.frombuffer(sec[k], np.float64) for k in ("F", "F_rerun", "consts", "q0", "mocap0")})
+    out["task"] = sec["task"]
+    return head, out
+
+
+# ------------------------------------------------------------------ grx_env.h mirrors
+class EnvConfig(ctypes.Structure):
+    _fields_ = [("autoreset_mode", ctypes.c_int), ("max_episode_steps", ctypes.c_int), ("seed_offset", ctypes.c_uint64)]
+
+
+class EnvOutputs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("num_envs", "obs_dim", "goal_dim", "packed_dim")] + [
+        (n, ctypes.c_void_p) for n in ("obs", "achieved", "desired", "reward", "success", "status", "packed", "terminated", "truncated")] + [
+        ("n_final", ctypes.c_int), ("final_idx", ctypes.c_void_p), ("final_rows", ctypes.c_void_p)]
+
+
+class EnvHostOutputs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "achieved", "desired", "reward", "success", "status", "packed", "terminated", "truncated", "n_final", "final_idx", "final_rows")]
+
+
+def lib():
+    """libgrx_env.so with its argument types (loads libgrx_hip.so first, through the package loader: one HIP runtime, the one torch uses)"""
+    global _lib
+    if _lib is None:
+        from . import _native
+
+        _native.lib()
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        L = ctypes.CDLL(LIB_PATH)
+        vp, ci, P = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER
+        L.grx_env_create.argtypes = [ctypes.c_char_p, ci, ci, P(EnvConfig), P(vp)]
+        L.grx_env_destroy.argtypes = [vp]
+        L.grx_env_dims.argtypes = [vp, P(ci), P(ci), P(ci), P(ctypes.c_double)]
+        L.grx_env_reset.argtypes = [vp, vp, vp, vp]
+        L.grx_env_step.argtypes = [vp, vp, vp]
+        L.grx_env_outputs.argtypes = [vp, P(EnvOutputs)]
+        L.grx_env_copy_outputs.argtypes = [vp, P(EnvHostOutputs)]
+        L.grx_env_compute_reward.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp]
+        L.grx_env_state_size.argtypes = [vp, P(ctypes.c_size_t)]
+        L.grx_env_get_state.argtypes = [vp, vp, ctypes.c_size_t]
+        L.grx_env_set_state.argtypes = [vp, vp, ctypes.c_size_t]
+        L.grx_env_seed_pcg64.argtypes = [vp, ci, vp]
+        L.grx_env_last_error.restype = ctypes.c_char_p
+        _lib = L
+    return _lib
+
+
+def check(rc):
+    if rc != 0:
+        raise RuntimeError(f"libgrx_env ({rc}): " + lib().grx_env_last_error().decode())
+
+
+def seed_pcg64(seeds):
+    """numpy's PCG64(SeedSequence(s)) positions through the library: uint64 [n, 4] (state_hi, state_lo, inc_hi, inc_lo)"""
+    s = np.ascontiguousarray(seeds, dtype=np.uint64)
+    out = np.zeros((len(s), 4), np.uint64)
+    check(lib().grx_env_seed_pcg64(s.ctypes.data, len(s), out.ctypes.data))
+    return out
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if len(argv) != 3 or argv[0] != "describe":
+        print("usage: python -m gymnasium_robotics_amd.env_capi describe <env id> <path>", file=sys.stderr)
+        return 2
+    write_env_desc(argv[1], argv[2])
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,113 @@
+/* grx_env.h -- env-level C ABI of the Fetch family (libgrx_env.so, on top of libgrx_hip.so).
+ *
+ * One handle = N Fetch worlds of one id (FetchReach / Push / Slide / PickAndPlace, sparse or Dense) on one GPU, stepped with the
+ * same launch group FetchVecEnv(output="torch").step issues (envs/fetch.py): cost-ordered split step launches, the entry-mode
+ * overflow re-run on the large tables, the same-step reset ahead of the step on a side stream (committed behind it), next-step
+ * resets through the masked step, and the time limit / autoreset bookkeeping on the host.  A caller that is not Python steps
+ * a Fetch world through these calls alone; INTEGRATION.md has the worked example (tests/capi/fetch_rollout.c).
+ *
+ * The handle is built from an environment description file written by
+ *     python -m gymnasium_robotics_amd.env_capi describe <env id> <path>
+ * (packed model tables, task struct, task constants, initial state: see gymnasium_robotics_amd/env_capi.py for the layout).
+ *
+ * Conventions (those of grx_capi.h): every call returns 0 or a negative code and leaves a thread-local message for
+ * grx_env_last_error(); nothing in grx_env_step waits for the device; a handle is not re-entrant; the pointers
+ * grx_env_outputs hands out stay valid until the next grx_env_step / grx_env_reset / grx_env_set_state.
+ * "stream" arguments are hipStream_t (NULL = the null stream); the handle owns one more stream of its own (the ahead reset).
+ */
+#ifndef GRX_ENV_H
+#define GRX_ENV_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define GRX_ENV_DESC_VERSION 1
+#define GRX_ENV_STATE_VERSION 1
+
+/* error codes (all calls: 0 = success) */
+#define GRX_ENV_EINVAL -1     /* NULL pointer, bad size, call out of order (step before reset) */
+#define GRX_ENV_EDESC -2      /* description file: unreadable, wrong magic / version, truncated, inconsistent */
+#define GRX_ENV_ENODEV -3     /* no HIP device (or the requested one does not exist) */
+#define GRX_ENV_EHIP -4       /* a HIP runtime call or a libgrx_hip.so entry point failed */
+#define GRX_ENV_ESTATE -5     /* state blob of another id / size / version, or malformed */
+
+#define GRX_ENV_NEXT_STEP 0
+#define GRX_ENV_SAME_STEP 1
+#define GRX_ENV_DISABLED 2
+
+typedef struct grx_env grx_env;
+
+typedef struct grx_env_config {
+  int autoreset_mode;      /* GRX_ENV_NEXT_STEP (gymnasium's default), GRX_ENV_SAME_STEP, GRX_ENV_DISABLED */
+  int max_episode_steps;   /* <= 0: no time limit.  (A NULL config takes the description file's limit, next-step autoreset, offset 0.) */
+  uint64_t seed_offset;    /* FetchVecEnv's seed_offset: the caller's convention for per-world seeds (seeds[i] = s + seed_offset + i);
+                            * grx_env_reset uses the seeds it is given as they are */
+} grx_env_config;
+
+/* Device outputs of the last step / reset (rows world-major, fp32 unless noted). */
+typedef struct grx_env_device_outputs {
+  int num_envs, obs_dim, goal_dim, packed_dim;   /* packed_dim = obs_dim + 8 */
+  const float* obs;                /* device [N, obs_dim] */
+  const float* achieved;           /* device [N, 3] */
+  const float* desired;            /* device [N, 3] */
+  const float* reward;             /* device [N] */
+  const uint8_t* success;          /* device [N] */
+  const int32_t* status;           /* device [N]: GRX_STATUS_* bits of the last launch (low half) and sticky (high half), grx_capi.h */
+  const float* packed;             /* device [N, packed_dim]: [obs | achieved | desired | reward | success] */
+  const uint8_t* terminated;       /* host [N] (always 0: Fetch episodes end by the time limit only) */
+  const uint8_t* truncated;        /* host [N] */
+  int n_final;                     /* same-step autoreset: worlds the last step finished and reset */
+  const int32_t* final_idx;        /* host [n_final], ascending */
+  const float* final_rows;         /* device [n_final, packed_dim]: their terminal packed rows (info["final_obs"]) */
+} grx_env_device_outputs;
+
+/* Host destinations of grx_env_copy_outputs; any pointer may be NULL (not copied). */
+typedef struct grx_env_host_outputs {
+  float* obs;            /* [N, obs_dim] */
+  float* achieved;       /* [N, 3] */
+  float* desired;        /* [N, 3] */
+  float* reward;         /* [N] */
+  uint8_t* success;      /* [N] */
+  int32_t* status;       /* [N] */
+  float* packed;         /* [N, obs_dim + 8] */
+  uint8_t* terminated;   /* [N] */
+  uint8_t* truncated;    /* [N] */
+  int* n_final;          /* [1] */
+  int32_t* final_idx;    /* [N] (n_final written) */
+  float* final_rows;     /* [N, obs_dim + 8] (n_final rows written) */
+} grx_env_host_outputs;
+
+/* Parses and validates the whole description file before the device is touched, creates the two models (fast and re-run tables),
+ * allocates the buffers, runs the _env_setup forward passes and seeds every world from OS entropy (numpy's SeedSequence(None)).
+ * device: HIP device index.  cfg: NULL = defaults (see grx_env_config). */
+int grx_env_create(const char* desc_path, int num_envs, int device, const grx_env_config* cfg, grx_env** out);
+int grx_env_destroy(grx_env* e);
+int grx_env_dims(const grx_env* e, int* obs_dim, int* goal_dim, int* act_dim, double* dt);
+/* Episode reset of the worlds with mask[i] != 0 (host [N]; NULL = all), gymnasium's reset / reset_mask.  seeds (host [N] or NULL = keep the
+ * worlds' streams): world i's stream becomes PCG64(SeedSequence(seeds[i])), so seeds[i] = s + seed_offset + i gives world i the state
+ * FetchVecEnv.reset(seed=s) gives it.  Enqueued on `stream`. */
+int grx_env_reset(grx_env* e, const uint8_t* mask, const uint64_t* seeds, void* stream);
+/* One env.step() of every world: actions [N, 4] fp32, device or pinned host memory.  Never waits for the device. */
+int grx_env_step(grx_env* e, const float* actions, void* stream);
+int grx_env_outputs(const grx_env* e, grx_env_device_outputs* out);
+/* The outputs into host memory (synchronises the handle's device). */
+int grx_env_copy_outputs(grx_env* e, grx_env_host_outputs* out);
+/* GoalEnv.compute_reward on a batch (HER): achieved / desired device [batch, 3], out device [batch]. */
+int grx_env_compute_reward(const grx_env* e, const float* achieved, const float* desired, int64_t batch, float* out, void* stream);
+/* Checkpoint / resume: everything that determines the future of the worlds at a step boundary, as one blob (header with id, N and
+ * version, then a named-section table).  get / set synchronise the device; set refuses a blob of another id, N, size or version. */
+int grx_env_state_size(const grx_env* e, size_t* bytes);
+int grx_env_get_state(grx_env* e, void* host, size_t bytes);
+int grx_env_set_state(grx_env* e, const void* host, size_t bytes);
+/* numpy's PCG64(SeedSequence(seeds[i])) stream positions: states[i] = (state_hi, state_lo, inc_hi, inc_lo).  Host only. */
+int grx_env_seed_pcg64(const uint64_t* seeds, int n, uint64_t* states);
+const char* grx_env_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
