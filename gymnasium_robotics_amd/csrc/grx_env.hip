@@ -1,5 +1,6 @@
-// grx_env.hip -- env-level C ABI of the Fetch family (include/grx_env.h): the launch group of FetchVecEnv(output="torch").step (envs/fetch.py)
-// in C++, on top of libgrx_hip.so's entry points, plus the few small kernels that replace the torch operations of that step.
+// grx_env.hip -- env-level C ABI (include/grx_env.h).  Two handle kinds behind the same entry points: the Fetch family below -- the launch group of
+// FetchVecEnv(output="torch").step (envs/fetch.py) in C++, on top of libgrx_hip.so's entry points, plus the few small kernels that replace the torch operations of that
+// step -- and the maze family (PointMaze / AntMaze) in grx_env_maze.inc, whose episode bookkeeping runs on the device.
 //
 // One step, as envs/fetch.py issues it by default:
 //   next-step resets pending:  mask <- 1, 0 for the pending worlds (grx_env_mask_kernel); the masked step launch
@@ -190,18 +191,25 @@ int take(const Container& c, const char* name, int64_t expect, std::vector<T>* d
   return 0;
 }
 
-int parse_desc(const char* path, Desc* d) {
+// the file into buf and its section table into c (which points into buf)
+int read_desc(const char* path, std::vector<uint8_t>* bufp, Container* cp) {
   FILE* f = std::fopen(path, "rb");
   if (!f) return fail(GRX_ENV_EDESC, std::string("environment description: cannot open ") + path);
-  std::vector<uint8_t> buf;
+  std::vector<uint8_t>& buf = *bufp;
   uint8_t chunk[1 << 16];
   size_t k;
   while ((k = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + k);
   std::fclose(f);
-  Container c;
+  Container& c = *cp;
   ENV_TRY(parse_container(buf.data(), buf.size(), kDescMagic, GRX_ENV_DESC_VERSION, "environment description", GRX_ENV_EDESC, &c));
   c.h.env_id[47] = 0;
-  d->env_id = c.h.env_id;
+  return 0;
+}
+
+struct MazeEnv;      // the maze handle (grx_env_maze.inc)
+void maze_free(MazeEnv* m);
+
+int parse_desc(const Container& c, Desc* d) {
   ENV_TRY(take<int32_t>(c, "H", -1, &d->H));
   ENV_TRY(take<int32_t>(c, "I", -1, &d->I));
   ENV_TRY(take<double>(c, "F", -1, &d->F));
@@ -228,6 +236,7 @@ struct grx_env {
   int device = 0, n = 0, mode = GRX_ENV_NEXT_STEP, max_steps = 0;
   uint64_t seed_offset = 0;
   Desc d;
+  MazeEnv* mz = nullptr;      // a maze handle: the fields below the model handle `h` are the Fetch handle's and stay unused
   grx_model *h = nullptr, *hbig = nullptr;
   int nq = 0, nv = 0, nmocap = 0, nu = 0, obs_dim = 0, pdim = 0, obj_qadr = -1;
   double g0[3] = {0, 0, 0}, toff[3] = {0, 0, 0}, height_offset = 0, dt = 0;
@@ -281,6 +290,7 @@ struct grx_env {
     for (void* p : allocs) (void)hipFree(p);
     if (h) grx_model_destroy(h);
     if (hbig) grx_model_destroy(hbig);
+    maze_free(mz);
   }
 
   template <class T>
@@ -476,7 +486,26 @@ int alloc_all(grx_env* e) {
 // the device rows and host arrays of a state blob, in blob order
 struct Section { const char* name; void* ptr; size_t bytes; bool host; };
 
+#include "grx_env_maze.inc"
+
+std::vector<Section> maze_sections(grx_env* e) {
+  MazeEnv& m = *e->mz;
+  const size_t n = e->n;
+  std::vector<Section> s = {
+      {"qpos", m.qpos, n * m.nq * 4, false}, {"qvel", m.qvel, n * m.nv * 4, false}, {"qacc_ws", m.qacc_ws, n * m.nv * 4, false}, {"goal", m.goal, n * 8, false},
+      {"obs", m.obs, n * e->obs_dim * 4, false}, {"achieved", m.achieved, n * 8, false}, {"reward", m.reward, n * 4, false}, {"success", m.success, n, false},
+      {"status", m.status, n * 4, false}, {"packed", m.packed, n * e->pdim * 4, false}, {"desired", m.desired, n * 8, false}, {"rng", m.rng, n * 40, false},
+      {"mask", m.mask, n, false}};
+  // the time-limit counters: on the host where the host keeps them (MazeEnv::host_book), else the device's
+  if (m.host_book) { s.push_back({"elapsed", m.h_elapsed.data(), n * 8, true}); s.push_back({"needs_reset", m.h_needs_reset.data(), n, true}); }
+  else { s.push_back({"elapsed", m.elapsed, n * 8, false}); s.push_back({"needs_reset", m.needs_reset, n, false}); }
+  if (m.split > 1) s.push_back({"split_state", m.split_state, n * 8, false});
+  s.push_back({"has_reset", &e->has_reset, 1, true});
+  return s;
+}
+
 std::vector<Section> state_sections(grx_env* e) {
+  if (e->mz) return maze_sections(e);
   const size_t n = e->n;
   std::vector<Section> s = {
       {"qpos", e->qpos, n * e->nq * 4, false}, {"qvel", e->qvel, n * e->nv * 4, false}, {"qacc_ws", e->qacc_ws, n * e->nv * 4, false},
@@ -527,12 +556,35 @@ extern "C" int grx_env_create(const char* desc_path, int num_envs, int device, c
   grx_env* e = new grx_env();
   e->n = num_envs;
   e->device = device;
-  int rc = parse_desc(desc_path, &e->d);      // the whole file, before the device is touched
-  if (rc != 0) { delete e; return rc; }
+  int rc = [&]() -> int {      // the whole file, before the device is touched
+    std::vector<uint8_t> buf;
+    Container c;
+    std::string family;
+    ENV_TRY(read_desc(desc_path, &buf, &c));
+    e->d.env_id = c.h.env_id;
+    if (desc_is_maze(c, &family)) {
+      e->mz = new MazeEnv();
+      return parse_maze_desc(c, &e->mz->d);
+    }
+    if (family != "fetch") return fail(GRX_ENV_EDESC, "environment description: unknown family '" + family + "' (this library reads fetch and maze descriptions)");
+    return parse_desc(c, &e->d);
+  }();
+  if (rc != 0) { std::string msg = g_err; delete e; g_err = msg; return rc; }
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { delete e; return fail(GRX_ENV_ENODEV, "grx_env_create: no HIP device"); }
   if (device < 0 || device >= count) { delete e; return fail(GRX_ENV_ENODEV, "grx_env_create: no HIP device " + std::to_string(device) + " (" + std::to_string(count) + " visible)"); }
   DeviceGuard g(device);
+  if (e->mz) {
+    rc = maze_create(e, cfg);
+    if (rc != 0) {
+      std::string msg = g_err;
+      delete e;
+      g_err = msg;
+      return rc;
+    }
+    *out = e;
+    return 0;
+  }
   const Desc& d = e->d;
   e->nq = d.dims[0]; e->nv = d.dims[1]; e->nmocap = d.dims[2]; e->nu = d.dims[3]; e->obs_dim = d.dims[4]; e->obj_qadr = d.dims[5];
   e->pdim = e->obs_dim + 8;
@@ -577,8 +629,8 @@ extern "C" int grx_env_destroy(grx_env* e) {
 extern "C" int grx_env_dims(const grx_env* e, int* obs_dim, int* goal_dim, int* act_dim, double* dt) {
   if (!e) return fail(GRX_ENV_EINVAL, "grx_env_dims: NULL handle");
   if (obs_dim) *obs_dim = e->obs_dim;
-  if (goal_dim) *goal_dim = 3;
-  if (act_dim) *act_dim = 4;
+  if (goal_dim) *goal_dim = e->mz ? 2 : 3;
+  if (act_dim) *act_dim = e->mz ? e->mz->nu : 4;
   if (dt) *dt = e->dt;
   return 0;
 }
@@ -587,6 +639,7 @@ extern "C" int grx_env_reset(grx_env* e, const uint8_t* mask, const uint64_t* se
   if (!e) return fail(GRX_ENV_EINVAL, "grx_env_reset: NULL handle");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
+  if (e->mz) return maze_reset(e, mask, seeds, s);
   auto& L = e->list;
   L.clear();
   for (int i = 0; i < e->n; ++i)
@@ -617,6 +670,7 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
   if (!e->has_reset) return fail(GRX_ENV_EINVAL, "grx_env_step: cannot step before grx_env_reset");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
+  if (e->mz) return maze_step(e, actions, s);
   const int n = e->n;
   ENV_HIP(hipMemcpyAsync(e->action, actions, (size_t)n * 16, hipMemcpyDefault, s));
   auto& pending = e->list;
@@ -702,6 +756,7 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
 
 extern "C" int grx_env_outputs(const grx_env* e, grx_env_device_outputs* out) {
   if (!e || !out) return fail(GRX_ENV_EINVAL, "grx_env_outputs: NULL argument");
+  if (e->mz) return maze_outputs(e, out);
   out->num_envs = e->n; out->obs_dim = e->obs_dim; out->goal_dim = 3; out->packed_dim = e->pdim;
   out->obs = e->obs; out->achieved = e->achieved; out->desired = e->goal; out->reward = e->reward; out->success = e->success; out->status = e->status; out->packed = e->packed;
   out->terminated = e->terminated.data(); out->truncated = e->truncated.data();
@@ -712,6 +767,7 @@ extern "C" int grx_env_outputs(const grx_env* e, grx_env_device_outputs* out) {
 extern "C" int grx_env_copy_outputs(grx_env* e, grx_env_host_outputs* out) {
   if (!e || !out) return fail(GRX_ENV_EINVAL, "grx_env_copy_outputs: NULL argument");
   DeviceGuard g(e->device);
+  if (e->mz) return maze_copy_outputs(e, out);
   ENV_HIP(hipDeviceSynchronize());
   const size_t n = e->n;
   auto d2h = [](void* dst, const void* src, size_t bytes) { return (dst && bytes) ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
@@ -734,6 +790,10 @@ extern "C" int grx_env_compute_reward(const grx_env* e, const float* achieved, c
   if (!e || !achieved || !desired || !out) return fail(GRX_ENV_EINVAL, "grx_env_compute_reward: NULL argument");
   if (batch < 0) return fail(GRX_ENV_EINVAL, "grx_env_compute_reward: negative batch");
   DeviceGuard g(e->device);
+  if (e->mz) {
+    ENV_GRX(grx_maze_compute_reward(achieved, desired, batch, e->mz->d.task.goal_radius, e->mz->d.task.sparse_reward, out, stream));
+    return 0;
+  }
   ENV_GRX(grx_fetch_compute_reward(achieved, desired, batch, e->d.task.distance_threshold, e->d.task.sparse_reward, out, stream));
   return 0;
 }
@@ -795,6 +855,7 @@ extern "C" int grx_env_set_state(grx_env* e, const void* host, size_t bytes) {
   }
   ENV_HIP(hipDeviceSynchronize());
   e->has_reset = e->has_reset ? 1 : 0;
+  if (e->mz) { e->mz->flags_live = false; e->mz->success_parked = false; }
   e->n_final = 0;
   e->final_idx.clear();
   std::fill(e->terminated.begin(), e->terminated.end(), 0);

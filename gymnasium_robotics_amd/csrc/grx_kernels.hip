@@ -1802,10 +1802,7 @@ extern "C" int grx_her_mark_resets(const unsigned char* reset_mask, int n_worlds
 }
 
 // maze episode reset for a compacted list of worlds (include/grx_capi.h): one 64-thread workgroup per listed world
-extern "C" __global__ void __launch_bounds__(64)
-grx_maze_reset_kernel(grx_maze_reset_args a, int n_reset) {
-  const int k = blockIdx.x, l = threadIdx.x;
-  if (k >= n_reset) return;
+__device__ __forceinline__ void grx_maze_reset_row(const grx_maze_reset_args& a, int k, int l, float* desired) {
   const int w = a.idx[k];
   const float sx = a.stage[4 * k], sy = a.stage[4 * k + 1], gx = a.stage[4 * k + 2], gy = a.stage[4 * k + 3];
   const int nobs_q = a.nq - a.obs_skip;
@@ -1829,7 +1826,18 @@ grx_maze_reset_kernel(grx_maze_reset_args a, int n_reset) {
       if (!a.keep_outcome) { row[a.obs_dim + 4] = 0.0f; row[a.obs_dim + 5] = succ ? 1.0f : 0.0f; }
     }
     if (!a.keep_outcome) a.reward[w] = 0.0f;     // a reset step reports reward 0 (next-step autoreset): reward[] and the packed row agree
+    if (desired) { desired[2 * (size_t)w] = gx; desired[2 * (size_t)w + 1] = gy; }
   }
+}
+extern "C" __global__ void __launch_bounds__(64)
+grx_maze_reset_kernel(grx_maze_reset_args a, int n_reset) {
+  if ((int)blockIdx.x < n_reset) grx_maze_reset_row(a, (int)blockIdx.x, threadIdx.x, nullptr);
+}
+// the same rows for a list whose length is in device memory: workgroups stride over the list; desired (or NULL): a second copy of the new goal (the goal rows a caller reads)
+__global__ void __launch_bounds__(64)
+grx_maze_reset_list_kernel(grx_maze_reset_args a, const int* __restrict__ count, int max_n, float* desired) {
+  const int n = *count < max_n ? *count : max_n;
+  for (int k = blockIdx.x; k < n; k += gridDim.x) grx_maze_reset_row(a, k, threadIdx.x, desired);
 }
 extern "C" int grx_maze_reset_rows(const grx_maze_reset_args* args, int n_reset, void* stream) {
   if (!args) return fail("grx_maze_reset_rows: null argument");
@@ -2118,10 +2126,11 @@ __device__ __forceinline__ int grx_pcg64_integers_dev(unsigned long long& hi, un
   return (int)(m >> 32);
 }
 __global__ void __launch_bounds__(64)
-grx_maze_sample_kernel(unsigned long long* __restrict__ states, const int* __restrict__ idx, int n, const double* __restrict__ goal_xy, int n_goal, const double* __restrict__ reset_xy,
-                       int n_reset, double noise, double scaling, int fixed_goal, double fgx, double fgy, int fixed_reset, double frx, double fry, float* __restrict__ stage) {
+grx_maze_sample_kernel(unsigned long long* __restrict__ states, const int* __restrict__ idx, int n, const int* __restrict__ count, const double* __restrict__ goal_xy, int n_goal,
+                       const double* __restrict__ reset_xy, int n_reset, double noise, double scaling, int fixed_goal, double fgx, double fgy, int fixed_reset, double frx, double fry,
+                       float* __restrict__ stage) {
   const int k = blockIdx.x * 64 + threadIdx.x;
-  if (k >= n) return;
+  if (k >= n || (count && k >= *count)) return;      // count: the list's length in device memory (grx_maze_sample_resets_list), n then only bounds the grid
   const int w = idx[k];
   unsigned long long hi = states[5 * w], lo = states[5 * w + 1], buf = states[5 * w + 4];
   const unsigned long long ihi = states[5 * w + 2], ilo = states[5 * w + 3];
@@ -2154,8 +2163,8 @@ extern "C" int grx_maze_sample_resets_device(uint64_t* states, const int* idx, i
   if (!states || !idx || !goal_xy || !reset_xy || !stage) return fail("grx_maze_sample_resets_device: null argument");
   if (n_goal < 1 || n_reset < 1) return fail("grx_maze_sample_resets_device: empty cell list");
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(grx_maze_sample_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)states, idx, n, goal_xy, n_goal, reset_xy, n_reset, noise_range,
-                     scaling, fixed_goal_xy ? 1 : 0, fixed_goal_xy ? fixed_goal_xy[0] : 0.0, fixed_goal_xy ? fixed_goal_xy[1] : 0.0, fixed_reset_xy ? 1 : 0,
+  hipLaunchKernelGGL(grx_maze_sample_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)states, idx, n, (const int*)nullptr, goal_xy, n_goal, reset_xy, n_reset,
+                     noise_range, scaling, fixed_goal_xy ? 1 : 0, fixed_goal_xy ? fixed_goal_xy[0] : 0.0, fixed_goal_xy ? fixed_goal_xy[1] : 0.0, fixed_reset_xy ? 1 : 0,
                      fixed_reset_xy ? fixed_reset_xy[0] : 0.0, fixed_reset_xy ? fixed_reset_xy[1] : 0.0, stage);
   HIP_OK(hipGetLastError());
   return 0;
@@ -2259,6 +2268,127 @@ extern "C" int grx_fetch_compute_reward(const float* achieved, const float* desi
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(grx_fetch_reward_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, achieved, desired, (long long)batch,
                      distance_threshold, sparse, reward_out);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// ---- maze episode bookkeeping ON THE DEVICE (include/grx_capi.h, grx_maze_episode_end): what PointMazeVecEnv.step does on the host behind the step launch -- the time limit,
+// termination, MazeEnv.update_goal's redraw (maze_v4.py:400-418) and the list of worlds to reset -- for a caller that must not wait for the device.  ONE workgroup of 1 024
+// threads walks the worlds in chunks of 1 024: the reset list is in ascending world order (wave64 ballot + mbcnt = the rank inside a wave, the 16 wave totals summed through
+// LDS, a running base across the chunks), so no atomic on a shared cursor decides the order.  (gfx950 build: 52 VGPRs, 64 B of LDS, no scratch; the argument block is
+// kept live across the redraw loop and 28 SGPRs spill to VGPR lanes, which costs nothing that matters at one workgroup.)
+__global__ void __launch_bounds__(1024)
+grx_maze_episode_end_kernel(grx_maze_episode_args a, int n_worlds) {
+  __shared__ int wave_total[16];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  int base = 0;
+  for (int start = 0; start < n_worlds; start += 1024) {
+    const int w = start + tid;
+    int listed = 0;
+    if (w < n_worlds) {
+      const int pending = a.needs_reset[w] != 0, stepped = !pending, succ = a.success[w] != 0;
+      long long el = a.elapsed[w] + stepped;
+      const int term = stepped && !a.continuing_task && succ, trunc = stepped && a.limit > 0 && el >= (long long)a.limit, done = term | trunc;
+      a.terminated[w] = (unsigned char)term; a.truncated[w] = (unsigned char)trunc;
+      if (a.step_success) a.step_success[w] = (unsigned char)succ;
+      if (a.desired) { a.desired[2 * (size_t)w] = a.goal[2 * (size_t)w]; a.desired[2 * (size_t)w + 1] = a.goal[2 * (size_t)w + 1]; }
+      if (a.reset_target && a.continuing_task && a.n_goal > 1 && stepped && succ) {
+        // update_goal: goal cell + xy noise until the goal is farther than the radius from the agent (fp64, the draw order of maze_spec.redraw_goal); the first test is on the
+        // goal that was just reached.  Drawn even when the world also ends in this step: its reset draws come behind these.
+        const double ax = (double)a.achieved[2 * (size_t)w], ay = (double)a.achieved[2 * (size_t)w + 1];
+        double gx = (double)a.goal[2 * (size_t)w], gy = (double)a.goal[2 * (size_t)w + 1];
+        unsigned long long* st = (unsigned long long*)a.rng + 5 * (size_t)w;
+        unsigned long long hi = st[0], lo = st[1], buf = st[4];
+        const unsigned long long ihi = st[2], ilo = st[3];
+        int guard = 0;
+        for (; guard < 65536; guard++) {
+          const double dx = __dsub_rn(ax, gx), dy = __dsub_rn(ay, gy);
+          if (!(__dsqrt_rn(__dadd_rn(grx_rounded(__dmul_rn(dx, dx)), grx_rounded(__dmul_rn(dy, dy)))) <= a.goal_radius)) break;
+          const int c = grx_pcg64_integers_dev(hi, lo, ihi, ilo, buf, (unsigned)a.n_goal);
+          gx = __dadd_rn(a.goal_xy[2 * c], grx_rounded(__dmul_rn(grx_pcg64_uniform_dev(hi, lo, ihi, ilo, -a.noise_range, a.noise_range), a.scaling)));
+          gy = __dadd_rn(a.goal_xy[2 * c + 1], grx_rounded(__dmul_rn(grx_pcg64_uniform_dev(hi, lo, ihi, ilo, -a.noise_range, a.noise_range), a.scaling)));
+        }
+        st[0] = hi; st[1] = lo; st[4] = buf;
+        if (guard == 65536) a.status[w] |= GRX_ST_BADNUM | (GRX_ST_BADNUM << 16);      // never silently: the goal stays, the world is flagged
+        else { a.goal[2 * (size_t)w] = (float)gx; a.goal[2 * (size_t)w + 1] = (float)gy; }
+      }
+      int next_pending = 0;
+      if (a.mode == 0) { listed = pending; next_pending = stepped && done; if (pending) el = 0; }      // next-step: the pending worlds are reset now, the finished ones wait
+      else if (a.mode == 1) { listed = done; if (done) el = 0; }                                       // same-step: the finished worlds are reset now
+      a.elapsed[w] = el;
+      a.needs_reset[w] = (unsigned char)next_pending;
+      if (a.mask) a.mask[w] = (unsigned char)!next_pending;
+    }
+    const unsigned long long ballot = __ballot(listed);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+    if ((tid & 63) == 0) wave_total[wave] = __popcll(ballot);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) { const int c = wave_total[k]; before += k < wave ? c : 0; total += c; }
+    if (listed) {
+      const int j = base + before + rank;
+      a.reset_idx[j] = w;
+      if (a.mode == 1 && a.final_idx) a.final_idx[j] = w;
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    *a.reset_count = base;
+    if (a.n_final) *a.n_final = a.mode == 1 ? base : 0;
+  }
+}
+
+// rows[j] <- packed[idx[j]] for j < *count (the terminal rows of a same-step autoreset, before the reset overwrites them)
+__global__ void __launch_bounds__(64)
+grx_maze_park_rows_kernel(float* __restrict__ rows, const float* __restrict__ packed, int width, const int* __restrict__ idx, const int* __restrict__ count) {
+  const int k = *count;
+  for (int j = blockIdx.x; j < k; j += gridDim.x) {
+    const float* s = packed + (size_t)idx[j] * width;
+    float* d = rows + (size_t)j * width;
+    for (int c = threadIdx.x; c < width; c += 64) d[c] = s[c];
+  }
+}
+
+extern "C" int grx_maze_episode_end(const grx_maze_episode_args* args, int n_worlds, void* stream) {
+  if (!args) return fail("grx_maze_episode_end: null argument");
+  const grx_maze_episode_args& a = *args;
+  if (!a.elapsed || !a.needs_reset || !a.success || !a.achieved || !a.goal || !a.status || !a.terminated || !a.truncated || !a.reset_count || !a.reset_idx)
+    return fail("grx_maze_episode_end: null buffer");
+  if (a.mode < 0 || a.mode > 2) return fail("grx_maze_episode_end: mode is 0 (next-step), 1 (same-step) or 2 (disabled)");
+  if (a.reset_target && (!a.rng || !a.goal_xy || a.n_goal < 1)) return fail("grx_maze_episode_end: reset_target needs the PCG64 rows and the goal cells");
+  if (a.final_rows && (!a.packed || a.packed_dim <= 0)) return fail("grx_maze_episode_end: final_rows needs the packed rows");
+  if (n_worlds <= 0) return 0;
+  hipLaunchKernelGGL(grx_maze_episode_end_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a, n_worlds);
+  HIP_OK(hipGetLastError());
+  if (a.mode == 1 && a.final_rows) {
+    hipLaunchKernelGGL(grx_maze_park_rows_kernel, dim3((unsigned)(n_worlds < 1024 ? n_worlds : 1024)), dim3(64), 0, (hipStream_t)stream, a.final_rows, a.packed, a.packed_dim,
+                       (const int*)a.reset_idx, (const int*)a.reset_count);
+    HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+// the reset draws and the reset rows for a list whose LENGTH lives in device memory (written by grx_maze_episode_end on the same stream): the grids are sized by the upper
+// bound max_n, entries at or beyond *count are left alone
+extern "C" int grx_maze_sample_resets_list(uint64_t* states, const int* idx, const int* count, int max_n, const double* goal_xy, int n_goal, const double* reset_xy, int n_reset,
+                                           double noise_range, double scaling, float* stage, void* stream) {
+  if (!states || !idx || !count || !goal_xy || !reset_xy || !stage) return fail("grx_maze_sample_resets_list: null argument");
+  if (n_goal < 1 || n_reset < 1) return fail("grx_maze_sample_resets_list: empty cell list");
+  if (max_n <= 0) return 0;
+  hipLaunchKernelGGL(grx_maze_sample_kernel, dim3((unsigned)((max_n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)states, idx, max_n, count, goal_xy, n_goal, reset_xy,
+                     n_reset, noise_range, scaling, 0, 0.0, 0.0, 0, 0.0, 0.0, stage);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+extern "C" int grx_maze_reset_rows_list(const grx_maze_reset_args* args, const int* count, int max_n, float* desired, void* stream) {
+  if (!args || !count) return fail("grx_maze_reset_rows_list: null argument");
+  const grx_maze_reset_args& a = *args;
+  if (!a.idx || !a.stage || !a.qpos0 || !a.qpos || !a.qvel || !a.qacc_ws || !a.goal || !a.obs || !a.achieved || !a.reward || !a.success) return fail("grx_maze_reset_rows_list: null buffer");
+  if (a.nq < 2 || a.nv <= 0 || a.obs_skip < 0 || a.obs_skip > 2 || a.obs_dim != a.nq + a.nv - a.obs_skip) return fail("grx_maze_reset_rows_list: obs_dim must be nq + nv - obs_skip");
+  if (max_n <= 0) return 0;
+  hipLaunchKernelGGL(grx_maze_reset_list_kernel, dim3((unsigned)(max_n < 1024 ? max_n : 1024)), dim3(64), 0, (hipStream_t)stream, a, count, max_n, desired);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -1,6 +1,7 @@
-"""Python side of the env-level C ABI of the Fetch family (include/grx_env.h, libgrx_env.so).
+"""Python side of the env-level C ABI (include/grx_env.h, libgrx_env.so): the Fetch family and the maze family (PointMaze-v3, AntMaze).
 
     python -m gymnasium_robotics_amd.env_capi describe FetchPickAndPlace-v4 pick.grxenv
+    python -m gymnasium_robotics_amd.env_capi describe AntMaze_Large_Diverse_GR-v5 ant.grxenv continuing_task=False
 
 writes the environment description file grx_env_create reads.  The file is built from the packaged model (models/*.npz) alone:
 no GPU, no asset tree.  This module also holds the ctypes loader of libgrx_env.so, struct mirrors of grx_env.h and a parser of the
@@ -24,6 +25,16 @@ Sections of a description (version 1):
     fast_caps             int32 [3]: maxefc, jpool, maxcon of the FETCH_CAPACITY tables (the overflow re-run's soft thresholds)
     q0                    float64 [nq]: qpos0 with the task's initial_qpos applied
     mocap0                float64 [7 nmocap]: mocap_pos0 | mocap_quat0
+
+Sections of a maze description (same version; told apart by the `family` section, which a Fetch description does not have):
+
+    family                "maze" (NUL-padded to 8 bytes)
+    H I F                 model.pack() of the model PointMazeVecEnv / AntMazeVecEnv steps (the ant at ANT_CAPACITY)
+    task                  the PointTaskStruct bytes (struct grx_point_task)
+    dims                  int32 [8]: nq, nv, nu, obs_dim, obs_skip (2 for the ant), number of goal cells, number of reset cells, max_episode_steps
+    consts                float64 [8]: goal radius, position_noise_range, maze_size_scaling, dt (frame skip x timestep), continuing_task, reset_target, sparse reward, 0
+    qpos0                 float64 [nq]
+    goal_xy reset_xy      float64 [cells, 2]: Maze.unique_goal_locations / unique_reset_locations (cell centres)
 """
 import ctypes
 import os
@@ -91,7 +102,8 @@ def state_arrays(blob, obs_dim=None):
     """the sections of a grx_env_get_state blob as numpy arrays (float32 rows, int32 / uint8 / int64 / uint64 where the state holds those)"""
     head, sec = parse_sections(blob)
     n = head["num_envs"]
-    dtypes = {"success": np.uint8, "status": np.int32, "cost": np.int32, "order": np.int32, "rng": np.uint64, "elapsed": np.int64, "needs_reset": np.uint8, "has_reset": np.uint8}
+    dtypes = {"success": np.uint8, "status": np.int32, "cost": np.int32, "order": np.int32, "rng": np.uint64, "elapsed": np.int64, "needs_reset": np.uint8, "has_reset": np.uint8, "mask": np.uint8,
+              "split_state": np.int32}
     out = {}
     for k, v in sec.items():
         a = np.frombuffer(v, dtype=dtypes.get(k, np.float32))
@@ -100,8 +112,47 @@ def state_arrays(blob, obs_dim=None):
 
 
 # ------------------------------------------------------------------ description file
-def describe(env_id):
-    """the description file of `env_id` as bytes (packaged model; no GPU)"""
+MAZE_KWARGS = {"continuing_task": True, "reset_target": False, "position_noise_range": 0.25}
+
+
+def is_maze_id(env_id):
+    return env_id.startswith("PointMaze_") or env_id.startswith("AntMaze_")
+
+
+def describe_maze(env_id, **kwargs):
+    """the description of a registered PointMaze / AntMaze id in the given mode (MAZE_KWARGS: the keyword arguments of PointMazeVecEnv with their defaults)"""
+    from . import _native
+    from .envs import maze_spec as ms
+    from .envs.point_maze import AntMazeVecEnv, PointMazeVecEnv, load_point_maze_model
+
+    unknown = set(kwargs) - set(MAZE_KWARGS)
+    if unknown:
+        raise TypeError(f"describe({env_id!r}): unknown keyword arguments {sorted(unknown)} (a maze description takes {sorted(MAZE_KWARGS)})")
+    kw = dict(MAZE_KWARGS, **kwargs)
+    cls = AntMazeVecEnv if env_id.startswith("AntMaze_") else PointMazeVecEnv
+    layout, reward_type, max_episode_steps = cls._parse_id(env_id)
+    maze = ms.Maze(ms.MAPS[layout], *cls.MAZE_GEOMETRY)
+    model = load_point_maze_model(maze, layout, None, cls.AGENT)
+    task = _native.PointTaskStruct(cls.N_SUBSTEPS, int(reward_type == "sparse"), int(bool(kw["continuing_task"])), int(cls.AGENT == "ant"), ms.GOAL_RADIUS, 5.0)
+    nq, nv, nu = model.dim("nq"), model.dim("nv"), model.dim("nu")
+    goal_xy = np.ascontiguousarray(np.asarray(maze.unique_goal_locations, dtype=np.float64).reshape(-1, 2))
+    reset_xy = np.ascontiguousarray(np.asarray(maze.unique_reset_locations, dtype=np.float64).reshape(-1, 2))
+    dims = np.array([nq, nv, nu, nq + nv - cls.OBS_SKIP, cls.OBS_SKIP, len(goal_xy), len(reset_xy), max_episode_steps or 0], np.int32)
+    consts = np.array([ms.GOAL_RADIUS, float(kw["position_noise_range"]), maze.maze_size_scaling, cls.N_SUBSTEPS * model.opt("timestep"), float(bool(kw["continuing_task"])),
+                       float(bool(kw["reset_target"])), float(reward_type == "sparse"), 0.0], np.float64)
+    H, I, F = model.pack()
+    f = lambda a, dt: np.ascontiguousarray(a, dtype=dt).tobytes()
+    sections = [("family", b"maze\0\0\0\0"), ("H", f(H, np.int32)), ("I", f(I, np.int32)), ("F", f(F, np.float64)), ("task", bytes(task)), ("dims", dims.tobytes()),
+                ("consts", consts.tobytes()), ("qpos0", f(model.tables["qpos0"], np.float64)), ("goal_xy", goal_xy.tobytes()), ("reset_xy", reset_xy.tobytes())]
+    return pack_sections(DESC_MAGIC, DESC_VERSION, env_id, 0, sections)
+
+
+def describe(env_id, **kwargs):
+    """the description file of `env_id` as bytes (packaged model; no GPU).  Maze ids take the mode of the environment as keyword arguments (MAZE_KWARGS)."""
+    if is_maze_id(env_id):
+        return describe_maze(env_id, **kwargs)
+    if kwargs:
+        raise TypeError(f"describe({env_id!r}): a Fetch description takes no keyword arguments")
     from .core import RERUN_CAPACITY
     from .envs.fetch import FETCH_CAPACITY, load_fetch_model
     from .envs.fetch_spec import DISTANCE_THRESHOLD, FETCH_TASKS, MAX_EPISODE_STEPS, make_fetch_task, parse_env_id
@@ -135,8 +186,8 @@ def describe(env_id):
     return pack_sections(DESC_MAGIC, DESC_VERSION, env_id, 0, sections)
 
 
-def write_env_desc(env_id, path):
-    blob = describe(env_id)
+def write_env_desc(env_id, path, **kwargs):
+    blob = describe(env_id, **kwargs)
     with open(path, "wb") as fh:
         fh.write(blob)
     return path
@@ -146,6 +197,12 @@ def read_env_desc(path):
     """-> (header, dict of numpy arrays / bytes) of a description file"""
     with open(path, "rb") as fh:
         head, sec = parse_sections(fh.read())
+    if sec.get("family", b"").rstrip(b"\0") == b"maze":
+        out = {k: np.frombuffer(sec[k], np.int32) for k in ("H", "I", "dims")}
+        out.update({k: np.frombuffer(sec[k], np.float64) for k in ("F", "consts", "qpos0")})
+        out.update({k: np.frombuffer(sec[k], np.float64).reshape(-1, 2) for k in ("goal_xy", "reset_xy")})
+        out.update(task=sec["task"], family="maze")
+        return head, out
     out = {k: np.frombuffer(sec[k], np.int32) for k in ("H", "I", "H_rerun", "I_rerun", "dims", "fast_caps")}
     out.update({k: np.frombuffer(sec[k], np.float64) for k in ("F", "F_rerun", "consts", "q0", "mocap0")})
     out["task"] = sec["task"]
@@ -210,10 +267,21 @@ def seed_pcg64(seeds):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if len(argv) != 3 or argv[0] != "describe":
-        print("usage: python -m gymnasium_robotics_amd.env_capi describe <env id> <path>", file=sys.stderr)
+    if len(argv) < 3 or argv[0] != "describe" or any("=" not in a for a in argv[3:]):
+        print("usage: python -m gymnasium_robotics_amd.env_capi describe <env id> <path> [key=value ...]   (maze ids: " + ", ".join(MAZE_KWARGS) + ")", file=sys.stderr)
         return 2
-    write_env_desc(argv[1], argv[2])
+    kwargs = {}
+    words = {"1": True, "true": True, "0": False, "false": False}
+    for a in argv[3:]:
+        k, v = a.split("=", 1)
+        try:
+            if k not in MAZE_KWARGS or not is_maze_id(argv[1]):
+                raise ValueError(f"unknown key {k!r}")
+            kwargs[k] = float(v) if k == "position_noise_range" else words[v.strip().lower()]
+        except (KeyError, ValueError):
+            print(f"describe: cannot use {a!r} (keys: {', '.join(MAZE_KWARGS)}, for maze ids; flags take true / false / 1 / 0, position_noise_range a number)", file=sys.stderr)
+            return 2
+    write_env_desc(argv[1], argv[2], **kwargs)
     return 0
 
 

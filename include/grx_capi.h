@@ -17,6 +17,8 @@
  *                              (nstep > 0: the raw mj_step settle loop of _env_setup, fetch/fetch_env.py:419-420)
  *   grx_fetch_compute_reward  GoalEnv.compute_reward on a batch (HER)   fetch/fetch_env.py:74-80, core.py:45-67
  *   grx_maze_sample_resets_device ... np_random.integers / uniform draws of MazeEnv.reset       maze/maze_v4.py:299-358
+ *   grx_maze_episode_end ............ the episode bookkeeping of a maze step on the device: time limit, termination, MazeEnv.update_goal, the reset list   maze/maze_v4.py:400-418
+ *   grx_maze_sample_resets_list, grx_maze_reset_rows_list ... the reset draws / rows over that list (its length stays in device memory)
  *   grx_adroit_sample_resets_device . np_random.uniform draws of the Adroit reset_model methods  adroit_hammer.py:374-376, adroit_door.py:362-370, adroit_relocate.py:353-372
  *   grx_fetch_sample_resets[_device] . np_random.uniform draws of _reset_sim/_sample_goal  fetch/fetch_env.py:153-166,388-391 (host / on the device)
  *   grx_fetch_commit_rows ........... commit of a Fetch reset that ran BESIDE the step kernel into staged rows      fetch/fetch_env.py:375-402, envs/robot_env.py:154-186
@@ -425,6 +427,45 @@ typedef struct grx_maze_reset_args {
   float *qpos, *qvel, *qacc_ws, *goal, *obs, *achieved, *reward; unsigned char* success; float* packed;
 } grx_maze_reset_args;
 int grx_maze_reset_rows(const grx_maze_reset_args* args, int n_reset, void* stream);
+/* The same rows for a list whose LENGTH is in device memory (count [1], written by grx_maze_episode_end earlier on the stream): max_n bounds the grid, entries at or beyond
+ * *count are left alone; stage rows are indexed by list position as above.  desired (or NULL): [N, 2], the new goal is written there as well (the goal rows a caller of the
+ * env-level ABI reads as `desired`). */
+int grx_maze_reset_rows_list(const grx_maze_reset_args* args, const int* count, int max_n, float* desired, void* stream);
+
+/* Episode bookkeeping of one maze step ON THE DEVICE, enqueued behind grx_point_step on the same stream: what PointMazeVecEnv.step (envs/point_maze.py) decides on the host.
+ * Per world w, with stepped = !needs_reset[w] as it was when the step was launched:
+ *   elapsed[w] += stepped;  terminated[w] = stepped && !continuing_task && success[w];  truncated[w] = stepped && limit > 0 && elapsed[w] >= limit;  done = either;
+ *   step_success[w] (if given) <- success[w], desired[w] (if given) <- goal[w]: the step's own values, before a reset or a redraw replaces them;
+ *   reset_target && continuing_task && n_goal > 1 && stepped && success[w]: MazeEnv.update_goal (maze/maze_v4.py:400-418) -- goal cell (integers) and xy noise (two uniforms times
+ *     the scaling) from the world's PCG64 row until the fp64 distance from achieved[w] exceeds goal_radius; the row advances in place, goal[w] takes the new goal (the packed row
+ *     keeps the one the step was scored against).  Drawn also for a world that is done in this step, ahead of its reset draws.  65 536 rejected draws: GRX_STATUS_BADNUM in
+ *     status[w] (both halves), the goal stays;
+ *   mode 0 (next-step): the list = the worlds pending at launch (elapsed <- 0), needs_reset[w] <- done of the stepped worlds, mask[w] <- !needs_reset[w] (the mask of the NEXT
+ *     masked grx_point_step);  mode 1 (same-step): the list = the done worlds (elapsed <- 0), their indices also in final_idx, *n_final = the count, their packed rows parked
+ *     compactly in final_rows;  mode 2 (disabled): flags only, an empty list.
+ * reset_idx is in ASCENDING world order (one workgroup, wave ballots and an LDS prefix sum: no atomics), *reset_count its length: grx_maze_sample_resets_list and
+ * grx_maze_reset_rows_list walk it.  All pointers are device pointers; nothing is read back. */
+typedef struct grx_maze_episode_args {
+  long long* elapsed;                    /* [N] */
+  unsigned char* needs_reset;            /* [N] */
+  const unsigned char* success;          /* [N] (the step kernel's) */
+  const float* achieved;                 /* [N, 2] */
+  float* goal;                           /* [N, 2] */
+  int* status;                           /* [N] */
+  const float* packed;                   /* [N, packed_dim] or NULL */
+  uint64_t* rng;                         /* [N, 5] PCG64 rows (grx_maze_sample_resets_device) or NULL without reset_target */
+  const double* goal_xy;                 /* [n_goal, 2] cell centres */
+  int n_goal, mode, limit, continuing_task, reset_target, packed_dim;
+  double noise_range, scaling, goal_radius;
+  unsigned char *terminated, *truncated; /* [N] out */
+  unsigned char* mask;                   /* [N] out or NULL */
+  unsigned char* step_success;           /* [N] out or NULL */
+  float* desired;                        /* [N, 2] out or NULL */
+  int *reset_count, *reset_idx;          /* [1], [N] out */
+  int *n_final, *final_idx;              /* [1], [N] out or NULL */
+  float* final_rows;                     /* [N, packed_dim] out or NULL */
+} grx_maze_episode_args;
+int grx_maze_episode_end(const grx_maze_episode_args* args, int n_worlds, void* stream);
 
 /* Commit of an overlapped hand-manipulate reset (envs/hand.py: the settle steps of _reset_sim, manipulate.py:154-224, ran on compacted side rows while the
  * old episode was finishing): row j of the source block replaces world idx[j] of the destination buffers -- qpos, qvel, qacc_ws, obs, achieved, palm,
@@ -492,6 +533,9 @@ int grx_adroit_sample_resets_device(uint64_t* states, const int64_t* idx, int n,
  * reference's order. */
 int grx_maze_sample_resets_device(uint64_t* states, const int* idx, int n, const double* goal_xy, int n_goal, const double* reset_xy, int n_reset, double noise_range, double scaling,
                                   const double* fixed_goal_xy, const double* fixed_reset_xy, float* stage, void* stream);
+/* The same draws for a list whose LENGTH is in device memory (count [1]; see grx_maze_episode_end): max_n bounds the grid, entries at or beyond *count draw nothing. */
+int grx_maze_sample_resets_list(uint64_t* states, const int* idx, const int* count, int max_n, const double* goal_xy, int n_goal, const double* reset_xy, int n_reset,
+                                double noise_range, double scaling, float* stage, void* stream);
 const char* grx_last_error(void);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-/* grx_env.h -- env-level C ABI of the Fetch family (libgrx_env.so, on top of libgrx_hip.so).
+/* grx_env.h -- env-level C ABI of the Fetch and the maze families (libgrx_env.so, on top of libgrx_hip.so).
  *
  * One handle = N Fetch worlds of one id (FetchReach / Push / Slide / PickAndPlace, sparse or Dense) on one GPU, stepped with the
  * same launch group FetchVecEnv(output="torch").step issues (envs/fetch.py): cost-ordered split step launches, the entry-mode
@@ -6,9 +6,15 @@
  * resets through the masked step, and the time limit / autoreset bookkeeping on the host.  A caller that is not Python steps
  * a Fetch world through these calls alone; INTEGRATION.md has the worked example (tests/capi/fetch_rollout.c).
  *
+ * A second handle kind behind the same calls = N maze worlds of one registered PointMaze-v3 / AntMaze id, in one mode of PointMazeVecEnv / AntMazeVecEnv
+ * (envs/point_maze.py: continuing_task, reset_target, position_noise_range are part of the description).  Its episode bookkeeping -- time limit, termination,
+ * the goal redraw of reset_target, the list of worlds to reset -- runs on the device behind the step launch (grx_maze_episode_end, grx_capi.h), so the step call
+ * enqueues and returns in every mode; the flags reach the host through one asynchronous copy per step (see the output structs).  Goals are xy pairs
+ * (goal_dim 2), actions [N, 2] (point mass) or [N, 8] (ant).  Worked example: tests/capi/maze_rollout.c.
+ *
  * The handle is built from an environment description file written by
- *     python -m gymnasium_robotics_amd.env_capi describe <env id> <path>
- * (packed model tables, task struct, task constants, initial state: see gymnasium_robotics_amd/env_capi.py for the layout).
+ *     python -m gymnasium_robotics_amd.env_capi describe <env id> <path> [key=value ...]
+ * (packed model tables, task struct, task constants, initial state, a family tag in a maze description: see gymnasium_robotics_amd/env_capi.py for the layout).
  *
  * Conventions (those of grx_capi.h): every call returns 0 or a negative code and leaves a thread-local message for
  * grx_env_last_error(); nothing in grx_env_step waits for the device; a handle is not re-entrant; the pointers
@@ -48,19 +54,26 @@ typedef struct grx_env_config {
                             * grx_env_reset uses the seeds it is given as they are */
 } grx_env_config;
 
-/* Device outputs of the last step / reset (rows world-major, fp32 unless noted). */
+/* Device outputs of the last step / reset (rows world-major, fp32 unless noted).  goal_dim is 3 (Fetch) or 2 (maze).
+ * Maze handles: the host arrays (terminated, truncated, n_final, final_idx) are written by a copy enqueued by the step; the outputs call waits for the event of that
+ * copy -- not for the device -- before it hands them out.  success is the step's own (info["success"]: in same-step mode a finished world reports the value of the
+ * episode it finished); desired is the goal the step was scored against, for a world reset inside the call its reset goal (with the reset observation); a goal
+ * redrawn by reset_target shows from the next step on.  The host block and its event are single: the next grx_env_step overwrites them, so a caller that
+ * needs the flags of step t reads them (grx_env_outputs) before it enqueues step t + 1.  In the modes where only the time limit ends an episode and no goal is
+ * redrawn (continuing_task on, reset_target off: the default) the handle keeps the counters on the host, as the Fetch handle does, and the flags are there
+ * when grx_env_step returns. */
 typedef struct grx_env_device_outputs {
-  int num_envs, obs_dim, goal_dim, packed_dim;   /* packed_dim = obs_dim + 8 */
+  int num_envs, obs_dim, goal_dim, packed_dim;   /* packed_dim = obs_dim + 2 goal_dim + 2 */
   const float* obs;                /* device [N, obs_dim] */
-  const float* achieved;           /* device [N, 3] */
-  const float* desired;            /* device [N, 3] */
+  const float* achieved;           /* device [N, goal_dim] */
+  const float* desired;            /* device [N, goal_dim] */
   const float* reward;             /* device [N] */
   const uint8_t* success;          /* device [N] */
   const int32_t* status;           /* device [N]: GRX_STATUS_* bits of the last launch (low half) and sticky (high half), grx_capi.h */
   const float* packed;             /* device [N, packed_dim]: [obs | achieved | desired | reward | success] */
-  const uint8_t* terminated;       /* host [N] (always 0: Fetch episodes end by the time limit only) */
+  const uint8_t* terminated;       /* host [N] (Fetch: always 0, episodes end by the time limit only; maze: the goal was reached and continuing_task is off) */
   const uint8_t* truncated;        /* host [N] */
-  int n_final;                     /* same-step autoreset: worlds the last step finished and reset */
+  int n_final;                     /* same-step autoreset: worlds the last step finished (terminated or truncated) and reset */
   const int32_t* final_idx;        /* host [n_final], ascending */
   const float* final_rows;         /* device [n_final, packed_dim]: their terminal packed rows (info["final_obs"]) */
 } grx_env_device_outputs;
@@ -68,21 +81,22 @@ typedef struct grx_env_device_outputs {
 /* Host destinations of grx_env_copy_outputs; any pointer may be NULL (not copied). */
 typedef struct grx_env_host_outputs {
   float* obs;            /* [N, obs_dim] */
-  float* achieved;       /* [N, 3] */
-  float* desired;        /* [N, 3] */
+  float* achieved;       /* [N, goal_dim] */
+  float* desired;        /* [N, goal_dim] */
   float* reward;         /* [N] */
   uint8_t* success;      /* [N] */
   int32_t* status;       /* [N] */
-  float* packed;         /* [N, obs_dim + 8] */
+  float* packed;         /* [N, packed_dim] */
   uint8_t* terminated;   /* [N] */
   uint8_t* truncated;    /* [N] */
   int* n_final;          /* [1] */
   int32_t* final_idx;    /* [N] (n_final written) */
-  float* final_rows;     /* [N, obs_dim + 8] (n_final rows written) */
+  float* final_rows;     /* [N, packed_dim] (n_final rows written) */
 } grx_env_host_outputs;
 
 /* Parses and validates the whole description file before the device is touched, creates the two models (fast and re-run tables),
  * allocates the buffers, runs the _env_setup forward passes and seeds every world from OS entropy (numpy's SeedSequence(None)).
+ * A maze description (its family section says so) makes a maze handle: one model, the rows of PointMazeVecEnv, per-world PCG64 rows, goal / reset cell tables.
  * device: HIP device index.  cfg: NULL = defaults (see grx_env_config). */
 int grx_env_create(const char* desc_path, int num_envs, int device, const grx_env_config* cfg, grx_env** out);
 int grx_env_destroy(grx_env* e);
@@ -91,15 +105,18 @@ int grx_env_dims(const grx_env* e, int* obs_dim, int* goal_dim, int* act_dim, do
  * worlds' streams): world i's stream becomes PCG64(SeedSequence(seeds[i])), so seeds[i] = s + seed_offset + i gives world i the state
  * FetchVecEnv.reset(seed=s) gives it.  Enqueued on `stream`. */
 int grx_env_reset(grx_env* e, const uint8_t* mask, const uint64_t* seeds, void* stream);
-/* One env.step() of every world: actions [N, 4] fp32, device or pinned host memory.  Never waits for the device. */
+/* One env.step() of every world: actions [N, act_dim] fp32 (Fetch: 4), device or pinned host memory.  Never waits for the device, in any mode of either family. */
 int grx_env_step(grx_env* e, const float* actions, void* stream);
 int grx_env_outputs(const grx_env* e, grx_env_device_outputs* out);
 /* The outputs into host memory (synchronises the handle's device). */
 int grx_env_copy_outputs(grx_env* e, grx_env_host_outputs* out);
-/* GoalEnv.compute_reward on a batch (HER): achieved / desired device [batch, 3], out device [batch]. */
+/* GoalEnv.compute_reward on a batch (HER): achieved / desired device [batch, goal_dim], out device [batch]. */
 int grx_env_compute_reward(const grx_env* e, const float* achieved, const float* desired, int64_t batch, float* out, void* stream);
 /* Checkpoint / resume: everything that determines the future of the worlds at a step boundary, as one blob (header with id, N and
- * version, then a named-section table).  get / set synchronise the device; set refuses a blob of another id, N, size or version. */
+ * version, then a named-section table).  get / set synchronise the device; set refuses a blob of another id (so of another family), N, size or version.
+ * A maze blob does not record the mode (continuing_task, reset_target, autoreset): restoring it into a handle of the same id in another mode is the caller's
+ * error and is not detected.  After set_state the outputs are those of a reset: no flags, no finished worlds, success = the worlds' current success flags
+ * (in same-step mode the step before get_state may have reported a finished episode's own value there). */
 int grx_env_state_size(const grx_env* e, size_t* bytes);
 int grx_env_get_state(grx_env* e, void* host, size_t bytes);
 int grx_env_set_state(grx_env* e, const void* host, size_t bytes);
