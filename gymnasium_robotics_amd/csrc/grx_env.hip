@@ -13,6 +13,9 @@
 //   next-step autoreset:       the pending worlds are reset behind the masked step; reward / packed reward zeroed (grx_env_zero_outcome_kernel)
 // Host bookkeeping (time limit, flags) as in FetchVecEnv.step.  Index lists reach the device through a ring of pinned buffers; the host never waits for the device in
 // grx_env_step.
+//
+// An on-device HER replay can be attached to a handle of either kind (include/grx_replay.h, grx_env_replay.inc): every step leaves behind, in host fields only, where the
+// list of the worlds it reset lives on the device (step_list / step_count / step_count_dev).  A handle without a replay issues the same launches either way.
 #include <hip/hip_runtime.h>
 
 #include <sys/random.h>
@@ -25,6 +28,7 @@
 
 #include "grx_capi.h"
 #include "grx_env.h"
+#include "grx_replay.h"
 
 namespace {
 
@@ -275,6 +279,13 @@ struct grx_env {
   std::vector<int32_t> final_idx, list, will;
   int n_final = 0;
   uint8_t has_reset = 0;
+  // for an attached replay (grx_env_replay.inc): the worlds whose packed row of the last step is the first row of a new episode, as a device index list -- its length on
+  // the host, or in device memory where step_count_dev is set -- and the counts of step / reset + set_state calls that order the replay's calls against the handle's
+  grx_replay* replay = nullptr;
+  const int* step_list = nullptr;
+  const int* step_count_dev = nullptr;
+  int step_count = 0;
+  uint64_t steps = 0, epoch = 0;
 
   ~grx_env() {
     (void)hipSetDevice(device);
@@ -622,6 +633,7 @@ extern "C" int grx_env_create(const char* desc_path, int num_envs, int device, c
 
 extern "C" int grx_env_destroy(grx_env* e) {
   if (!e) return fail(GRX_ENV_EINVAL, "grx_env_destroy: NULL handle");
+  if (e->replay) return fail(GRX_ENV_EINVAL, "grx_env_destroy: a replay is attached to the handle: grx_replay_destroy first");
   delete e;
   return 0;
 }
@@ -639,6 +651,8 @@ extern "C" int grx_env_reset(grx_env* e, const uint8_t* mask, const uint64_t* se
   if (!e) return fail(GRX_ENV_EINVAL, "grx_env_reset: NULL handle");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
+  e->epoch += 1;
+  e->step_list = nullptr; e->step_count_dev = nullptr; e->step_count = 0;
   if (e->mz) return maze_reset(e, mask, seeds, s);
   auto& L = e->list;
   L.clear();
@@ -670,6 +684,8 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
   if (!e->has_reset) return fail(GRX_ENV_EINVAL, "grx_env_step: cannot step before grx_env_reset");
   DeviceGuard g(e->device);
   hipStream_t s = (hipStream_t)stream;
+  e->steps += 1;
+  e->step_list = nullptr; e->step_count_dev = nullptr; e->step_count = 0;
   if (e->mz) return maze_step(e, actions, s);
   const int n = e->n;
   ENV_HIP(hipMemcpyAsync(e->action, actions, (size_t)n * 16, hipMemcpyDefault, s));
@@ -717,6 +733,7 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
     ENV_TRY(sample_resets(e, e->idx_main, kp, e->samp_main, s));
     ENV_TRY(reset_inline(e, e->idx_main, kp, e->samp_main, false, s));
     mark_reset(e, pending);
+    e->step_list = e->idx_main; e->step_count = kp;
     hipLaunchKernelGGL(grx_env_zero_outcome_kernel, dim3(blocks(kp)), dim3(64), 0, s, e->reward, e->packed, e->pdim, (const int*)e->idx_main, kp);
     ENV_HIP(hipGetLastError());
   }
@@ -746,6 +763,7 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
     hipLaunchKernelGGL(grx_env_gather_kernel, dim3(blocks(kd)), dim3(64), 0, s, e->final_rows, (const float*)e->final_packed, e->pdim, idx_dev, kd);
     ENV_HIP(hipGetLastError());
     e->n_final = kd;
+    e->step_list = idx_dev; e->step_count = kd;
   } else {
     if (e->mode == GRX_ENV_NEXT_STEP)
       for (int w : e->final_idx) e->needs_reset[w] = 1;
@@ -855,6 +873,8 @@ extern "C" int grx_env_set_state(grx_env* e, const void* host, size_t bytes) {
   }
   ENV_HIP(hipDeviceSynchronize());
   e->has_reset = e->has_reset ? 1 : 0;
+  e->epoch += 1;
+  e->step_list = nullptr; e->step_count_dev = nullptr; e->step_count = 0;
   if (e->mz) { e->mz->flags_live = false; e->mz->success_parked = false; }
   e->n_final = 0;
   e->final_idx.clear();
@@ -862,3 +882,5 @@ extern "C" int grx_env_set_state(grx_env* e, const void* host, size_t bytes) {
   std::fill(e->truncated.begin(), e->truncated.end(), 0);
   return 0;
 }
+
+#include "grx_env_replay.inc"

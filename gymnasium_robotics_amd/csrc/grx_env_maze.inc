@@ -242,6 +242,7 @@ int maze_step_host_book(grx_env* e, hipStream_t s) {
     m.rargs.keep_outcome = 0;
     ENV_GRX(grx_maze_reset_rows(&m.rargs, kp, s));
     for (int w : pending) { m.h_elapsed[w] = 0; m.h_needs_reset[w] = 0; }
+    e->step_list = m.idx; e->step_count = kp;
   }
   const int kd = (int)done.size();
   if (e->mode == GRX_ENV_NEXT_STEP) {
@@ -258,6 +259,7 @@ int maze_step_host_book(grx_env* e, hipStream_t s) {
     for (int j = 0; j < kd; ++j) { fidx[j] = done[j]; m.h_elapsed[done[j]] = 0; }
     n_final = kd;
     m.success_parked = true;
+    e->step_list = m.idx; e->step_count = kd;
   }
   std::memcpy(f + m.off_nfinal, &n_final, 4);
   m.flags_live = true;
@@ -271,6 +273,7 @@ int maze_step(grx_env* e, const float* actions, hipStream_t s) {
   if (m.host_book) return maze_step_host_book(e, s);
   ENV_GRX(grx_point_step(e->h, &m.d.task, e->mode == GRX_ENV_NEXT_STEP ? &m.bufs_masked : &m.bufs, n, s));
   ENV_GRX(grx_maze_episode_end(&m.eargs, n, s));
+  e->step_list = m.rlist; e->step_count_dev = m.rcount;      // (the list and its length stay on the device: an attached replay reads them there)
   if (e->mode != GRX_ENV_DISABLED) {
     ENV_GRX(grx_maze_sample_resets_list(m.rng, m.rlist, m.rcount, n, m.goal_xy, m.n_goal, m.reset_xy, m.n_reset, m.d.consts[1], m.d.consts[2], m.stage, s));
     ENV_GRX(grx_maze_reset_rows_list(&m.rargs_list, m.rcount, n, m.redraw ? m.desired : nullptr, s));

@@ -1251,27 +1251,43 @@ GRX_DEV void grx_her_outcome(const GrxHerArgs& a, const float* ag, const float* 
     *reward = grx_fetch_reward(d, a.p0, a.sparse); *success = (d < a.p0) ? 1.0f : 0.0f;
   }
 }
+// word e of output row b (the whole arithmetic of the relabel: both kernels below write exactly this value)
+GRX_DEV float grx_her_word(const GrxHerArgs& a, long long b, int e) {
+  const int od = a.obs_dim, gd = a.goal_dim, ad = a.act_dim, OW = 2 * od + 3 * gd + ad + 2;
+  const int R = a.T + 1, t = a.t_idx[b] % R, t1 = (a.t_idx[b] + 1) % R, w = a.w_idx[b], tg = a.t_goal[b];
+  const int tt = a.term_t ? a.term_t[w] : -1;   // the row index whose ring entry is the first row of a new episode; the terminal row is in term_rows[w]
+  const float* r0 = a.rows + ((size_t)t * a.N + w) * a.W;
+  const float* r1 = (a.t_idx[b] + 1 == tt) ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)t1 * a.N + w) * a.W;
+  const float* g = tg < 0 ? r0 + od + gd : ((tg == tt ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)(tg % R) * a.N + w) * a.W) + od);   // the substituted goal: achieved at row tg
+  float v;
+  if (e < od + gd) v = r0[e];
+  else if (e < od + 2 * gd) v = g[e - od - gd];
+  else if (e < od + 2 * gd + ad) v = a.acts[((size_t)t1 * a.N + w) * ad + (e - od - 2 * gd)];
+  else if (e == od + 2 * gd + ad || e == OW - 1) {
+    float ag[16], gg[16], rw, sc;
+    for (int k = 0; k < gd; k++) { ag[k] = r1[od + k]; gg[k] = g[k]; }
+    grx_her_outcome(a, ag, gg, &rw, &sc);
+    v = (e == OW - 1) ? sc : rw;
+  } else v = r1[e - (od + 2 * gd + ad + 1)];
+  return v;
+}
 extern "C" __global__ void __launch_bounds__(256)
 grx_her_relabel_kernel(GrxHerArgs a, long long B) {
-  const int od = a.obs_dim, gd = a.goal_dim, ad = a.act_dim, OW = 2 * od + 3 * gd + ad + 2;
+  const int OW = 2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < B * OW; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / OW; const int e = (int)(i - b * OW);
-    const int R = a.T + 1, t = a.t_idx[b] % R, t1 = (a.t_idx[b] + 1) % R, w = a.w_idx[b], tg = a.t_goal[b];
-    const int tt = a.term_t ? a.term_t[w] : -1;   // the row index whose ring entry is the first row of a new episode; the terminal row is in term_rows[w]
-    const float* r0 = a.rows + ((size_t)t * a.N + w) * a.W;
-    const float* r1 = (a.t_idx[b] + 1 == tt) ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)t1 * a.N + w) * a.W;
-    const float* g = tg < 0 ? r0 + od + gd : ((tg == tt ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)(tg % R) * a.N + w) * a.W) + od);   // the substituted goal: achieved at row tg
-    float v;
-    if (e < od + gd) v = r0[e];
-    else if (e < od + 2 * gd) v = g[e - od - gd];
-    else if (e < od + 2 * gd + ad) v = a.acts[((size_t)t1 * a.N + w) * ad + (e - od - 2 * gd)];
-    else if (e == od + 2 * gd + ad || e == OW - 1) {
-      float ag[16], gg[16], rw, sc;
-      for (int k = 0; k < gd; k++) { ag[k] = r1[od + k]; gg[k] = g[k]; }
-      grx_her_outcome(a, ag, gg, &rw, &sc);
-      v = (e == OW - 1) ? sc : rw;
-    } else v = r1[e - (od + 2 * gd + ad + 1)];
-    a.out[i] = v;
+    const long long b = i / OW;
+    a.out[i] = grx_her_word(a, b, (int)(i - b * OW));
+  }
+}
+// the same rows behind a device-side decision (grx_her_sample_relabel): *valid == 0 -- the sample kernel found no world with a transition, its indices mean nothing --
+// zero-fills the slot and reads no index
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_relabel_valid_kernel(GrxHerArgs a, long long B, const int* __restrict__ valid) {
+  const int OW = 2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2;
+  const bool ok = *valid != 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < B * OW; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / OW;
+    a.out[i] = ok ? grx_her_word(a, b, (int)(i - b * OW)) : 0.0f;
   }
 }
 
@@ -1743,31 +1759,51 @@ static __device__ __forceinline__ unsigned long long grx_splitmix(unsigned long 
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-extern "C" __global__ void __launch_bounds__(256)
-grx_her_sample_kernel(const int* __restrict__ start, const int* __restrict__ prev_start, const int* __restrict__ term_t, int N, int t_now, int T, int k_future,
-                      unsigned long long seed, unsigned long long call, long long B, int* __restrict__ t_idx, int* __restrict__ w_idx, int* __restrict__ t_goal) {
+// the draws of sample b; false when the probe loop has visited all N worlds without finding one that has a transition (then no world has one: every sample agrees)
+static __device__ __forceinline__ bool grx_her_draw(const int* __restrict__ start, const int* __restrict__ prev_start, const int* __restrict__ term_t, int N, int t_now, int T,
+                                                    int k_future, unsigned long long seed, unsigned long long call, long long b, int* t_out, int* w_out, int* tg_out) {
   const int lo_min = t_now - T > 0 ? t_now - T : 0;
   // first row of the episode world w is sampled from: its current one, or -- when that one began in this very step -- the one that has just ended
 #define GRX_HER_LO(W_) ((term_t && term_t[W_] == t_now) ? (prev_start[W_] > lo_min ? prev_start[W_] : lo_min) : (start[W_] > lo_min ? start[W_] : lo_min))
-  for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (long long)gridDim.x * blockDim.x) {
-    unsigned long long s = seed * 0xD1342543DE82EF95ull + call * 0x2545F4914F6CDD1Dull + (unsigned long long)b;
-    (void)grx_splitmix(s);
-    int w = 0, lo = t_now;
-    for (int attempt = 0; attempt < 64 && lo >= t_now; attempt++) {          // uniform over the worlds that have a transition (the caller made sure one exists)
-      w = (int)(((grx_splitmix(s) >> 32) * (unsigned long long)N) >> 32);
-      lo = GRX_HER_LO(w);
-    }
-    for (int probe = 0; probe < N && lo >= t_now; probe++) { w = w + 1 < N ? w + 1 : 0; lo = GRX_HER_LO(w); }
-    const unsigned long long r = grx_splitmix(s), r2 = grx_splitmix(s);
-    const float u0 = (float)(r >> 40) * (1.0f / 16777216.0f), u1 = (float)((r >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f), u2 = (float)(r2 >> 40) * (1.0f / 16777216.0f);
-    int t = lo + (int)(u0 * (float)(t_now - lo));
-    if (t > t_now - 1) t = t_now - 1;
-    int fut = t + 1 + (int)(u1 * (float)(t_now - t));
-    if (fut > t_now) fut = t_now;
-    t_idx[b] = t; w_idx[b] = w;
-    t_goal[b] = (u2 >= (float)k_future / ((float)k_future + 1.0f)) ? -1 : fut;
+  unsigned long long s = seed * 0xD1342543DE82EF95ull + call * 0x2545F4914F6CDD1Dull + (unsigned long long)b;
+  (void)grx_splitmix(s);
+  int w = 0, lo = t_now;
+  for (int attempt = 0; attempt < 64 && lo >= t_now; attempt++) {          // uniform over the worlds that have a transition
+    w = (int)(((grx_splitmix(s) >> 32) * (unsigned long long)N) >> 32);
+    lo = GRX_HER_LO(w);
   }
+  for (int probe = 0; probe < N && lo >= t_now; probe++) { w = w + 1 < N ? w + 1 : 0; lo = GRX_HER_LO(w); }
 #undef GRX_HER_LO
+  const unsigned long long r = grx_splitmix(s), r2 = grx_splitmix(s);
+  const float u0 = (float)(r >> 40) * (1.0f / 16777216.0f), u1 = (float)((r >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f), u2 = (float)(r2 >> 40) * (1.0f / 16777216.0f);
+  int t = lo + (int)(u0 * (float)(t_now - lo));
+  if (t > t_now - 1) t = t_now - 1;
+  int fut = t + 1 + (int)(u1 * (float)(t_now - t));
+  if (fut > t_now) fut = t_now;
+  *t_out = t; *w_out = w;
+  *tg_out = (u2 >= (float)k_future / ((float)k_future + 1.0f)) ? -1 : fut;
+  return lo < t_now;
+}
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_sample_kernel(const int* __restrict__ start, const int* __restrict__ prev_start, const int* __restrict__ term_t, int N, int t_now, int T, int k_future,
+                      unsigned long long seed, unsigned long long call, long long B, int* __restrict__ t_idx, int* __restrict__ w_idx, int* __restrict__ t_goal) {
+  for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (long long)gridDim.x * blockDim.x) {      // (the caller made sure a world with a transition exists)
+    int t, w, tg;
+    (void)grx_her_draw(start, prev_start, term_t, N, t_now, T, k_future, seed, call, b, &t, &w, &tg);
+    t_idx[b] = t; w_idx[b] = w; t_goal[b] = tg;
+  }
+}
+// the same draws for a caller that keeps no host mirror of the episode boundaries: sample 0 also reports whether anything could be sampled (valid[0] = B or 0)
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_sample_valid_kernel(const int* __restrict__ start, const int* __restrict__ prev_start, const int* __restrict__ term_t, int N, int t_now, int T, int k_future,
+                            unsigned long long seed, unsigned long long call, long long B, int* __restrict__ t_idx, int* __restrict__ w_idx, int* __restrict__ t_goal,
+                            int* __restrict__ valid) {
+  for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (long long)gridDim.x * blockDim.x) {
+    int t, w, tg;
+    const bool found = grx_her_draw(start, prev_start, term_t, N, t_now, T, k_future, seed, call, b, &t, &w, &tg);
+    t_idx[b] = t; w_idx[b] = w; t_goal[b] = tg;
+    if (b == 0) *valid = found ? (int)B : 0;
+  }
 }
 extern "C" int grx_her_sample_final(const int* episode_start, const int* prev_start, const int* term_t, int n_worlds, int t_now, int T, int k_future, uint64_t seed,
                                     uint64_t call, int64_t batch, int* t_idx, int* w_idx, int* t_goal, void* stream) {
@@ -1785,6 +1821,31 @@ extern "C" int grx_her_sample_final(const int* episode_start, const int* prev_st
 extern "C" int grx_her_sample(const int* episode_start, int n_worlds, int t_now, int T, int k_future, uint64_t seed, uint64_t call, int64_t batch,
                               int* t_idx, int* w_idx, int* t_goal, void* stream) {
   return grx_her_sample_final(episode_start, nullptr, nullptr, n_worlds, t_now, T, k_future, seed, call, batch, t_idx, w_idx, t_goal, stream);
+}
+extern "C" int grx_her_sample_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call,
+                                      int64_t batch, int* scratch, int* valid, void* stream) {
+  if (!args || !episode_start || !scratch || !valid) return fail("grx_her_sample_relabel: null argument");
+  GrxHerArgs a; memcpy(&a, args, sizeof(a));
+  if (!a.rows || !a.acts || !a.out) return fail("grx_her_sample_relabel: null buffer");
+  if ((a.term_rows == nullptr) != (a.term_t == nullptr) || (prev_start == nullptr) != (a.term_t == nullptr))
+    return fail("grx_her_sample_relabel: term_rows, term_t and prev_start go together");
+  if (a.T <= 0 || a.N <= 0 || a.obs_dim <= 0 || a.goal_dim <= 0 || a.goal_dim > 16 || a.act_dim <= 0 || a.W < a.obs_dim + 2 * a.goal_dim)
+    return fail("grx_her_sample_relabel: dimensions out of range (goal_dim <= 16, W >= obs_dim + 2 goal_dim)");
+  if (a.kind < 0 || a.kind > 3 || (a.kind == 0 && a.goal_dim != 3) || (a.kind == 2 && a.goal_dim != 2) || (a.kind == 3 && a.goal_dim != 7))
+    return fail("grx_her_sample_relabel: reward kind does not fit goal_dim");
+  if (t_now < 0 || k_future < 0 || batch <= 0 || batch > (1ll << 30)) return fail("grx_her_sample_relabel: t_now, k_future >= 0 and 1 <= batch <= 2^30");
+  a.t_idx = scratch; a.w_idx = scratch + batch; a.t_goal = scratch + 2 * batch;
+  long long blocks = (batch + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(grx_her_sample_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, episode_start, prev_start, a.term_t, a.N, t_now, a.T, k_future,
+                     (unsigned long long)seed, (unsigned long long)call, (long long)batch, scratch, scratch + batch, scratch + 2 * batch, valid);
+  HIP_OK(hipGetLastError());
+  const long long words = (long long)batch * (2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2);
+  blocks = (words + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(grx_her_relabel_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (long long)batch, (const int*)valid);
+  HIP_OK(hipGetLastError());
+  return 0;
 }
 extern "C" __global__ void __launch_bounds__(256)
 grx_her_mark_kernel(const unsigned char* __restrict__ mask, int N, int t, int* __restrict__ start, int* __restrict__ prev_start, int* __restrict__ term_t) {

@@ -5,7 +5,7 @@
 
 writes the environment description file grx_env_create reads.  The file is built from the packaged model (models/*.npz) alone:
 no GPU, no asset tree.  This module also holds the ctypes loader of libgrx_env.so, struct mirrors of grx_env.h and a parser of the
-section tables both files use.
+section tables both files use, and the struct mirrors of grx_replay.h (the HER replay attached to a handle: ReplayConfig, ReplayBatch).
 
 Container (little endian; the description file and the state blob of grx_env_get_state share it):
 
@@ -51,6 +51,7 @@ ENTRY = struct.Struct("<24sQQ")            # 40 bytes
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libgrx_env.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_env.h")
+REPLAY_HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_replay.h")
 _lib = None
 
 AUTORESET = {"next_step": 0, "same_step": 1, "disabled": 2}
@@ -224,6 +225,15 @@ class EnvHostOutputs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "achieved", "desired", "reward", "success", "status", "packed", "terminated", "truncated", "n_final", "final_idx", "final_rows")]
 
 
+# ------------------------------------------------------------------ grx_replay.h mirrors
+class ReplayConfig(ctypes.Structure):
+    _fields_ = [("horizon", ctypes.c_int), ("keep_final", ctypes.c_int), ("capacity", ctypes.c_int64), ("max_batch", ctypes.c_int64), ("seed", ctypes.c_uint64)]
+
+
+class ReplayBatch(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_void_p), ("batch", ctypes.c_int64), ("offset", ctypes.c_int64), ("valid", ctypes.c_void_p)]
+
+
 def lib():
     """libgrx_env.so with its argument types (loads libgrx_hip.so first, through the package loader: one HIP runtime, the one torch uses)"""
     global _lib
@@ -248,6 +258,15 @@ def lib():
         L.grx_env_set_state.argtypes = [vp, vp, ctypes.c_size_t]
         L.grx_env_seed_pcg64.argtypes = [vp, ci, vp]
         L.grx_env_last_error.restype = ctypes.c_char_p
+        i64, u64 = ctypes.c_int64, ctypes.c_uint64
+        L.grx_replay_create.argtypes = [vp, P(ReplayConfig), P(vp)]
+        L.grx_replay_destroy.argtypes = [vp]
+        L.grx_replay_dims.argtypes = [vp, P(ci), P(ci), P(ci), P(ci)]
+        L.grx_replay_begin.argtypes = [vp, vp]
+        L.grx_replay_append.argtypes = [vp, vp]
+        L.grx_replay_relabel.argtypes = [vp, i64, ci, P(ReplayBatch), vp]
+        L.grx_replay_reseed.argtypes = [vp, u64]
+        L.grx_replay_ring.argtypes = [vp, P(vp), P(i64), P(i64), P(i64)]
         _lib = L
     return _lib
 
@@ -255,6 +274,18 @@ def lib():
 def check(rc):
     if rc != 0:
         raise RuntimeError(f"libgrx_env ({rc}): " + lib().grx_env_last_error().decode())
+
+
+class _DeviceArray:
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def device_view(ptr, shape, dtype=np.float32, device="cuda:0"):
+    """a torch tensor over device memory the library owns (grx_env_outputs / grx_replay_relabel pointers): no copy, valid as long as the pointer is"""
+    import torch
+
+    return torch.as_tensor(_DeviceArray(ptr, shape, np.dtype(dtype).str), device=device)
 
 
 def seed_pcg64(seeds):

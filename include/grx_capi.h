@@ -412,6 +412,12 @@ int grx_her_sample_final(const int* episode_start, const int* prev_start, const 
 /* Episode bookkeeping of the worlds reset in the step that produced row t (reset_mask[w] != 0): prev_start[w] <- episode_start[w], term_t[w] <- t,
  * episode_start[w] <- t.  One kernel.  prev_start / term_t may be NULL (then only episode_start is updated). */
 int grx_her_mark_resets(const unsigned char* reset_mask, int n_worlds, int t, int* episode_start, int* prev_start, int* term_t, void* stream);
+/* grx_her_sample_final + grx_her_relabel for a caller that keeps NO host mirror of the episode boundaries (the replay of the env-level ABI, grx_replay.h): two kernels.
+ * The draws are grx_her_sample_final's (prev_start / args->term_t / args->term_rows all given or all NULL) into scratch [3 batch] (args->t_idx / w_idx / t_goal are ignored),
+ * the rows grx_her_relabel's.  Whether any world has a transition is decided on the device: a sample whose probe loop has visited all n worlds without finding one knows
+ * that none exists; then valid[0] = 0 and out is zero-filled, else valid[0] = batch.  t_now = 0 (nothing appended yet) is allowed and samples nothing. */
+int grx_her_sample_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call, int64_t batch,
+                           int* scratch, int* valid, void* stream);
 
 /* Episode reset of a COMPACTED list of maze worlds (maze/point_maze.py:377-390 / ant_maze_v5.py reset_model, maze_v4.py:299-358: qpos = init_qpos with
  * xy <- the drawn reset position, qvel = 0, new goal, observation of the reset state): one kernel writes state, goal, obs / achieved / success and the

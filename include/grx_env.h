@@ -20,6 +20,9 @@
  * grx_env_last_error(); nothing in grx_env_step waits for the device; a handle is not re-entrant; the pointers
  * grx_env_outputs hands out stay valid until the next grx_env_step / grx_env_reset / grx_env_set_state.
  * "stream" arguments are hipStream_t (NULL = the null stream); the handle owns one more stream of its own (the ahead reset).
+ *
+ * Hindsight experience replay on the device, attached to a handle of either kind: grx_replay.h (same library).  A handle with a replay attached refuses to be
+ * destroyed until the replay is.
  */
 #ifndef GRX_ENV_H
 #define GRX_ENV_H
