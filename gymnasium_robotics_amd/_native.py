@@ -73,6 +73,12 @@ class HerArgsStruct(ctypes.Structure):
         (n, ctypes.c_int) for n in ("sparse", "ignore_pos", "ignore_rot", "ignore_z")] + [("out", ctypes.c_void_p), ("term_rows", ctypes.c_void_p), ("term_t", ctypes.c_void_p)]
 
 
+class HerAppendArgsStruct(ctypes.Structure):      # include/grx_capi.h, grx_her_append_args
+    _fields_ = [(n, ctypes.c_void_p) for n in ("packed", "action", "row_dst", "act_dst")] + [("n_row", ctypes.c_longlong), ("n_act", ctypes.c_longlong)] + [
+        (n, ctypes.c_void_p) for n in ("list", "count_dev", "mask")] + [(n, ctypes.c_int) for n in ("count", "n_worlds", "t", "W")] + [
+        (n, ctypes.c_void_p) for n in ("start", "prev_start", "term_t", "final_rows", "term_rows")]
+
+
 class MazeResetArgsStruct(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("idx", "stage", "qpos0")] + [(n, ctypes.c_int) for n in ("nq", "nv", "obs_dim", "obs_skip")] + [
         ("goal_radius", ctypes.c_double), ("keep_outcome", ctypes.c_int)] + [
@@ -128,6 +134,9 @@ def lib():
         L.grx_her_sample_final.argtypes = [vp, vp, vp, ci, ci, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp, vp, vp, vp]
         L.grx_her_mark_resets.argtypes = [vp, ci, ci, vp, vp, vp, vp]
         L.grx_her_sample_relabel.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp, vp, vp]
+        L.grx_her_draw_relabel.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp, vp]
+        L.grx_her_append.argtypes = [vp, vp]
+        L.grx_fetch_post_step.argtypes = [vp, vp, ctypes.c_float, ci, ci, vp, vp, vp, vp]
         L.grx_kitchen_step.argtypes = [vp, vp, vp, ci, ci, vp]
         L.grx_sample_uniform_rows.argtypes = [vp, vp, ci, ci, vp]
         L.grx_uniform_rows_device.argtypes = [vp, vp, ci, ci, vp, vp]
@@ -184,7 +193,7 @@ def check(rc: int):
 
 EXPORTED_SYMBOLS = [
     "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_dim",
-    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
+    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
 ]
 
 

@@ -21,6 +21,7 @@
 #include <sys/random.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -29,6 +30,7 @@
 #include "grx_capi.h"
 #include "grx_env.h"
 #include "grx_replay.h"
+#include "grx_copy.h"
 
 namespace {
 
@@ -265,6 +267,7 @@ struct grx_env {
   int* a_status;
   grx_fetch_buffers bufs{}, bufs_masked{}, lane_plain{}, lane_masked{}, ahead_bufs{};
   bool balance = false, ahead = false;
+  bool fused_tail = true;      // GRX_FETCH_FUSED_TAIL=0: order, commit and gather as launches of their own (FetchVecEnv._fused)
   int slots_per_xcd = 0, split = 1;
   hipStream_t side = nullptr;
   hipEvent_t ev_before = nullptr, ev_ahead = nullptr;
@@ -346,7 +349,7 @@ grx_fetch_buffers make_bufs(grx_env* e, float* qpos, float* qvel, float* qacc, f
 }
 
 // core.OverflowLane.rerun_only: the step launch with the entry list armed, then the large tables over the worlds that overflowed; then the next order (FetchVecEnv._launch_step)
-int launch_step(grx_env* e, bool masked, hipStream_t s) {
+int launch_step(grx_env* e, bool masked, bool order_now, hipStream_t s) {
   grx_fetch_buffers& fb = masked ? e->bufs_masked : e->bufs;
   ENV_HIP(hipMemsetAsync(e->lane_head, 0, e->lane_head_bytes, s));
   int* counts = e->lane_head + (e->lane_head_bytes / 4 - 2);      // next_count, entry_count
@@ -361,7 +364,7 @@ int launch_step(grx_env* e, bool masked, hipStream_t s) {
   b.lane.next_flags = (unsigned char*)e->lane_head; b.lane.next_count = counts; b.lane.next_list = e->lane_next_list; b.lane.ttl = e->lane_ttl; b.lane.next_cap = 0;
   b.lane.soft_maxefc = e->soft[0]; b.lane.soft_jpool = e->soft[1]; b.lane.soft_maxcon = e->soft[2]; b.lane.ttl_init = e->soft[3];
   ENV_GRX(grx_fetch_step(e->hbig, &e->d.task, &b, e->n, s));
-  if (e->balance) ENV_GRX(grx_order_by_cost_slots(e->cost, e->cost_ema, kBalanceAlpha, e->n, e->slots_per_xcd, e->order, s));
+  if (e->balance && order_now) ENV_GRX(grx_order_by_cost_slots(e->cost, e->cost_ema, kBalanceAlpha, e->n, e->slots_per_xcd, e->order, s));
   return 0;
 }
 
@@ -442,6 +445,7 @@ int alloc_all(grx_env* e) {
   ENV_TRY(e->zalloc(&e->lane_head, e->lane_head_bytes / 4)); ENV_TRY(e->zalloc(&e->lane_next_list, n)); ENV_TRY(e->zalloc(&e->lane_entry_list, n)); ENV_TRY(e->zalloc(&e->lane_ttl, n));
   // cost-ordered dispatch (FetchVecEnv._alloc): a multiple of 8 worlds, one XCD slice per sorting workgroup
   e->balance = n % 8 == 0 && n >= 1024 && n <= 65536 * 8;
+  { const char* v = std::getenv("GRX_FETCH_FUSED_TAIL"); e->fused_tail = !(v && v[0] == '0' && v[1] == 0); }
   if (e->balance) {
     ENV_TRY(e->zalloc(&e->cost, n)); ENV_TRY(e->zalloc(&e->cost_ema, n)); ENV_TRY(e->zalloc(&e->order, n));
     const int lds = grx_model_lds_bytes(e->h);
@@ -707,7 +711,10 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
     hipLaunchKernelGGL(grx_env_mask_kernel, dim3(blocks(kp)), dim3(64), 0, s, e->mask, (const int*)e->idx_main, kp);
     ENV_HIP(hipGetLastError());
   }
-  ENV_TRY(launch_step(e, kp > 0, s));
+  // fused tail (grx_fetch_post_step): in same-step mode the next order is sorted by the launch that commits the reset rows (the step's costs are final once it has ended)
+  const bool post = e->fused_tail && e->mode == GRX_ENV_SAME_STEP && kp == 0;
+  bool ordered = !(post && e->balance);
+  ENV_TRY(launch_step(e, kp > 0, !post, s));
   if (kw) {      // queued behind the step launch: its workgroups take the wave slots the first finished worlds free
     ENV_HIP(hipStreamWaitEvent(e->side, e->ev_before, 0));
     ENV_TRY(e->upload(e->idx_ahead, will.data(), (size_t)kw * 4, e->side));
@@ -738,11 +745,14 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
     ENV_HIP(hipGetLastError());
   }
   const int kd = (int)e->final_idx.size();
+  bool gathered = false;
   if (e->mode == GRX_ENV_SAME_STEP && kd) {
     const int* idx_dev;
     if (kw) {
-      if (kw != kd || !std::equal(will.begin(), will.end(), e->final_idx.begin()))
+      if (kw != kd || !std::equal(will.begin(), will.end(), e->final_idx.begin())) {
+        if (!ordered) (void)grx_fetch_post_step(e->cost, e->cost_ema, kBalanceAlpha, e->n, e->slots_per_xcd, e->order, nullptr, nullptr, s);      // nothing is committed: the order alone
         return fail(GRX_ENV_EINVAL, "grx_env_step: the worlds reset ahead of the step are not the ones it truncated");
+      }
       ENV_HIP(hipStreamWaitEvent(s, e->ev_ahead, 0));
       grx_fetch_commit_args c;
       std::memset(&c, 0, sizeof c);
@@ -751,7 +761,10 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
       c.s_achieved = e->a_achieved; c.s_status = e->a_status;
       c.qpos = e->qpos; c.qvel = e->qvel; c.qacc_ws = e->qacc_ws; c.mocap = e->mocap; c.aux = e->aux; c.goal = e->goal; c.obs = e->obs; c.achieved = e->achieved;
       c.packed = e->packed; c.final_packed = e->final_packed; c.status = e->status;
-      ENV_GRX(grx_fetch_commit_rows(&c, s));
+      if (post) {
+        ENV_GRX(grx_fetch_post_step(e->cost, e->cost_ema, kBalanceAlpha, e->n, e->slots_per_xcd, e->balance ? e->order : nullptr, &c, e->final_rows, s));
+        ordered = gathered = true;
+      } else ENV_GRX(grx_fetch_commit_rows(&c, s));
       idx_dev = e->idx_ahead;
     } else {      // one world (no side stream): the in-line reset parks the terminal rows itself
       ENV_TRY(e->upload(e->idx_main, e->final_idx.data(), (size_t)kd * 4, s));
@@ -760,8 +773,10 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
       idx_dev = e->idx_main;
     }
     mark_reset(e, e->final_idx);
-    hipLaunchKernelGGL(grx_env_gather_kernel, dim3(blocks(kd)), dim3(64), 0, s, e->final_rows, (const float*)e->final_packed, e->pdim, idx_dev, kd);
-    ENV_HIP(hipGetLastError());
+    if (!gathered) {
+      hipLaunchKernelGGL(grx_env_gather_kernel, dim3(blocks(kd)), dim3(64), 0, s, e->final_rows, (const float*)e->final_packed, e->pdim, idx_dev, kd);
+      ENV_HIP(hipGetLastError());
+    }
     e->n_final = kd;
     e->step_list = idx_dev; e->step_count = kd;
   } else {
@@ -769,6 +784,7 @@ extern "C" int grx_env_step(grx_env* e, const float* actions, void* stream) {
       for (int w : e->final_idx) e->needs_reset[w] = 1;
     e->final_idx.clear();
   }
+  if (!ordered) ENV_GRX(grx_fetch_post_step(e->cost, e->cost_ema, kBalanceAlpha, e->n, e->slots_per_xcd, e->order, nullptr, nullptr, s));      // no world ended (or one world, reset in line)
   return 0;
 }
 

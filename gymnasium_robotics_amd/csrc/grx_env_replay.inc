@@ -3,7 +3,7 @@
 // gymnasium_robotics_amd/her.py (HerReplay, continuous=True) without its host mirrors: the worlds whose row of a step is a reset row are read from the index list the step
 // left on the device (grx_env::step_list: a host-known length for the Fetch and the host-bookkeeping maze handles, the device word rcount behind rlist for a maze handle
 // with device-side bookkeeping), and "is there anything to sample" is answered by the sampling kernel (grx_her_sample_relabel, grx_capi.h).  Per step: one append kernel,
-// two relabel kernels, no copy, nothing read back.
+// one relabel kernel, no copy, nothing read back.
 
 struct grx_replay {
   grx_env* e = nullptr;
@@ -12,7 +12,7 @@ struct grx_replay {
   uint64_t seed = 0, calls = 0;
   bool track = false;             // keep_final in same-step mode: prev_start / term_t / terminal rows are live
   float *episode = nullptr, *actions = nullptr, *rows = nullptr, *term_rows = nullptr;      // term_rows: the replay's own [N, W] (maze) or the Fetch handle's final_packed
-  int *start = nullptr, *prev_start = nullptr, *term_t = nullptr, *scratch = nullptr, *valid = nullptr;
+  int *start = nullptr, *prev_start = nullptr, *term_t = nullptr, *valid = nullptr;
   std::vector<void*> allocs;
   int t = 0;                      // absolute index of the newest row
   bool begun = false;
@@ -22,59 +22,11 @@ struct grx_replay {
 
 namespace {
 
-struct ReplayAppend {
-  const float *packed, *action;      // the handle's rows of this step: [N, W], [N, act_dim]
-  float *row_dst, *act_dst;          // ring row (t + 1) % R of the two rings
-  long long n_row, n_act;            // words
-  const int* list;                   // worlds whose row is the first of a new episode
-  const int* count_dev;              // its length in device memory, or NULL: `count`
-  int count, max_n, t;
-  int *start, *prev_start, *term_t;  // prev_start / term_t NULL: only episode_start is kept
-  const float* final_rows;           // [count, W] terminal rows in list order, scattered to term_rows [N, W]; both NULL: nothing to scatter
-  float* term_rows;
-  int W;
-};
-
-// flat copy of n words by the whole grid: 16-byte accesses when both bases allow (the handle's rows always do; a ring row does unless N W is odd), the tail word by word
-__device__ __forceinline__ void replay_copy(float* __restrict__ dst, const float* __restrict__ src, long long n, long long tid, long long nth) {
-  if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0) {
-    const long long n4 = n >> 2;
-    const float4* __restrict__ s4 = (const float4*)src;
-    float4* __restrict__ d4 = (float4*)dst;
-    for (long long i = tid; i < n4; i += nth) d4[i] = s4[i];
-    for (long long i = (n4 << 2) + tid; i < n; i += nth) dst[i] = src[i];
-  } else {
-    for (long long i = tid; i < n; i += nth) dst[i] = src[i];
-  }
-}
-
-// HerReplay.append in one launch: the two row copies, grx_her_mark_resets for the listed worlds, the terminal-row scatter.  The marks of a world touch only that world's
-// three words and the copies only the ring row, so the parts are independent: grid-stride loops, no atomics, no ordering between workgroups.
-__global__ void __launch_bounds__(256) grx_replay_append_kernel(ReplayAppend a) {
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
-  replay_copy(a.row_dst, a.packed, a.n_row, tid, nth);
-  replay_copy(a.act_dst, a.action, a.n_act, tid, nth);
-  int k = a.count_dev ? *a.count_dev : a.count;
-  k = k < 0 ? 0 : (k > a.max_n ? a.max_n : k);
-  for (long long j = tid; j < k; j += nth) {
-    const int w = a.list[j];
-    if ((unsigned)w >= (unsigned)a.max_n) continue;
-    if (a.prev_start) { a.prev_start[w] = a.start[w]; a.term_t[w] = a.t; }
-    a.start[w] = a.t;
-  }
-  if (a.term_rows)
-    for (long long i = tid; i < (long long)k * a.W; i += nth) {
-      const long long j = i / a.W;
-      const int w = a.list[j];
-      if ((unsigned)w < (unsigned)a.max_n) a.term_rows[(size_t)w * a.W + (i - j * a.W)] = a.final_rows[i];
-    }
-}
-
 // HerReplay.begin_episode + set_episode_start(-elapsed): row 0 <- the packed rows; episode_start from the device counters (elapsed NULL: the host uploaded it already)
 __global__ void __launch_bounds__(256) grx_replay_begin_kernel(const float* __restrict__ packed, float* __restrict__ row0, long long n_row, const long long* __restrict__ elapsed, int n,
                                                                int* __restrict__ start, int* __restrict__ prev_start, int* __restrict__ term_t) {
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
-  replay_copy(row0, packed, n_row, tid, nth);
+  grx_copy_words(row0, packed, n_row, tid, nth);
   for (long long w = tid; w < n; w += nth) {
     if (elapsed) start[w] = -(int)elapsed[w];
     prev_start[w] = 0;
@@ -131,7 +83,7 @@ extern "C" int grx_replay_create(grx_env* e, const grx_replay_config* cfg, grx_r
     ENV_TRY(replay_zalloc(r, &r->actions, (size_t)r->R * n * r->ad));
     ENV_TRY(replay_zalloc(r, &r->rows, (size_t)r->capacity * r->OW));
     ENV_TRY(replay_zalloc(r, &r->start, n)); ENV_TRY(replay_zalloc(r, &r->prev_start, n)); ENV_TRY(replay_zalloc(r, &r->term_t, n));
-    ENV_TRY(replay_zalloc(r, &r->scratch, (size_t)3 * r->max_batch)); ENV_TRY(replay_zalloc(r, &r->valid, 1));
+    ENV_TRY(replay_zalloc(r, &r->valid, 1));
     ENV_HIP(hipMemset(r->term_t, 0xFF, n * 4));      // -1: no episode has ended yet
     if (r->track) {
       if (e->mz) ENV_TRY(replay_zalloc(r, &r->term_rows, n * r->W));
@@ -204,20 +156,19 @@ extern "C" int grx_replay_append(grx_replay* r, void* stream) {
   if (r->t == INT32_MAX - 1) return fail(GRX_ENV_EINVAL, "grx_replay_append: row counter exhausted: call grx_replay_begin");
   DeviceGuard g(e->device);
   const int t = r->t + 1, row = t % r->R;
-  ReplayAppend a;
+  grx_her_append_args a;      // HerReplay.append in one launch (grx_capi.h grx_her_append): the two row copies, the marks of the listed worlds, the terminal-row scatter
   std::memset(&a, 0, sizeof a);
   a.packed = replay_packed(e); a.action = replay_action(e);
   a.n_row = (long long)r->n * r->W; a.n_act = (long long)r->n * r->ad;
   a.row_dst = r->episode + (size_t)row * a.n_row; a.act_dst = r->actions + (size_t)row * a.n_act;
-  a.list = e->step_list; a.count_dev = e->step_count_dev; a.count = e->step_list ? e->step_count : 0; a.max_n = r->n; a.t = t;
+  a.list = e->step_list; a.count_dev = e->step_list ? e->step_count_dev : nullptr; a.count = e->step_list ? e->step_count : 0; a.n_worlds = r->n; a.t = t;
   a.start = r->start;
   if (r->track) {
     a.prev_start = r->prev_start; a.term_t = r->term_t;
-    if (e->mz) { a.final_rows = e->mz->final_rows; a.term_rows = r->term_rows; }
+    if (e->mz && a.list) { a.final_rows = e->mz->final_rows; a.term_rows = r->term_rows; }
   }
   a.W = r->W;
-  hipLaunchKernelGGL(grx_replay_append_kernel, dim3(replay_blocks(a.n_row)), dim3(256), 0, (hipStream_t)stream, a);
-  ENV_HIP(hipGetLastError());
+  ENV_GRX(grx_her_append(&a, stream));
   r->t = t;
   r->last_step = e->steps;
   return 0;
@@ -233,7 +184,8 @@ extern "C" int grx_replay_relabel(grx_replay* r, int64_t batch, int k_future, gr
   if (r->head + batch > r->capacity) r->head = 0;      // every batch contiguous (a ring of whole batches)
   grx_her_args a = r->ha;
   a.out = r->rows + (size_t)r->head * r->OW;
-  ENV_GRX(grx_her_sample_relabel(&a, r->start, r->track ? r->prev_start : nullptr, r->t, k_future, r->seed, r->calls, batch, r->scratch, r->valid, stream));
+  ENV_GRX(grx_her_sample_relabel(&a, r->start, r->track ? r->prev_start : nullptr, r->t, k_future, r->seed, r->calls, batch,
+                                 /* scratch: unused since the draws stay in the workgroup, any non-null pointer */ r->valid, r->valid, stream));
   r->calls += 1;
   if (out) { out->rows = a.out; out->batch = batch; out->offset = r->head; out->valid = r->valid; }
   r->head += batch;

@@ -35,6 +35,7 @@
 #include "grx_adroit_task.h"
 #include "grx_kitchen_task.h"
 #include "grx_host_model.h"
+#include "grx_copy.h"
 
 static_assert(sizeof(grx_fetch_task) == sizeof(GrxFetchTask), "grx_fetch_task must mirror GrxFetchTask");
 static_assert(sizeof(grx_fetch_buffers) == sizeof(GrxFetchBuffers), "grx_fetch_buffers must mirror GrxFetchBuffers");
@@ -1252,12 +1253,13 @@ GRX_DEV void grx_her_outcome(const GrxHerArgs& a, const float* ag, const float* 
   }
 }
 // word e of output row b (the whole arithmetic of the relabel: both kernels below write exactly this value)
-GRX_DEV float grx_her_word(const GrxHerArgs& a, long long b, int e) {
+// (ti, w, tg): the sample's draws -- absolute row, world, goal row
+GRX_DEV float grx_her_word_at(const GrxHerArgs& a, int ti, int w, int tg, int e) {
   const int od = a.obs_dim, gd = a.goal_dim, ad = a.act_dim, OW = 2 * od + 3 * gd + ad + 2;
-  const int R = a.T + 1, t = a.t_idx[b] % R, t1 = (a.t_idx[b] + 1) % R, w = a.w_idx[b], tg = a.t_goal[b];
+  const int R = a.T + 1, t = ti % R, t1 = (ti + 1) % R;
   const int tt = a.term_t ? a.term_t[w] : -1;   // the row index whose ring entry is the first row of a new episode; the terminal row is in term_rows[w]
   const float* r0 = a.rows + ((size_t)t * a.N + w) * a.W;
-  const float* r1 = (a.t_idx[b] + 1 == tt) ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)t1 * a.N + w) * a.W;
+  const float* r1 = (ti + 1 == tt) ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)t1 * a.N + w) * a.W;
   const float* g = tg < 0 ? r0 + od + gd : ((tg == tt ? a.term_rows + (size_t)w * a.W : a.rows + ((size_t)(tg % R) * a.N + w) * a.W) + od);   // the substituted goal: achieved at row tg
   float v;
   if (e < od + gd) v = r0[e];
@@ -1271,6 +1273,7 @@ GRX_DEV float grx_her_word(const GrxHerArgs& a, long long b, int e) {
   } else v = r1[e - (od + 2 * gd + ad + 1)];
   return v;
 }
+GRX_DEV float grx_her_word(const GrxHerArgs& a, long long b, int e) { return grx_her_word_at(a, a.t_idx[b], a.w_idx[b], a.t_goal[b], e); }
 extern "C" __global__ void __launch_bounds__(256)
 grx_her_relabel_kernel(GrxHerArgs a, long long B) {
   const int OW = 2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2;
@@ -1623,21 +1626,22 @@ extern "C" int grx_kitchen_step(const grx_model* m, const grx_kitchen_task* task
 // Cost-ordered dispatch, device side: one workgroup per XCD slice sorts (cost, world) keys of its contiguous `per` worlds in LDS
 // (bitonic, descending cost, ties by world index) and writes order[i * 8 + slice] = the i-th most expensive world of the slice --
 // workgroup b of the next step launch runs on XCD b & 7 and starts in index order.
+// key of position i of a slice (i >= per: padding, sorts last); updates the moving average of the world's cost
+static __device__ __forceinline__ unsigned long long grx_order_key(const int* __restrict__ cost, float* __restrict__ ema, float alpha, int base, int per, int i) {
+  if (i >= per) return 0ull;
+  // the sort key: the last cost, or its exponential moving average (a world's cost has a persistent part -- is the object in contact -- and
+  // a per-step part; averaging predicts the next step better than the last sample alone)
+  float c = (float)cost[base + i];
+  if (ema) { c = (1.0f - alpha) * ema[base + i] + alpha * c; ema[base + i] = c; }
+  const unsigned k = (unsigned)fminf(fmaxf(c * 16.0f, 0.0f), 4.0e9f);
+  return ((unsigned long long)k << 32) | (unsigned)(0x7FFFFFFF - i);
+}
+static __device__ void grx_order_place(const unsigned long long* keys, int s, int base, int per, int slots, int* __restrict__ order);
 extern "C" __global__ void __launch_bounds__(256)
 grx_order_kernel(const int* __restrict__ cost, float* __restrict__ ema, float alpha, int per, int npow2, int slots, int* __restrict__ order) {
   extern __shared__ unsigned long long keys[];
   const int s = blockIdx.x, base = s * per;
-  for (int i = threadIdx.x; i < npow2; i += 256) {
-    unsigned k = 0;
-    if (i < per) {
-      // the sort key: the last cost, or its exponential moving average (a world's cost has a persistent part -- is the object in contact -- and
-      // a per-step part; averaging predicts the next step better than the last sample alone)
-      float c = (float)cost[base + i];
-      if (ema) { c = (1.0f - alpha) * ema[base + i] + alpha * c; ema[base + i] = c; }
-      k = (unsigned)fminf(fmaxf(c * 16.0f, 0.0f), 4.0e9f);
-    }
-    keys[i] = i < per ? (((unsigned long long)k << 32) | (unsigned)(0x7FFFFFFF - i)) : 0ull;   // padding sorts last
-  }
+  for (int i = threadIdx.x; i < npow2; i += 256) keys[i] = grx_order_key(cost, ema, alpha, base, per, i);
   __syncthreads();
   for (int k = 2; k <= npow2; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -1651,6 +1655,10 @@ grx_order_kernel(const int* __restrict__ cost, float* __restrict__ ema, float al
       }
       __syncthreads();
     }
+  grx_order_place(keys, s, base, per, slots, order);
+}
+// keys: the slice's sorted list (descending) in LDS, complete for every thread of the 256-thread workgroup -> order
+static __device__ void grx_order_place(const unsigned long long* keys, int s, int base, int per, int slots, int* __restrict__ order) {
   // Two worlds per wave slot (per <= 2 * slots: BASELINE cfg 2, 4096 worlds on 2048 slots).  K predicted stragglers -- worlds that take longer than the two
   // cheapest worlds one after the other (the arm resting on the head: two hull pairs in contact) -- hold their slots for the whole launch, so M = per - 2 slots + K
   // workgroups have to be a slot's THIRD world.  With the plain descending order those are dispatched when the first slots finish their second world, two MEDIAN
@@ -1805,6 +1813,33 @@ grx_her_sample_valid_kernel(const int* __restrict__ start, const int* __restrict
     if (b == 0) *valid = found ? (int)B : 0;
   }
 }
+// The draws and the rows in ONE launch (grx_her_draw_relabel): a workgroup takes GRX_HER_CHUNK consecutive samples at a time, its first threads make their draws
+// (grx_her_draw: the very values the sample kernels write) and hand them over in LDS, then all 256 threads write the chunk's output words (grx_her_word_at: the relabel
+// kernels' arithmetic).  No index array goes through HBM.  valid (or NULL: the caller knows that a world with a transition exists): sample 0 reports valid[0] = B or 0, and
+// a sample that found no world zero-fills its row -- then every sample found none (grx_her_draw), which is what the relabel kernel reads from *valid.
+#define GRX_HER_CHUNK 32
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_draw_relabel_kernel(GrxHerArgs a, const int* __restrict__ start, const int* __restrict__ prev_start, int t_now, int k_future, unsigned long long seed,
+                            unsigned long long call, long long B, int* __restrict__ valid) {
+  __shared__ int s_t[GRX_HER_CHUNK], s_w[GRX_HER_CHUNK], s_g[GRX_HER_CHUNK], s_ok[GRX_HER_CHUNK];
+  const int OW = 2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2, x = threadIdx.x;
+  for (long long b0 = (long long)blockIdx.x * GRX_HER_CHUNK; b0 < B; b0 += (long long)gridDim.x * GRX_HER_CHUNK) {
+    const int rows = B - b0 < GRX_HER_CHUNK ? (int)(B - b0) : GRX_HER_CHUNK;
+    if (x < rows) {
+      int t, w, tg;
+      const bool found = grx_her_draw(start, prev_start, a.term_t, a.N, t_now, a.T, k_future, seed, call, b0 + x, &t, &w, &tg);
+      s_t[x] = t; s_w[x] = w; s_g[x] = tg; s_ok[x] = (found || !valid) ? 1 : 0;
+      if (valid && b0 + x == 0) *valid = found ? (int)B : 0;
+    }
+    __syncthreads();
+    float* __restrict__ out = a.out + b0 * OW;
+    for (int i = x; i < rows * OW; i += 256) {
+      const int r = i / OW;
+      out[i] = s_ok[r] ? grx_her_word_at(a, s_t[r], s_w[r], s_g[r], i - r * OW) : 0.0f;
+    }
+    __syncthreads();
+  }
+}
 extern "C" int grx_her_sample_final(const int* episode_start, const int* prev_start, const int* term_t, int n_worlds, int t_now, int T, int k_future, uint64_t seed,
                                     uint64_t call, int64_t batch, int* t_idx, int* w_idx, int* t_goal, void* stream) {
   if (!episode_start || !t_idx || !w_idx || !t_goal) return fail("grx_her_sample: null argument");
@@ -1822,30 +1857,35 @@ extern "C" int grx_her_sample(const int* episode_start, int n_worlds, int t_now,
                               int* t_idx, int* w_idx, int* t_goal, void* stream) {
   return grx_her_sample_final(episode_start, nullptr, nullptr, n_worlds, t_now, T, k_future, seed, call, batch, t_idx, w_idx, t_goal, stream);
 }
-extern "C" int grx_her_sample_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call,
-                                      int64_t batch, int* scratch, int* valid, void* stream) {
-  if (!args || !episode_start || !scratch || !valid) return fail("grx_her_sample_relabel: null argument");
+static int grx_her_draw_relabel_impl(const char* who, const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed,
+                                     uint64_t call, int64_t batch, int* valid, void* stream) {
   GrxHerArgs a; memcpy(&a, args, sizeof(a));
-  if (!a.rows || !a.acts || !a.out) return fail("grx_her_sample_relabel: null buffer");
+  if (!a.rows || !a.acts || !a.out) return fail(std::string(who) + ": null buffer");
   if ((a.term_rows == nullptr) != (a.term_t == nullptr) || (prev_start == nullptr) != (a.term_t == nullptr))
-    return fail("grx_her_sample_relabel: term_rows, term_t and prev_start go together");
+    return fail(std::string(who) + ": term_rows, term_t and prev_start go together");
   if (a.T <= 0 || a.N <= 0 || a.obs_dim <= 0 || a.goal_dim <= 0 || a.goal_dim > 16 || a.act_dim <= 0 || a.W < a.obs_dim + 2 * a.goal_dim)
-    return fail("grx_her_sample_relabel: dimensions out of range (goal_dim <= 16, W >= obs_dim + 2 goal_dim)");
+    return fail(std::string(who) + ": dimensions out of range (goal_dim <= 16, W >= obs_dim + 2 goal_dim)");
   if (a.kind < 0 || a.kind > 3 || (a.kind == 0 && a.goal_dim != 3) || (a.kind == 2 && a.goal_dim != 2) || (a.kind == 3 && a.goal_dim != 7))
-    return fail("grx_her_sample_relabel: reward kind does not fit goal_dim");
-  if (t_now < 0 || k_future < 0 || batch <= 0 || batch > (1ll << 30)) return fail("grx_her_sample_relabel: t_now, k_future >= 0 and 1 <= batch <= 2^30");
-  a.t_idx = scratch; a.w_idx = scratch + batch; a.t_goal = scratch + 2 * batch;
-  long long blocks = (batch + 255) / 256;
+    return fail(std::string(who) + ": reward kind does not fit goal_dim");
+  if (t_now < 0 || k_future < 0 || batch <= 0 || batch > (1ll << 30)) return fail(std::string(who) + ": t_now, k_future >= 0 and 1 <= batch <= 2^30");
+  a.t_idx = a.w_idx = a.t_goal = nullptr;
+  long long blocks = (batch + GRX_HER_CHUNK - 1) / GRX_HER_CHUNK;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(grx_her_sample_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, episode_start, prev_start, a.term_t, a.N, t_now, a.T, k_future,
-                     (unsigned long long)seed, (unsigned long long)call, (long long)batch, scratch, scratch + batch, scratch + 2 * batch, valid);
-  HIP_OK(hipGetLastError());
-  const long long words = (long long)batch * (2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2);
-  blocks = (words + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(grx_her_relabel_valid_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (long long)batch, (const int*)valid);
+  hipLaunchKernelGGL(grx_her_draw_relabel_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, episode_start, prev_start, t_now, k_future,
+                     (unsigned long long)seed, (unsigned long long)call, (long long)batch, valid);
   HIP_OK(hipGetLastError());
   return 0;
+}
+extern "C" int grx_her_draw_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call,
+                                    int64_t batch, int* valid, void* stream) {
+  if (!args || !episode_start) return fail("grx_her_draw_relabel: null argument");
+  if (!valid && t_now <= 0) return fail("grx_her_draw_relabel: without valid the caller vouches for a world with a transition (t_now > 0)");
+  return grx_her_draw_relabel_impl("grx_her_draw_relabel", args, episode_start, prev_start, t_now, k_future, seed, call, batch, valid, stream);
+}
+extern "C" int grx_her_sample_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call,
+                                      int64_t batch, int* scratch, int* valid, void* stream) {
+  if (!args || !episode_start || !scratch || !valid) return fail("grx_her_sample_relabel: null argument");      // (scratch: unused since the draws stay in the workgroup)
+  return grx_her_draw_relabel_impl("grx_her_sample_relabel", args, episode_start, prev_start, t_now, k_future, seed, call, batch, valid, stream);
 }
 extern "C" __global__ void __launch_bounds__(256)
 grx_her_mark_kernel(const unsigned char* __restrict__ mask, int N, int t, int* __restrict__ start, int* __restrict__ prev_start, int* __restrict__ term_t) {
@@ -1858,6 +1898,49 @@ extern "C" int grx_her_mark_resets(const unsigned char* reset_mask, int n_worlds
   if (!reset_mask || !episode_start || n_worlds <= 0) return fail("grx_her_mark_resets: null argument");
   if ((prev_start == nullptr) != (term_t == nullptr)) return fail("grx_her_mark_resets: prev_start and term_t go together");
   hipLaunchKernelGGL(grx_her_mark_kernel, dim3((unsigned)((n_worlds + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reset_mask, n_worlds, t, episode_start, prev_start, term_t);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// HerReplay.append in one launch (include/grx_capi.h, grx_her_append): the two row copies, the episode marks of the reset worlds, the terminal-row scatter.  The marks of a
+// world touch only that world's three words and the copies only the ring row, so the parts are independent: grid-stride loops, no atomics, no ordering between workgroups.
+static __device__ __forceinline__ void grx_her_mark(const grx_her_append_args& a, int w) {
+  if (a.prev_start) { a.prev_start[w] = a.start[w]; a.term_t[w] = a.t; }
+  a.start[w] = a.t;
+}
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_append_kernel(grx_her_append_args a) {
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+  grx_copy_words(a.row_dst, a.packed, a.n_row, tid, nth);
+  grx_copy_words(a.act_dst, a.action, a.n_act, tid, nth);
+  if (a.mask)
+    for (long long w = tid; w < a.n_worlds; w += nth)
+      if (a.mask[w]) grx_her_mark(a, (int)w);
+  if (!a.list) return;
+  int k = a.count_dev ? *a.count_dev : a.count;
+  k = k < 0 ? 0 : (k > a.n_worlds ? a.n_worlds : k);
+  for (long long j = tid; j < k; j += nth) {
+    const int w = a.list[j];
+    if ((unsigned)w < (unsigned)a.n_worlds) grx_her_mark(a, w);
+  }
+  if (a.term_rows)
+    for (long long i = tid; i < (long long)k * a.W; i += nth) {
+      const long long j = i / a.W;
+      const int w = a.list[j];
+      if ((unsigned)w < (unsigned)a.n_worlds) a.term_rows[(size_t)w * a.W + (i - j * a.W)] = a.final_rows[i];
+    }
+}
+extern "C" int grx_her_append(const grx_her_append_args* args, void* stream) {
+  if (!args) return fail("grx_her_append: null argument");
+  const grx_her_append_args& a = *args;
+  if (!a.packed || !a.action || !a.row_dst || !a.act_dst || !a.start) return fail("grx_her_append: null buffer");
+  if (a.n_worlds <= 0 || a.n_row <= 0 || a.n_act <= 0 || a.W <= 0) return fail("grx_her_append: bad dimensions");
+  if ((a.prev_start == nullptr) != (a.term_t == nullptr)) return fail("grx_her_append: prev_start and term_t go together");
+  if (a.list && a.mask) return fail("grx_her_append: the reset worlds come as a list or as a mask, not both");
+  if ((a.term_rows == nullptr) != (a.final_rows == nullptr) || (a.term_rows && !a.list)) return fail("grx_her_append: final_rows and term_rows go together, with a list");
+  long long blocks = (a.n_row / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  hipLaunchKernelGGL(grx_her_append_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1941,10 +2024,8 @@ extern "C" int grx_hand_commit_rows(const grx_hand_commit_args* args, void* stre
 
 // commit of an overlapped Fetch reset (include/grx_capi.h): one 64-thread workgroup per listed world; staged rows are indexed by WORLD (the reset kernel wrote them through a
 // second grx_fetch_buffers)
-extern "C" __global__ void __launch_bounds__(64)
-grx_fetch_commit_kernel(grx_fetch_commit_args a) {
-  const int j = blockIdx.x, l = threadIdx.x;
-  if (j >= a.k) return;
+// rows: [k, obs_dim + 8] or NULL -- the terminal row of world idx[j] also goes to rows[j] (the compact block behind info["final_obs"])
+static __device__ __forceinline__ void grx_fetch_commit_world(const grx_fetch_commit_args& a, int j, int l, float* __restrict__ rows) {
   const size_t w = (size_t)a.idx[j];
   const int od = a.obs_dim, pw = od + 8;
   for (int i = l; i < a.nq; i += 64) a.qpos[w * a.nq + i] = a.s_qpos[w * a.nq + i];
@@ -1956,18 +2037,119 @@ grx_fetch_commit_kernel(grx_fetch_commit_args a) {
   for (int i = l; i < pw; i += 64) {      // the thread that parks a word of the terminal row is the one that overwrites it
     const float old = a.packed[w * pw + i];
     if (a.final_packed) a.final_packed[w * pw + i] = old;
+    if (rows) rows[(size_t)j * pw + i] = old;
     a.packed[w * pw + i] = i < od ? a.s_obs[w * od + i] : (i < od + 3 ? a.s_achieved[w * 3 + i - od] : (i < od + 6 ? a.s_goal[w * 3 + i - od - 3] : old));
   }
   if (l == 0) a.status[w] = grx_status_word(a.status[w], a.s_status[w]);
 }
+extern "C" __global__ void __launch_bounds__(64)
+grx_fetch_commit_kernel(grx_fetch_commit_args a) {
+  if ((int)blockIdx.x < a.k) grx_fetch_commit_world(a, blockIdx.x, threadIdx.x, nullptr);
+}
+static int grx_fetch_commit_check(const grx_fetch_commit_args& a, const char* who) {
+  if (!a.idx || !a.s_qpos || !a.s_qvel || !a.s_qacc_ws || !a.s_aux || !a.s_goal || !a.s_obs || !a.s_achieved || !a.s_status || !a.qpos || !a.qvel || !a.qacc_ws || !a.aux ||
+      !a.goal || !a.obs || !a.achieved || !a.packed || !a.status || (a.mocap_words > 0 && (!a.s_mocap || !a.mocap))) return fail(std::string(who) + ": null buffer");
+  if (a.nq <= 0 || a.nv <= 0 || a.obs_dim <= 0 || a.mocap_words < 0) return fail(std::string(who) + ": bad dimensions");
+  return 0;
+}
 extern "C" int grx_fetch_commit_rows(const grx_fetch_commit_args* args, void* stream) {
   if (!args) return fail("grx_fetch_commit_rows: null argument");
   const grx_fetch_commit_args& a = *args;
-  if (!a.idx || !a.s_qpos || !a.s_qvel || !a.s_qacc_ws || !a.s_aux || !a.s_goal || !a.s_obs || !a.s_achieved || !a.s_status || !a.qpos || !a.qvel || !a.qacc_ws || !a.aux ||
-      !a.goal || !a.obs || !a.achieved || !a.packed || !a.status || (a.mocap_words > 0 && (!a.s_mocap || !a.mocap))) return fail("grx_fetch_commit_rows: null buffer");
-  if (a.nq <= 0 || a.nv <= 0 || a.obs_dim <= 0 || a.mocap_words < 0) return fail("grx_fetch_commit_rows: bad dimensions");
+  if (grx_fetch_commit_check(a, "grx_fetch_commit_rows")) return -1;
   if (a.k <= 0) return 0;
   hipLaunchKernelGGL(grx_fetch_commit_kernel, dim3((unsigned)a.k), dim3(64), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// Everything behind a Fetch step in ONE launch (include/grx_capi.h, grx_fetch_post_step).  Workgroups [0, n_sort) order one XCD slice each for the next step launch,
+// workgroups [n_sort, ...) commit four listed worlds each (a wave per world: the lane arithmetic of grx_fetch_commit_kernel).  The two halves share no data.
+//
+// The sort holds E = P / 256 keys per thread in registers (key e of thread x is position x + 256 e of the bitonic network, P = the slice padded to a power of two >= 256):
+// a compare-exchange at stride j < 64 is a wave shuffle (position bits 0-5 are the lane), at stride j >= 64 the keys go through LDS (one write, one read, two barriers).
+// At 512 keys that is 6 exchanges through LDS and 39 in registers, against grx_order_kernel's 45 barrier-separated passes over LDS.  Keys are unique (cost, world), so the
+// sorted list -- and with it `order` -- is grx_order_kernel's.
+template <int E>
+static __device__ __forceinline__ void grx_order_sort(unsigned long long* __restrict__ lds, const int* __restrict__ cost, float* __restrict__ ema, float alpha, int s, int per,
+                                                      int slots, int* __restrict__ order) {
+  constexpr int P = 256 * E;
+  const int x = threadIdx.x, base = s * per;
+  unsigned long long key[E];
+#pragma unroll
+  for (int e = 0; e < E; e++) key[e] = grx_order_key(cost, ema, alpha, base, per, x + 256 * e);
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (j >= 64) {
+#pragma unroll
+        for (int e = 0; e < E; e++) lds[x + 256 * e] = key[e];
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+          const int i = x + 256 * e;
+          const unsigned long long o = lds[i ^ j];
+          const bool keep_max = ((i & k) == 0) == ((i & j) == 0);      // descending run and the lower position, or ascending run and the upper one
+          key[e] = keep_max ? (key[e] > o ? key[e] : o) : (key[e] < o ? key[e] : o);
+        }
+        __syncthreads();
+      } else {
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+          const int i = x + 256 * e;
+          const unsigned long long o = __shfl_xor(key[e], j);
+          const bool keep_max = ((i & k) == 0) == ((i & j) == 0);
+          key[e] = keep_max ? (key[e] > o ? key[e] : o) : (key[e] < o ? key[e] : o);
+        }
+      }
+    }
+#pragma unroll
+  for (int e = 0; e < E; e++) lds[x + 256 * e] = key[e];
+  __syncthreads();
+  grx_order_place(lds, s, base, per, slots, order);
+}
+extern "C" __global__ void __launch_bounds__(256)
+grx_fetch_post_step_kernel(const int* __restrict__ cost, float* __restrict__ ema, float alpha, int per, int epl, int slots, int* __restrict__ order, int n_sort,
+                           grx_fetch_commit_args a, float* __restrict__ rows) {
+  extern __shared__ unsigned long long post_keys[];
+  if ((int)blockIdx.x < n_sort) {      // (uniform per workgroup: the barriers inside are reached by all of its threads)
+    const int s = blockIdx.x;
+    switch (epl) {
+      case 1: grx_order_sort<1>(post_keys, cost, ema, alpha, s, per, slots, order); break;
+      case 2: grx_order_sort<2>(post_keys, cost, ema, alpha, s, per, slots, order); break;
+      case 4: grx_order_sort<4>(post_keys, cost, ema, alpha, s, per, slots, order); break;
+      case 8: grx_order_sort<8>(post_keys, cost, ema, alpha, s, per, slots, order); break;
+      case 16: grx_order_sort<16>(post_keys, cost, ema, alpha, s, per, slots, order); break;
+      default: grx_order_sort<32>(post_keys, cost, ema, alpha, s, per, slots, order); break;
+    }
+    return;
+  }
+  // (the commit workgroups get the sort's dynamic LDS -- 2 KB per 256 worlds of a slice, 4 KB at 4 096 worlds, 64 KB at the largest batch -- without using it: at very
+  // large batches that bounds how many of them share a CU; they are short and few, one per four reset worlds)
+  const int j = ((int)blockIdx.x - n_sort) * 4 + (int)(threadIdx.x >> 6);
+  if (j < a.k) grx_fetch_commit_world(a, j, threadIdx.x & 63, rows);
+}
+extern "C" int grx_fetch_post_step(const int* cost, float* ema, float alpha, int n_worlds, int slots_per_xcd, int* order, const grx_fetch_commit_args* commit, float* final_rows,
+                                   void* stream) {
+  int per = 0, epl = 1, n_sort = 0;
+  if (order) {
+    if (!cost) return fail("grx_fetch_post_step: order without cost");
+    if (ema && !(alpha > 0.0f && alpha <= 1.0f)) return fail("grx_fetch_post_step: alpha must be in (0, 1]");
+    if (n_worlds <= 0 || (n_worlds & 7)) return fail("grx_fetch_post_step: the number of worlds must be a positive multiple of 8 (one contiguous slice per XCD)");
+    per = n_worlds >> 3;
+    while (256 * epl < per) epl <<= 1;
+    if (epl > 32) return fail("grx_fetch_post_step: more than 65536 worlds per launch are not supported");
+    n_sort = 8;
+  }
+  grx_fetch_commit_args a;
+  memset(&a, 0, sizeof(a));
+  if (commit) {
+    a = *commit;
+    if (grx_fetch_commit_check(a, "grx_fetch_post_step")) return -1;
+    if (a.k < 0) a.k = 0;
+  }
+  const unsigned grid = (unsigned)n_sort + (unsigned)((a.k + 3) / 4);
+  if (grid == 0) return 0;
+  hipLaunchKernelGGL(grx_fetch_post_step_kernel, dim3(grid), dim3(256), n_sort ? (size_t)256 * epl * 8 : 0, (hipStream_t)stream, cost, ema, alpha, per, epl,
+                     slots_per_xcd < 0 ? 0 : slots_per_xcd, order, n_sort, a, final_rows);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -176,7 +176,10 @@ class FetchVecEnv(GoalVecEnv):
                 l1.record()
                 self.step_events.append((l0, l1))
         if self.balance:
-            self._rebalance()
+            if self._defer_order:      # fused tail: the launch that commits this step's reset rows sorts the next order as well (step())
+                self._order_pending = True
+            else:
+                self._rebalance()
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, n):
@@ -193,6 +196,13 @@ class FetchVecEnv(GoalVecEnv):
         # expensive worlds while the rest of the chip idles.  Worlds stay inside their XCD's slice (L2 locality of neighbouring rows).
         self.balance = bool(self.balance) and n % 8 == 0 and 1024 <= n <= 65536 * 8   # grx_order_by_cost sorts one XCD slice (n / 8 worlds, <= 65536) per workgroup in LDS
         self._reset_stage = z(n, 6)   # device side of the reset staging buffer (see _reset_worlds)
+        # Fused tail (include/grx_capi.h grx_fetch_post_step): in same-step mode ONE launch behind the step launch sorts the next dispatch order, commits the overlapped reset and
+        # writes the terminal rows of info["final_obs"] compactly -- instead of the order kernel, the commit kernel and a gather.  GRX_FETCH_FUSED_TAIL=0: those launches (A/B, tests).
+        self._fused = os.environ.get("GRX_FETCH_FUSED_TAIL", "1") != "0"
+        self._defer_order, self._order_pending = False, False
+        # the worlds the last step() reset inside the step (same-step autoreset): (int32 device index tensor, host count), valid until the next step(); None otherwise.
+        # HerReplay.append marks their episode boundaries from it instead of uploading a mask.
+        self.step_reset_list = None
         self.packed = z(n, self.obs_dim + 8)   # [obs | achieved | desired | reward | success] rows written by the step kernel (cross-rank gather, parallel.py)
         self.final_packed = z(n, self.obs_dim + 8)   # same-step autoreset: row w = the TERMINAL packed row of world w's last finished episode (info["final_obs"], HerReplay.append(final_rows=...))
         self.cost = torch.zeros(n, dtype=torch.int32, device=d) if self.balance else None
@@ -371,8 +381,17 @@ class FetchVecEnv(GoalVecEnv):
             done.record(self._ahead_stream)
         return staged, done
 
-    def _commit_ahead(self, ahead, idx):
-        """behind the step kernel (and the re-run of the worlds that overflowed its tables): the staged reset rows replace the live ones (grx_fetch_commit_rows)"""
+    def _post_step(self, commit=None, rows=None):
+        """grx_fetch_post_step: the pending order of the next launch and / or the commit of the overlapped reset (rows: [k, W] <- the terminal rows), one launch"""
+        order = self._order_pending
+        self._order_pending = False
+        _native.check(self._L.grx_fetch_post_step(self.cost.data_ptr() if order else None, self.cost_ema.data_ptr() if order else None, self.balance_alpha, self.num_envs,
+                                                  self._slots_per_xcd, self.order.data_ptr() if order else None, None if commit is None else ctypes.byref(commit),
+                                                  None if rows is None else rows.data_ptr(), self._stream()))
+
+    def _commit_ahead(self, ahead, idx, rows=None):
+        """behind the step kernel (and the re-run of the worlds that overflowed its tables): the staged reset rows replace the live ones (grx_fetch_commit_rows, or the fused
+        grx_fetch_post_step, which also fills rows [k, W] with the terminal rows)"""
         (n, idx_dev, _), done = ahead
         torch.cuda.current_stream(self.device).wait_event(done)
         A = self._ahead
@@ -381,7 +400,10 @@ class FetchVecEnv(GoalVecEnv):
                                           A["obs"].data_ptr(), A["achieved"].data_ptr(), A["status"].data_ptr(),
                                           self.qpos.data_ptr(), self.qvel.data_ptr(), self.qacc_ws.data_ptr(), self.mocap.data_ptr(), self.aux.data_ptr(), self.goal.data_ptr(),
                                           self.obs.data_ptr(), self.achieved.data_ptr(), self.packed.data_ptr(), self.final_packed.data_ptr(), self.status.data_ptr())
-        _native.check(self._L.grx_fetch_commit_rows(ctypes.byref(a), self._stream()))
+        if self._fused:
+            self._post_step(a, rows)
+        else:
+            _native.check(self._L.grx_fetch_commit_rows(ctypes.byref(a), self._stream()))
         self._elapsed[idx] = 0
         self._needs_reset[idx] = False
 
@@ -398,7 +420,7 @@ class FetchVecEnv(GoalVecEnv):
             self._seed_worlds(seeds)
         with torch.cuda.device(self.device):
             self._reset_worlds(np.arange(self.num_envs))
-        self._has_reset = True
+        self._has_reset, self.step_reset_list = True, None
         return self._obs_dict(), {}
 
     # ------------------------------------------------------------------ step (robot_env.py:114-152)
@@ -424,12 +446,17 @@ class FetchVecEnv(GoalVecEnv):
                     before.record(torch.cuda.current_stream(self.device))
                 elif len(will):
                     ahead = (will, self._launch_reset_ahead(will))
+            self.step_reset_list = None
+            if self._order_pending:      # a step that raised between its launch and its post-step launch left its order unsorted: sort it now, from the costs that launch wrote
+                self._post_step()
+            self._defer_order = self._fused and self.autoreset_mode == "same_step" and not len(pending)
             if len(pending):
                 self.mask.fill_(1)
                 self.mask.index_fill_(0, self._stage_idx(pending), 0)      # (pinned staging + index_fill_: nothing here waits for the running kernel)
                 self._launch_step(self._bufs_masked)
             else:
                 self._launch_step(self._bufs)
+            self._defer_order = False
             if before is not None:
                 ahead = (will, self._launch_reset_ahead(will, after=before))      # queued behind the step launch: its workgroups take the slots the first finished worlds free
             stepped = ~self._needs_reset if len(pending) else np.ones(self.num_envs, bool)
@@ -444,27 +471,35 @@ class FetchVecEnv(GoalVecEnv):
                 self.reward.index_fill_(0, tp, 0.0)
                 self.packed[:, -2].index_fill_(0, tp, 0.0)
             if self.autoreset_mode == "same_step" and truncated.any():
-                done = np.nonzero(truncated)[0]
+                done, fo = np.nonzero(truncated)[0], None
                 # the reset parks the terminal packed rows of these worlds in final_packed (info["final_obs"], the last transition for HER) and
                 # leaves reward / success at the finished episode's values (keep_outcome)
                 if ahead is not None:
                     if not np.array_equal(ahead[0], done):
+                        if self._order_pending:      # nothing will be committed: the ordering half alone, so that the flag does not outlive this step
+                            self._post_step()
                         raise RuntimeError("overlapped reset: the worlds reset ahead of the step are not the ones it truncated")
                     staged = ahead[1][0]
                     if self.output != "torch":
                         info["final_obs"] = self._obs_dict(rows=done)
-                    self._commit_ahead(ahead[1], done)
+                    elif self._fused:      # a fresh buffer every step (callers keep final_obs): the commit writes the terminal rows there, no gather
+                        fo = torch.empty(len(done), self.obs_dim + 8, dtype=torch.float32, device=self.device)
+                    self._commit_ahead(ahead[1], done, rows=fo)
                 else:
                     staged = self._stage_reset(done)
                     if self.output != "torch":
                         info["final_obs"] = self._obs_dict(rows=done)
                     self._launch_reset(staged, done, keep_outcome=True)
+                self.step_reset_list = (staged[1], len(done))
                 if self.output == "torch":
-                    fo = self.final_packed[staged[1]]      # (int32 device indices: one gather kernel)
+                    if fo is None:
+                        fo = self.final_packed[staged[1]]      # (int32 device indices: one gather kernel)
                     info["final_obs"] = {"observation": fo[:, : self.obs_dim], "achieved_goal": fo[:, self.obs_dim: self.obs_dim + 3],
                                          "desired_goal": fo[:, self.obs_dim + 3: self.obs_dim + 6]}
             elif self.autoreset_mode == "next_step":
                 self._needs_reset |= truncated
+            if self._order_pending:      # no overlapped reset to commit in this step: the ordering half alone
+                self._post_step()
         obs = self._obs_dict()
         if self.output == "torch":
             info["is_success"] = self.success

@@ -14,6 +14,7 @@ probability k / (k + 1)), recomputes reward and success with the device function
 into a device ring buffer.  Nothing leaves HBM; the learner reads ``replay.rows``.
 """
 import ctypes
+import os
 from typing import Optional
 
 import numpy as np
@@ -77,6 +78,9 @@ class HerReplay:
         self.t = 0                                 # absolute index of the newest row
         self._seed, self._calls = int(seed), 0     # counter-based index stream (grx_her_sample): see reseed()
         self._L = _native.lib()
+        # one kernel per append (grx_her_append) and one per relabel (grx_her_draw_relabel); GRX_FETCH_FUSED_TAIL=0: the copies, the mark kernel and the sample + relabel pair
+        self._fused = os.environ.get("GRX_FETCH_FUSED_TAIL", "1") != "0"
+        self._last_list = None
         # reset masks reach the device through pinned buffers: a copy from pageable memory would make the host wait for the step kernel (core.PinnedStager)
         self._mask_pin = [dict(buf=torch.empty(self.N, dtype=torch.bool, pin_memory=True), event=None) for _ in range(4)]
         self._mask_next, self._mask_dev = 0, torch.zeros(self.N, dtype=torch.bool, device=self.device)
@@ -99,6 +103,8 @@ class HerReplay:
             raise RuntimeError("episode buffer is full: call begin_episode()")
         self.t += 1
         r = self.t % self.R
+        if self._fused:
+            return self._append_fused(r, actions, packed_rows, reset_mask, final_rows)
         self.actions[r].copy_(actions)
         self.episode[r].copy_(packed_rows)
         if reset_mask is not None:     # bool [N]: numpy / CPU tensor (what the envs return) or a device tensor
@@ -126,6 +132,54 @@ class HerReplay:
         elif self._final_rows is not None:
             self._just_ended = np.zeros(self.N, bool)
 
+    def _upload_mask(self, host):
+        slot = self._mask_pin[self._mask_next]
+        self._mask_next = (self._mask_next + 1) % len(self._mask_pin)
+        if slot["event"] is not None:
+            slot["event"].synchronize()
+        slot["buf"].numpy()[:] = host
+        self._mask_dev.copy_(slot["buf"], non_blocking=True)
+        slot["event"] = torch.cuda.Event()
+        slot["event"].record(torch.cuda.current_stream(self.device))
+        return self._mask_dev
+
+    def _append_fused(self, r, actions, packed_rows, reset_mask, final_rows):
+        """append() as ONE kernel (grx_her_append): both row copies and the episode marks of the reset worlds.  Those are read from the index list the environment left on the
+        device (`env.step_reset_list`: int32 tensor + host count, e.g. FetchVecEnv) when its count agrees with reset_mask; otherwise from the mask (uploaded if it is a host array)."""
+        dev_rows = lambda x, shape: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(device=self.device, dtype=torch.float32).contiguous().view(shape)
+        acts, rows = dev_rows(actions, (self.N, self.act_dim)), dev_rows(packed_rows, (self.N, self.W))
+        a = _native.HerAppendArgsStruct()
+        a.packed, a.action, a.row_dst, a.act_dst = rows.data_ptr(), acts.data_ptr(), self.episode[r].data_ptr(), self.actions[r].data_ptr()
+        a.n_row, a.n_act, a.n_worlds, a.t, a.W = self.N * self.W, self.N * self.act_dim, self.N, self.t, self.W
+        a.start = self.episode_start.data_ptr()
+        keep = None      # (a device mask made here stays alive until the launch is enqueued)
+        if reset_mask is not None:
+            host = (reset_mask.cpu().numpy() if isinstance(reset_mask, torch.Tensor) else np.asarray(reset_mask)).astype(bool)
+            self._start_host[host] = self.t
+            if final_rows is not None:
+                assert tuple(final_rows.shape) == (self.N, self.W) and final_rows.is_contiguous()
+                self._final_rows = final_rows
+            track = self._final_rows is not None
+            self._just_ended = host if track else self._just_ended
+            if track:
+                a.prev_start, a.term_t = self.prev_start.data_ptr(), self.term_t.data_ptr()
+            count, lst = int(host.sum()), getattr(self.env, "step_reset_list", None)
+            if lst is self._last_list:      # the environment publishes a fresh tuple with every step: the one an earlier append consumed is stale
+                lst = None
+            self._last_list = lst
+            if count == 0:
+                pass
+            elif lst is not None and lst[1] == count and lst[0].dtype == torch.int32 and lst[0].device == self.device:
+                a.list, a.count = lst[0].data_ptr(), count
+            elif isinstance(reset_mask, torch.Tensor) and reset_mask.device == self.device:
+                keep = reset_mask if reset_mask.dtype in (torch.bool, torch.uint8) else reset_mask.bool()
+                a.mask = keep.data_ptr()
+            else:
+                a.mask = self._upload_mask(host).data_ptr()
+        elif self._final_rows is not None:
+            self._just_ended = np.zeros(self.N, bool)
+        _native.check(self._L.grx_her_append(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
     def set_episode_start(self, starts):
         """absolute row at which every world's current episode began (e.g. negative values for episodes that were already under way at row 0)"""
         self._start_host[:] = np.asarray(starts, dtype=np.int64)
@@ -136,13 +190,18 @@ class HerReplay:
         """restart the index stream: the same (seed, number of sample_indices calls since) reproduces the same draws"""
         self._seed, self._calls = int(seed), 0
 
+    def _can_sample(self) -> bool:
+        """host mirror: does any world have a transition in the ring (of its current episode, or of the one that ended in this step when terminal rows are kept)"""
+        track = self._final_rows is not None
+        return bool(((np.maximum(self._start_host, max(self.t - self.T, 0)) < self.t) | (self._just_ended if track else False)).any())
+
     def sample_indices(self, batch: int, k_future: int = 4):
         """(t, world, t_goal): a uniform world, a uniform transition of that world's current episode among the rows still in the ring; with
         probability k / (k + 1) the goal achieved at a uniformly drawn LATER row of the same episode (the "future" strategy of Andrychowicz et al.
         2017), else -1 = keep the episode's goal.  Worlds whose episode has no transition yet (just reset) are not drawn.  One kernel
         (grx_her_sample) with a counter-based generator; None when nothing can be sampled."""
         track = self._final_rows is not None
-        if not ((np.maximum(self._start_host, max(self.t - self.T, 0)) < self.t) | (self._just_ended if track else False)).any():
+        if not self._can_sample():
             return None                                                                   # every world has just been reset: nothing to sample
         t, w, tg = (torch.empty(batch, dtype=torch.int32, device=self.device) for _ in range(3))
         _native.check(self._L.grx_her_sample_final(self.episode_start.data_ptr(), self.prev_start.data_ptr() if track else None, self.term_t.data_ptr() if track else None,
@@ -151,16 +210,20 @@ class HerReplay:
         self._calls += 1
         return t, w, tg
 
-    def relabel_into(self, out: torch.Tensor, t: torch.Tensor, w: torch.Tensor, t_goal: torch.Tensor):
-        """the kernel alone: out[b] <- relabelled transition (t[b], w[b], t_goal[b]); int32 index tensors on the device"""
+    def _her_args(self, out: torch.Tensor):
         a = _native.HerArgsStruct()
-        a.rows, a.acts = self.episode.data_ptr(), self.actions.data_ptr()
+        a.rows, a.acts, a.out = self.episode.data_ptr(), self.actions.data_ptr(), out.data_ptr()
         a.T, a.N, a.W, a.obs_dim, a.goal_dim, a.act_dim = self.T, self.N, self.W, self.obs_dim, self.goal_dim, self.act_dim   # ring of T + 1 rows
-        a.t_idx, a.w_idx, a.t_goal, a.out = t.data_ptr(), w.data_ptr(), t_goal.data_ptr(), out.data_ptr()
         if self._final_rows is not None:
             a.term_rows, a.term_t = self._final_rows.data_ptr(), self.term_t.data_ptr()
         for k, v in self.spec.items():
             setattr(a, k, v)
+        return a
+
+    def relabel_into(self, out: torch.Tensor, t: torch.Tensor, w: torch.Tensor, t_goal: torch.Tensor):
+        """the kernel alone: out[b] <- relabelled transition (t[b], w[b], t_goal[b]); int32 index tensors on the device"""
+        a = self._her_args(out)
+        a.t_idx, a.w_idx, a.t_goal = t.data_ptr(), w.data_ptr(), t_goal.data_ptr()
         assert out.is_contiguous() and tuple(out.shape) == (len(t), self.OW) and t.dtype == w.dtype == t_goal.dtype == torch.int32
         _native.check(self._L.grx_her_relabel(ctypes.byref(a), len(t), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return out
@@ -171,12 +234,20 @@ class HerReplay:
             raise ValueError("batch larger than the replay capacity")
         if self.head + batch > self.capacity:
             self.head = 0                                    # keep every batch contiguous (a ring of whole batches)
-        idx = self.sample_indices(batch, k_future)
-        if idx is None:
-            return self.rows[self.head: self.head]
-        t, w, tg = idx
         view = self.rows[self.head: self.head + batch]
-        self.relabel_into(view, t, w, tg)
+        if self._fused:      # the draws of sample_indices and the rows of relabel_into in one kernel: no index tensors
+            if not self._can_sample():
+                return self.rows[self.head: self.head]
+            track = self._final_rows is not None
+            _native.check(self._L.grx_her_draw_relabel(ctypes.byref(self._her_args(view)), self.episode_start.data_ptr(), self.prev_start.data_ptr() if track else None,
+                                                       self.t, int(k_future), self._seed, self._calls, batch, None,
+                                                       ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            self._calls += 1
+        else:
+            idx = self.sample_indices(batch, k_future)
+            if idx is None:
+                return self.rows[self.head: self.head]
+            self.relabel_into(view, *idx)
         self.head += batch
         self.size = min(self.capacity, max(self.size, self.head))
         return view

@@ -412,12 +412,33 @@ int grx_her_sample_final(const int* episode_start, const int* prev_start, const 
 /* Episode bookkeeping of the worlds reset in the step that produced row t (reset_mask[w] != 0): prev_start[w] <- episode_start[w], term_t[w] <- t,
  * episode_start[w] <- t.  One kernel.  prev_start / term_t may be NULL (then only episode_start is updated). */
 int grx_her_mark_resets(const unsigned char* reset_mask, int n_worlds, int t, int* episode_start, int* prev_start, int* term_t, void* stream);
-/* grx_her_sample_final + grx_her_relabel for a caller that keeps NO host mirror of the episode boundaries (the replay of the env-level ABI, grx_replay.h): two kernels.
+/* grx_her_sample_final + grx_her_relabel for a caller that keeps NO host mirror of the episode boundaries (the replay of the env-level ABI, grx_replay.h): ONE kernel since grx_her_draw_relabel (below), which this call issues; scratch is unused.
  * The draws are grx_her_sample_final's (prev_start / args->term_t / args->term_rows all given or all NULL) into scratch [3 batch] (args->t_idx / w_idx / t_goal are ignored),
  * the rows grx_her_relabel's.  Whether any world has a transition is decided on the device: a sample whose probe loop has visited all n worlds without finding one knows
  * that none exists; then valid[0] = 0 and out is zero-filled, else valid[0] = batch.  t_now = 0 (nothing appended yet) is allowed and samples nothing. */
 int grx_her_sample_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call, int64_t batch,
                            int* scratch, int* valid, void* stream);
+/* The draws and the rows in ONE kernel: every workgroup makes the draws of the rows it writes (the generator is counter-based, keyed by the sample index) and passes them
+ * through LDS; no index array exists.  The rows are bit for bit those of grx_her_sample_final + grx_her_relabel.  valid != NULL: the device-side decision of
+ * grx_her_sample_relabel (which is this launch; its scratch argument is no longer used).  valid == NULL: the caller knows that a world with a transition exists (HerReplay's
+ * host mirror of the episode boundaries), t_now > 0.  args->t_idx / w_idx / t_goal are ignored. */
+int grx_her_draw_relabel(const grx_her_args* args, const int* episode_start, const int* prev_start, int t_now, int k_future, uint64_t seed, uint64_t call, int64_t batch,
+                         int* valid, void* stream);
+/* HerReplay.append in ONE kernel: ring row <- the packed rows and the actions of this step (16-byte accesses where the bases allow), and grx_her_mark_resets' bookkeeping
+ * (prev_start[w] <- start[w], term_t[w] <- t, start[w] <- t) for the worlds reset in this step.  Those come EITHER as a device index list -- `count` entries, or *count_dev
+ * where the length lives on the device; entries outside [0, n_worlds) are skipped -- OR as a device mask [n_worlds]; neither: no world was reset.  With a list, final_rows
+ * [count, W] (terminal rows in list order) may be scattered to term_rows [n_worlds, W].  A world must not be listed twice.  All pointers are device pointers. */
+typedef struct grx_her_append_args {
+  const float *packed, *action;        /* the rows of this step: [n_worlds, W], [n_worlds, act_dim] */
+  float *row_dst, *act_dst;            /* ring row (t % (T + 1)) of grx_her_args.rows / .acts */
+  long long n_row, n_act;              /* words: n_worlds W, n_worlds act_dim */
+  const int* list; const int* count_dev;
+  const unsigned char* mask;
+  int count, n_worlds, t, W;           /* t: absolute index of the row being appended */
+  int *start, *prev_start, *term_t;    /* prev_start / term_t NULL: only episode_start is kept */
+  const float* final_rows; float* term_rows;
+} grx_her_append_args;
+int grx_her_append(const grx_her_append_args* args, void* stream);
 
 /* Episode reset of a COMPACTED list of maze worlds (maze/point_maze.py:377-390 / ant_maze_v5.py reset_model, maze_v4.py:299-358: qpos = init_qpos with
  * xy <- the drawn reset position, qvel = 0, new goal, observation of the reset state): one kernel writes state, goal, obs / achieved / success and the
@@ -498,6 +519,12 @@ typedef struct grx_fetch_commit_args {
   float *qpos, *qvel, *qacc_ws, *mocap, *aux, *goal, *obs, *achieved, *packed, *final_packed; int* status;
 } grx_fetch_commit_args;
 int grx_fetch_commit_rows(const grx_fetch_commit_args* args, void* stream);
+/* Everything that follows a Fetch step launch, in ONE launch: grx_order_by_cost_slots (workgroups 0-7, one XCD slice each; the same moving average, the same unique
+ * (cost, world) keys, hence the same `order`) and grx_fetch_commit_rows (the other workgroups), which share no data.  final_rows (or NULL): [commit->k, obs_dim + 8], row j
+ * <- the terminal packed row of world commit->idx[j] -- what a gather of final_packed by idx would return.  order == NULL: no ordering (cost / ema are not read);
+ * commit == NULL or commit->k == 0: no commit; both: no launch.  ema may be NULL as in grx_order_by_cost. */
+int grx_fetch_post_step(const int* cost, float* ema, float alpha, int n_worlds, int slots_per_xcd, int* order, const grx_fetch_commit_args* commit, float* final_rows,
+                        void* stream);
 
 /* Commit of an overlapped Adroit reset (envs/adroit.py; hammer / door / relocate, whose reset_model draws are made on the device).  The Adroit tasks never terminate
  * (adroit_hammer.py:291-329 returns terminated = False), so the worlds a step truncates are known before it is launched: the draws (grx_adroit_sample_resets_device writing the

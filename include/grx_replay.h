@@ -38,7 +38,7 @@ typedef struct grx_replay_config {
   int keep_final;      /* same-step autoreset only: keep the finished episode's last transition sampleable in the step that ends it, its next observation being the terminal
                         * row (HerReplay.append(final_rows=...)); ignored in the other autoreset modes */
   int64_t capacity;    /* rows of the replay ring, >= 1 */
-  int64_t max_batch;   /* the largest batch relabel will be asked for (index scratch is allocated once, at create); <= 0: capacity */
+  int64_t max_batch;   /* the largest batch relabel will be asked for (relabel refuses larger ones); <= 0: capacity */
   uint64_t seed;       /* index stream, as HerReplay(seed=...) */
 } grx_replay_config;
 
