@@ -85,6 +85,13 @@ class MazeResetArgsStruct(ctypes.Structure):
         (n, ctypes.c_void_p) for n in ("qpos", "qvel", "qacc_ws", "goal", "obs", "achieved", "reward", "success", "packed")]
 
 
+class MazeEpisodeArgsStruct(ctypes.Structure):      # include/grx_capi.h, grx_maze_episode_args
+    _fields_ = [(n, ctypes.c_void_p) for n in ("elapsed", "needs_reset", "success", "achieved", "goal", "status", "packed", "rng", "goal_xy")] + [
+        (n, ctypes.c_int) for n in ("n_goal", "mode", "limit", "continuing_task", "reset_target", "packed_dim")] + [
+        (n, ctypes.c_double) for n in ("noise_range", "scaling", "goal_radius")] + [
+        (n, ctypes.c_void_p) for n in ("terminated", "truncated", "mask", "step_success", "desired", "reset_count", "reset_idx", "n_final", "final_idx", "final_rows")]
+
+
 class HandCommitArgsStruct(ctypes.Structure):
     _fields_ = [("idx", ctypes.c_void_p), ("k", ctypes.c_int)] + [(n, ctypes.c_int) for n in ("nq", "nv", "obs_dim", "goal_dim")] + [
         (n, ctypes.c_void_p) for n in ("s_qpos", "s_qvel", "s_qacc_ws", "s_obs", "s_achieved", "s_palm", "s_goal", "s_packed", "s_status",
@@ -151,6 +158,7 @@ def lib():
         L.grx_order_by_cost.argtypes = [vp, vp, ctypes.c_float, ci, vp, vp]
         L.grx_order_by_cost_slots.argtypes = [vp, vp, ctypes.c_float, ci, ci, vp, vp]
         L.grx_maze_reset_rows.argtypes = [vp, ci, vp]
+        L.grx_maze_episode_end.argtypes = [vp, ci, vp]
         L.grx_hand_commit_rows.argtypes = [vp, vp]
         L.grx_fetch_commit_rows.argtypes = [vp, vp]
         L.grx_adroit_commit_rows.argtypes = [vp, vp]
