@@ -1252,7 +1252,7 @@ GRX_DEV void grx_her_outcome(const GrxHerArgs& a, const float* ag, const float* 
     *reward = grx_fetch_reward(d, a.p0, a.sparse); *success = (d < a.p0) ? 1.0f : 0.0f;
   }
 }
-// word e of output row b (the whole arithmetic of the relabel: both kernels below write exactly this value)
+// word e of output row b (the whole arithmetic of the relabel: grx_her_relabel_kernel and grx_her_draw_relabel_kernel write exactly this value)
 // (ti, w, tg): the sample's draws -- absolute row, world, goal row
 GRX_DEV float grx_her_word_at(const GrxHerArgs& a, int ti, int w, int tg, int e) {
   const int od = a.obs_dim, gd = a.goal_dim, ad = a.act_dim, OW = 2 * od + 3 * gd + ad + 2;
@@ -1280,17 +1280,6 @@ grx_her_relabel_kernel(GrxHerArgs a, long long B) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < B * OW; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / OW;
     a.out[i] = grx_her_word(a, b, (int)(i - b * OW));
-  }
-}
-// the same rows behind a device-side decision (grx_her_sample_relabel): *valid == 0 -- the sample kernel found no world with a transition, its indices mean nothing --
-// zero-fills the slot and reads no index
-extern "C" __global__ void __launch_bounds__(256)
-grx_her_relabel_valid_kernel(GrxHerArgs a, long long B, const int* __restrict__ valid) {
-  const int OW = 2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2;
-  const bool ok = *valid != 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < B * OW; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / OW;
-    a.out[i] = ok ? grx_her_word(a, b, (int)(i - b * OW)) : 0.0f;
   }
 }
 
@@ -1801,22 +1790,10 @@ grx_her_sample_kernel(const int* __restrict__ start, const int* __restrict__ pre
     t_idx[b] = t; w_idx[b] = w; t_goal[b] = tg;
   }
 }
-// the same draws for a caller that keeps no host mirror of the episode boundaries: sample 0 also reports whether anything could be sampled (valid[0] = B or 0)
-extern "C" __global__ void __launch_bounds__(256)
-grx_her_sample_valid_kernel(const int* __restrict__ start, const int* __restrict__ prev_start, const int* __restrict__ term_t, int N, int t_now, int T, int k_future,
-                            unsigned long long seed, unsigned long long call, long long B, int* __restrict__ t_idx, int* __restrict__ w_idx, int* __restrict__ t_goal,
-                            int* __restrict__ valid) {
-  for (long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (long long)gridDim.x * blockDim.x) {
-    int t, w, tg;
-    const bool found = grx_her_draw(start, prev_start, term_t, N, t_now, T, k_future, seed, call, b, &t, &w, &tg);
-    t_idx[b] = t; w_idx[b] = w; t_goal[b] = tg;
-    if (b == 0) *valid = found ? (int)B : 0;
-  }
-}
 // The draws and the rows in ONE launch (grx_her_draw_relabel): a workgroup takes GRX_HER_CHUNK consecutive samples at a time, its first threads make their draws
-// (grx_her_draw: the very values the sample kernels write) and hand them over in LDS, then all 256 threads write the chunk's output words (grx_her_word_at: the relabel
-// kernels' arithmetic).  No index array goes through HBM.  valid (or NULL: the caller knows that a world with a transition exists): sample 0 reports valid[0] = B or 0, and
-// a sample that found no world zero-fills its row -- then every sample found none (grx_her_draw), which is what the relabel kernel reads from *valid.
+// (grx_her_draw: the very values the sample kernel writes) and hand them over in LDS, then all 256 threads write the chunk's output words (grx_her_word_at: the relabel
+// kernel's arithmetic).  No index array goes through HBM.  valid (or NULL: the caller knows that a world with a transition exists): sample 0 reports valid[0] = B or 0, and
+// a sample that found no world zero-fills its row -- then every sample found none (grx_her_draw): the whole slot is zero.
 #define GRX_HER_CHUNK 32
 extern "C" __global__ void __launch_bounds__(256)
 grx_her_draw_relabel_kernel(GrxHerArgs a, const int* __restrict__ start, const int* __restrict__ prev_start, int t_now, int k_future, unsigned long long seed,
