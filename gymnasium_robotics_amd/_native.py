@@ -79,6 +79,12 @@ class HerAppendArgsStruct(ctypes.Structure):      # include/grx_capi.h, grx_her_
         (n, ctypes.c_void_p) for n in ("start", "prev_start", "term_t", "final_rows", "term_rows")]
 
 
+class HerArchiveArgsStruct(ctypes.Structure):      # include/grx_capi.h, grx_her_archive_args
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rows", "acts", "start", "list", "count_dev")] + [
+        (n, ctypes.c_int) for n in ("count", "n_worlds", "T", "W", "act_dim", "t_prev", "final_compact")] + [
+        (n, ctypes.c_void_p) for n in ("final_rows", "step_action", "ep_rows", "ep_acts", "ep_meta", "ep_count")] + [("episodes", ctypes.c_longlong)]
+
+
 class MazeResetArgsStruct(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("idx", "stage", "qpos0")] + [(n, ctypes.c_int) for n in ("nq", "nv", "obs_dim", "obs_skip")] + [
         ("goal_radius", ctypes.c_double), ("keep_outcome", ctypes.c_int)] + [
@@ -143,6 +149,8 @@ def lib():
         L.grx_her_sample_relabel.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp, vp, vp]
         L.grx_her_draw_relabel.argtypes = [vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp, vp]
         L.grx_her_append.argtypes = [vp, vp]
+        L.grx_her_archive.argtypes = [vp, vp]
+        L.grx_her_episode_sample.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, vp, vp, vp]
         L.grx_fetch_post_step.argtypes = [vp, vp, ctypes.c_float, ci, ci, vp, vp, vp, vp]
         L.grx_kitchen_step.argtypes = [vp, vp, vp, ci, ci, vp]
         L.grx_sample_uniform_rows.argtypes = [vp, vp, ci, ci, vp]
@@ -201,7 +209,7 @@ def check(rc: int):
 
 EXPORTED_SYMBOLS = [
     "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_dim",
-    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
+    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
 ]
 
 

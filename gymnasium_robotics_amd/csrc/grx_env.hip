@@ -30,6 +30,7 @@
 #include "grx_capi.h"
 #include "grx_env.h"
 #include "grx_replay.h"
+#include "grx_episodes.h"
 #include "grx_copy.h"
 
 namespace {
@@ -900,3 +901,4 @@ extern "C" int grx_env_set_state(grx_env* e, const void* host, size_t bytes) {
 }
 
 #include "grx_env_replay.inc"
+#include "grx_env_episodes.inc"

@@ -18,9 +18,12 @@ struct grx_replay {
   bool begun = false;
   uint64_t epoch = 0, last_step = 0;      // the handle's reset / set_state count at begin; its step count at the last append (or at begin)
   grx_her_args ha{};
+  grx_episodes* episodes = nullptr;      // the store of finished episodes attached to this replay (include/grx_episodes.h, grx_env_episodes.inc), or none
 };
 
 namespace {
+
+int episodes_archive(grx_replay* r, void* stream);      // grx_env_episodes.inc
 
 // HerReplay.begin_episode + set_episode_start(-elapsed): row 0 <- the packed rows; episode_start from the device counters (elapsed NULL: the host uploaded it already)
 __global__ void __launch_bounds__(256) grx_replay_begin_kernel(const float* __restrict__ packed, float* __restrict__ row0, long long n_row, const long long* __restrict__ elapsed, int n,
@@ -106,6 +109,7 @@ extern "C" int grx_replay_create(grx_env* e, const grx_replay_config* cfg, grx_r
 
 extern "C" int grx_replay_destroy(grx_replay* r) {
   if (!r) return fail(GRX_ENV_EINVAL, "grx_replay_destroy: NULL replay");
+  if (r->episodes) return fail(GRX_ENV_EINVAL, "grx_replay_destroy: an episode store is attached to the replay: grx_episodes_destroy first");
   DeviceGuard g(r->e->device);
   (void)hipDeviceSynchronize();
   r->e->replay = nullptr;
@@ -155,6 +159,7 @@ extern "C" int grx_replay_append(grx_replay* r, void* stream) {
   if (e->steps != r->last_step + 1) return fail(GRX_ENV_EINVAL, "grx_replay_append: " + std::to_string(e->steps - r->last_step) + " steps since the last append: every step is appended");
   if (r->t == INT32_MAX - 1) return fail(GRX_ENV_EINVAL, "grx_replay_append: row counter exhausted: call grx_replay_begin");
   DeviceGuard g(e->device);
+  if (r->episodes) ENV_TRY(episodes_archive(r, stream));      // before this step's row overwrites the oldest ring row and before its worlds are re-marked
   const int t = r->t + 1, row = t % r->R;
   grx_her_append_args a;      // HerReplay.append in one launch (grx_capi.h grx_her_append): the two row copies, the marks of the listed worlds, the terminal-row scatter
   std::memset(&a, 0, sizeof a);

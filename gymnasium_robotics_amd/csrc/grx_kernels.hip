@@ -1922,6 +1922,169 @@ extern "C" int grx_her_append(const grx_her_append_args* args, void* stream) {
   return 0;
 }
 
+// The episode store (include/grx_capi.h, grx_her_archive): the finished episode of list position j moves from the ring into slot (ep_count + j) % E, one workgroup per
+// list position at a time.  Every workgroup reads the old ep_count; the one-thread kernel behind it on the same stream advances it.  Plain word copies: neither the slot
+// bases nor the ring rows are 16-byte aligned for odd W.  The list order assigns the slots: no atomics.
+static __device__ __forceinline__ int grx_her_list_count(const int* count_dev, int count, int n_worlds) {
+  const int k = count_dev ? *count_dev : count;
+  return k < 0 ? 0 : (k > n_worlds ? n_worlds : k);
+}
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_archive_kernel(grx_her_archive_args a) {
+  const int k = grx_her_list_count(a.count_dev, a.count, a.n_worlds);
+  const int T = a.T, R = T + 1, W = a.W, ad = a.act_dim, N = a.n_worlds, s = a.final_rows ? 1 : 0, x = threadIdx.x;
+  const long long E = a.episodes, before = *a.ep_count;
+  for (int j = blockIdx.x; j < k; j += gridDim.x) {
+    const int w = a.list[j];
+    const size_t slot = (size_t)((unsigned long long)(before + j) % (unsigned long long)E);
+    int* meta = a.ep_meta + slot * 4;
+    if ((unsigned)w >= (unsigned)N) {      // not a world: the slot is taken and left empty
+      if (x < 4) meta[x] = x == 1 ? w : 0;
+      continue;
+    }
+    int a0 = a.start[w];
+    if (a0 < a.t_prev - T + s) a0 = a.t_prev - T + s;
+    if (a0 < 0) a0 = 0;
+    int L = a.t_prev - a0 + s;
+    if (L < 0) L = 0;      // (a mark beyond the newest row: nothing of that episode is in the ring)
+    if (x < 4) meta[x] = x == 0 ? L : (x == 1 ? w : (x == 2 ? a0 : 0));
+    if (L == 0) continue;
+    const int n_ring = a.t_prev - a0 + 1;      // rows of the episode that the ring holds: 1 .. T + 1 - s
+    float* er = a.ep_rows + slot * (size_t)R * W;
+    float* ea = a.ep_acts + slot * (size_t)R * ad;
+    for (int i = x; i < n_ring * W; i += 256) {
+      const int r = i / W, c = i - r * W;
+      er[i] = a.rows[((size_t)((a0 + r) % R) * N + w) * W + c];
+    }
+    for (int i = x; i < n_ring * ad; i += 256) {
+      const int r = i / ad, c = i - r * ad;
+      ea[i] = r == 0 ? 0.0f : a.acts[((size_t)((a0 + r) % R) * N + w) * ad + c];
+    }
+    if (s) {      // the terminal row and the action that led to it: neither is in the ring yet
+      const float* fr = a.final_rows + (size_t)(a.final_compact ? j : w) * W;
+      for (int c = x; c < W; c += 256) er[(size_t)L * W + c] = fr[c];
+      for (int c = x; c < ad; c += 256) ea[(size_t)L * ad + c] = a.step_action[(size_t)w * ad + c];
+    }
+  }
+}
+extern "C" __global__ void grx_her_archive_count_kernel(const int* count_dev, int count, int n_worlds, long long* ep_count) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ep_count += grx_her_list_count(count_dev, count, n_worlds);
+}
+extern "C" int grx_her_archive(const grx_her_archive_args* args, void* stream) {
+  if (!args) return fail("grx_her_archive: null argument");
+  const grx_her_archive_args& a = *args;
+  if (!a.rows || !a.acts || !a.start || !a.ep_rows || !a.ep_acts || !a.ep_meta || !a.ep_count) return fail("grx_her_archive: null buffer");
+  if (a.n_worlds <= 0 || a.T <= 0 || a.W <= 0 || a.act_dim <= 0 || a.t_prev < 0) return fail("grx_her_archive: bad dimensions");
+  if (a.episodes < a.n_worlds || a.episodes > 0x7FFFFFFFll) return fail("grx_her_archive: the store needs n_worlds <= episodes < 2^31 slots (one launch never writes a slot twice)");
+  if ((a.final_rows == nullptr) != (a.step_action == nullptr)) return fail("grx_her_archive: final_rows and step_action go together");
+  if (!a.list) {
+    if (a.count_dev || a.count != 0) return fail("grx_her_archive: a count without a list");
+    return 0;
+  }
+  if (!a.count_dev && a.count <= 0) return 0;      // host-known: no episode ended in this step
+  int blocks = a.count_dev ? a.n_worlds : (a.count < a.n_worlds ? a.count : a.n_worlds);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(grx_her_archive_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(grx_her_archive_count_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, a.count_dev, a.count, a.n_worlds, a.ep_count);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// Sampling from the episode store (include/grx_capi.h, grx_her_episode_sample): the structure of grx_her_draw_relabel_kernel -- 32 samples per chunk, the chunk's first
+// threads draw (slot, transition, goal row) and hand them over in LDS, all 256 threads write the chunk's words.  The stream is grx_her_draw's with a domain constant.
+#define GRX_EPISODES_DOMAIN 0x455049534F444553ull
+static __device__ __forceinline__ bool grx_her_episode_draw(const int* __restrict__ ep_meta, long long F, int T, int strategy, int k_future, unsigned long long seed,
+                                                            unsigned long long call, long long b, int* e_out, int* t_out, int* g_out) {
+  unsigned long long s = ((seed * 0xD1342543DE82EF95ull + call * 0x2545F4914F6CDD1Dull) ^ GRX_EPISODES_DOMAIN) + (unsigned long long)b;
+  (void)grx_splitmix(s);
+  *e_out = 0; *t_out = 0; *g_out = -1;
+  if (F <= 0) return false;
+  long long e = 0;
+  int L = 0;
+  for (int attempt = 0; attempt < 64 && L <= 0; attempt++) {      // uniform over the filled slots
+    e = (long long)(((grx_splitmix(s) >> 32) * (unsigned long long)F) >> 32);
+    L = ep_meta[4 * e];
+  }
+  for (long long probe = 0; probe < F && L <= 0; probe++) { e = e + 1 < F ? e + 1 : 0; L = ep_meta[4 * e]; }
+  if (L <= 0) return false;
+  if (L > T) L = T;      // (a store holds 0 <= len <= T: no row outside the slot is read whatever the word says)
+  const unsigned long long r = grx_splitmix(s), r2 = grx_splitmix(s);
+  const float u0 = (float)(r >> 40) * (1.0f / 16777216.0f), u1 = (float)((r >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f);
+  int t = (int)(u0 * (float)L);
+  if (t > L - 1) t = L - 1;
+  int g;
+  if (strategy == 1) g = L;
+  else if (strategy == 2) { g = (int)(u1 * (float)(L + 1)); if (g > L) g = L; }
+  else { g = t + 1 + (int)(u1 * (float)(L - t)); if (g > L) g = L; }
+  const bool keep = (r2 >> 40) * (unsigned long long)((long long)k_future + 1) >= ((unsigned long long)k_future << 24);      // integers: exact
+  *e_out = (int)e; *t_out = t; *g_out = keep ? -1 : g;
+  return true;
+}
+// word i of the row of the draw (slot e, transition t, goal row g; g < 0: the episode's own goal)
+GRX_DEV float grx_her_episode_word(const GrxHerArgs& a, const float* __restrict__ ep_rows, const float* __restrict__ ep_acts, int e, int t, int g, int i) {
+  const int od = a.obs_dim, gd = a.goal_dim, ad = a.act_dim, OW = 2 * od + 3 * gd + ad + 2, R = a.T + 1;
+  const float* base = ep_rows + (size_t)e * R * a.W;
+  const float *r0 = base + (size_t)t * a.W, *r1 = r0 + a.W;
+  const float* goal = g < 0 ? r0 + od + gd : base + (size_t)g * a.W + od;
+  float v;
+  if (i < od + gd) v = r0[i];
+  else if (i < od + 2 * gd) v = goal[i - od - gd];
+  else if (i < od + 2 * gd + ad) v = ep_acts[((size_t)e * R + t + 1) * ad + (i - od - 2 * gd)];
+  else if (i == od + 2 * gd + ad || i == OW - 1) {
+    float ag[16], gg[16], rw, sc;
+    for (int k = 0; k < gd; k++) { ag[k] = r1[od + k]; gg[k] = goal[k]; }
+    grx_her_outcome(a, ag, gg, &rw, &sc);
+    v = (i == OW - 1) ? sc : rw;
+  } else v = r1[i - (od + 2 * gd + ad + 1)];
+  return v;
+}
+extern "C" __global__ void __launch_bounds__(256)
+grx_her_episode_sample_kernel(GrxHerArgs a, const float* __restrict__ ep_rows, const float* __restrict__ ep_acts, const int* __restrict__ ep_meta,
+                              const long long* __restrict__ ep_count, long long E, int strategy, int k_future, unsigned long long seed, unsigned long long call, long long B,
+                              int* __restrict__ valid) {
+  __shared__ int s_e[GRX_HER_CHUNK], s_t[GRX_HER_CHUNK], s_g[GRX_HER_CHUNK], s_ok[GRX_HER_CHUNK];
+  const int OW = 2 * a.obs_dim + 3 * a.goal_dim + a.act_dim + 2, x = threadIdx.x;
+  long long F = *ep_count;
+  F = F < 0 ? 0 : (F > E ? E : F);
+  for (long long b0 = (long long)blockIdx.x * GRX_HER_CHUNK; b0 < B; b0 += (long long)gridDim.x * GRX_HER_CHUNK) {
+    const int rows = B - b0 < GRX_HER_CHUNK ? (int)(B - b0) : GRX_HER_CHUNK;
+    if (x < rows) {
+      int e, t, g;
+      const bool found = grx_her_episode_draw(ep_meta, F, a.T, strategy, k_future, seed, call, b0 + x, &e, &t, &g);
+      s_e[x] = e; s_t[x] = t; s_g[x] = g; s_ok[x] = found ? 1 : 0;
+      if (b0 + x == 0) *valid = found ? (int)B : 0;
+    }
+    __syncthreads();
+    float* __restrict__ out = a.out + b0 * OW;
+    for (int i = x; i < rows * OW; i += 256) {
+      const int r = i / OW;
+      out[i] = s_ok[r] ? grx_her_episode_word(a, ep_rows, ep_acts, s_e[r], s_t[r], s_g[r], i - r * OW) : 0.0f;
+    }
+    __syncthreads();
+  }
+}
+extern "C" int grx_her_episode_sample(const grx_her_args* args, const float* ep_rows, const float* ep_acts, const int* ep_meta, const long long* ep_count, int64_t episodes,
+                                      int strategy, int k_future, uint64_t seed, uint64_t call, int64_t batch, float* out, int* valid, void* stream) {
+  if (!args || !ep_rows || !ep_acts || !ep_meta || !ep_count || !out || !valid) return fail("grx_her_episode_sample: null argument");
+  GrxHerArgs a; memcpy(&a, args, sizeof(a));
+  if (a.T <= 0 || a.obs_dim <= 0 || a.goal_dim <= 0 || a.goal_dim > 16 || a.act_dim <= 0 || a.W < a.obs_dim + 2 * a.goal_dim)
+    return fail("grx_her_episode_sample: dimensions out of range (goal_dim <= 16, W >= obs_dim + 2 goal_dim)");
+  if (a.kind < 0 || a.kind > 3 || (a.kind == 0 && a.goal_dim != 3) || (a.kind == 2 && a.goal_dim != 2) || (a.kind == 3 && a.goal_dim != 7))
+    return fail("grx_her_episode_sample: reward kind does not fit goal_dim");
+  if (episodes < 1 || episodes > 0x7FFFFFFFll) return fail("grx_her_episode_sample: 1 <= episodes < 2^31");
+  if (strategy < 0 || strategy > 2) return fail("grx_her_episode_sample: unknown strategy (0 future, 1 final, 2 episode)");
+  if (k_future < 0 || batch <= 0 || batch > (1ll << 30)) return fail("grx_her_episode_sample: k_future >= 0 and 1 <= batch <= 2^30");
+  a.rows = a.acts = nullptr; a.t_idx = a.w_idx = a.t_goal = nullptr; a.term_rows = nullptr; a.term_t = nullptr;
+  a.out = out;
+  long long blocks = (batch + GRX_HER_CHUNK - 1) / GRX_HER_CHUNK;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(grx_her_episode_sample_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, ep_rows, ep_acts, ep_meta, ep_count, (long long)episodes,
+                     strategy, k_future, (unsigned long long)seed, (unsigned long long)call, (long long)batch, valid);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 // maze episode reset for a compacted list of worlds (include/grx_capi.h): one 64-thread workgroup per listed world
 __device__ __forceinline__ void grx_maze_reset_row(const grx_maze_reset_args& a, int k, int l, float* desired) {
   const int w = a.idx[k];

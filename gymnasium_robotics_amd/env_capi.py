@@ -5,7 +5,8 @@
 
 writes the environment description file grx_env_create reads.  The file is built from the packaged model (models/*.npz) alone:
 no GPU, no asset tree.  This module also holds the ctypes loader of libgrx_env.so, struct mirrors of grx_env.h and a parser of the
-section tables both files use, and the struct mirrors of grx_replay.h (the HER replay attached to a handle: ReplayConfig, ReplayBatch).
+section tables both files use, and the struct mirrors of grx_replay.h (the HER replay attached to a handle: ReplayConfig, ReplayBatch) and of grx_episodes.h (the
+store of finished episodes attached to a replay: EpisodesConfig, EpisodesBatch).
 
 Container (little endian; the description file and the state blob of grx_env_get_state share it):
 
@@ -52,6 +53,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libgrx_env.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_env.h")
 REPLAY_HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_replay.h")
+EPISODES_HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_episodes.h")
 _lib = None
 
 AUTORESET = {"next_step": 0, "same_step": 1, "disabled": 2}
@@ -234,6 +236,18 @@ class ReplayBatch(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_void_p), ("batch", ctypes.c_int64), ("offset", ctypes.c_int64), ("valid", ctypes.c_void_p)]
 
 
+# ------------------------------------------------------------------ grx_episodes.h mirrors
+EPISODES_STRATEGY = {"future": 0, "final": 1, "episode": 2}      # GRX_EPISODES_FUTURE / _FINAL / _EPISODE
+
+
+class EpisodesConfig(ctypes.Structure):
+    _fields_ = [("episodes", ctypes.c_int64), ("max_batch", ctypes.c_int64), ("seed", ctypes.c_uint64)]
+
+
+class EpisodesBatch(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_void_p), ("batch", ctypes.c_int64), ("valid", ctypes.c_void_p)]
+
+
 def lib():
     """libgrx_env.so with its argument types (loads libgrx_hip.so first, through the package loader: one HIP runtime, the one torch uses)"""
     global _lib
@@ -267,6 +281,12 @@ def lib():
         L.grx_replay_relabel.argtypes = [vp, i64, ci, P(ReplayBatch), vp]
         L.grx_replay_reseed.argtypes = [vp, u64]
         L.grx_replay_ring.argtypes = [vp, P(vp), P(i64), P(i64), P(i64)]
+        L.grx_episodes_create.argtypes = [vp, P(EpisodesConfig), P(vp)]
+        L.grx_episodes_destroy.argtypes = [vp]
+        L.grx_episodes_dims.argtypes = [vp, P(ci), P(ci), P(ci), P(ci)]
+        L.grx_episodes_sample.argtypes = [vp, i64, ci, ci, P(EpisodesBatch), vp]
+        L.grx_episodes_reseed.argtypes = [vp, u64]
+        L.grx_episodes_store.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(i64)]
         _lib = L
     return _lib
 

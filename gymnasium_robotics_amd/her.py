@@ -258,3 +258,100 @@ class HerReplay:
         c = np.cumsum([0, o, g, g, a, 1, o, g, 1])
         names = ("observation", "achieved_goal", "desired_goal", "action", "reward", "next_observation", "next_achieved_goal", "success")
         return {n: rows[:, c[i]: c[i + 1]] for i, n in enumerate(names)}
+
+
+class EpisodicHerReplay(HerReplay):
+    """HerReplay + a device store of FINISHED episodes (grx_her_archive, grx_her_episode_sample: include/grx_capi.h).  The ring of HerReplay only holds episodes that are
+    still running; here every episode that ends moves, rows and actions, into one of `episodes` slots [episodes, horizon + 1, W] before the step that ended it is appended,
+    and `sample` draws relabelled transitions from whole episodes -- "future" goals from the whole rest of the episode, "final" and "episode" goals, a fresh relabel of old
+    experience at every call -- in the row format `relabel` writes.  HerReplay's own ring, marks and draws are untouched by the store.
+
+        buf = EpisodicHerReplay(env, horizon=50, capacity=1 << 20, episodes=1 << 16, continuous=True)
+        ... buf.append(a, env.packed, done, final_rows=env.final_packed)      # archives the worlds of `done`, then HerReplay.append
+        rows = buf.sample(4 * env.num_envs, k_future=4, strategy="future")
+    """
+    STRATEGIES = {"future": 0, "final": 1, "episode": 2}
+
+    def __init__(self, env, horizon: int, capacity: int, episodes: int, **kw):
+        if int(episodes) < int(env.num_envs):
+            raise ValueError(f"episodes = {episodes} is less than the number of worlds {env.num_envs}: one step can end an episode in every world")
+        if int(episodes) >= 1 << 31:
+            raise ValueError("episodes must be below 2^31")
+        super().__init__(env, horizon, capacity, **kw)
+        self.E = int(episodes)
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.device)
+        self.ep_rows, self.ep_acts = z(self.E, self.R, self.W), z(self.E, self.R, self.act_dim)      # ep_acts[e, j] = the action that led to row j of episode e
+        self.ep_meta, self.ep_count = z(self.E, 4, dtype=torch.int32), z(1, dtype=torch.int64)         # {len, world, first_row, 0}; episodes archived so far (device)
+        self.archived = 0                          # host mirror of ep_count: decides without a device sync whether anything can be sampled
+        self._sample_seed, self._sample_calls = self._seed, 0
+        self._sample_valid = z(1, dtype=torch.int32)
+        self._list_pin = [dict(buf=torch.empty(self.N, dtype=torch.int32, pin_memory=True), event=None) for _ in range(4)]
+        self._list_next, self._list_dev = 0, z(self.N, dtype=torch.int32)
+
+    def _upload_list(self, worlds):
+        slot = self._list_pin[self._list_next]
+        self._list_next = (self._list_next + 1) % len(self._list_pin)
+        if slot["event"] is not None:
+            slot["event"].synchronize()
+        slot["buf"].numpy()[:len(worlds)] = worlds
+        self._list_dev[:len(worlds)].copy_(slot["buf"][:len(worlds)], non_blocking=True)
+        slot["event"] = torch.cuda.Event()
+        slot["event"].record(torch.cuda.current_stream(self.device))
+        return self._list_dev
+
+    def append(self, actions: torch.Tensor, packed_rows: torch.Tensor, reset_mask: Optional[torch.Tensor] = None, final_rows: Optional[torch.Tensor] = None):
+        """HerReplay.append, after the episodes of the worlds in reset_mask have been moved into the store (one grx_her_archive launch pair, issued BEFORE the append: it
+        reads the ring before this step's row overwrites the oldest one, and the episode marks before these worlds are re-marked).  With terminal rows (final_rows, now or in
+        an earlier call) the stored episode ends with the terminal row and this step's action; without, with the newest ring row."""
+        if self.t >= self.T and not self.continuous:
+            raise RuntimeError("episode buffer is full: call begin_episode()")
+        if reset_mask is not None:
+            host = (reset_mask.cpu().numpy() if isinstance(reset_mask, torch.Tensor) else np.asarray(reset_mask)).astype(bool)
+            count = int(host.sum())
+            if count:
+                actions = (actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions))).to(device=self.device, dtype=torch.float32).contiguous().view(self.N, self.act_dim)
+                term = final_rows if final_rows is not None else self._final_rows
+                a = _native.HerArchiveArgsStruct()
+                a.rows, a.acts, a.start = self.episode.data_ptr(), self.actions.data_ptr(), self.episode_start.data_ptr()
+                a.n_worlds, a.T, a.W, a.act_dim, a.t_prev, a.count = self.N, self.T, self.W, self.act_dim, self.t, count
+                lst = getattr(self.env, "step_reset_list", None)
+                if lst is self._last_list:      # (HerReplay._append_fused: the tuple an earlier append consumed is stale; super().append records this one)
+                    lst = None
+                if lst is not None and lst[1] == count and lst[0].dtype == torch.int32 and lst[0].device == self.device:
+                    a.list = lst[0].data_ptr()
+                else:
+                    a.list = self._upload_list(np.nonzero(host)[0].astype(np.int32)).data_ptr()
+                if term is not None:
+                    assert tuple(term.shape) == (self.N, self.W) and term.is_contiguous()
+                    a.final_rows, a.step_action, a.final_compact = term.data_ptr(), actions.data_ptr(), 0
+                a.ep_rows, a.ep_acts, a.ep_meta, a.ep_count, a.episodes = self.ep_rows.data_ptr(), self.ep_acts.data_ptr(), self.ep_meta.data_ptr(), self.ep_count.data_ptr(), self.E
+                _native.check(self._L.grx_her_archive(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                self.archived += count
+        return super().append(actions, packed_rows, reset_mask, final_rows)
+
+    def reseed_samples(self, seed: int):
+        """restart the index stream of sample(): the same (seed, number of sample calls since) reproduces the same draws; relabel's stream is not touched"""
+        self._sample_seed, self._sample_calls = int(seed), 0
+
+    def sample(self, batch: int, k_future: int = 4, strategy: str = "future", out: Optional[torch.Tensor] = None):
+        """[batch, OW] relabelled transitions drawn from the stored episodes in one kernel: a uniform stored episode, a uniform transition t of it, and with probability
+        k / (k + 1) a substituted goal -- "future": achieved at a uniform later row t + 1 .. L, "final": at the last row, "episode": at a uniform row 0 .. L.  Nothing
+        archived yet: an empty view, and the stream does not advance (as relabel)."""
+        if strategy not in self.STRATEGIES:
+            raise ValueError(f"unknown strategy {strategy!r}: one of {sorted(self.STRATEGIES)}")
+        if batch < 1 or k_future < 0:
+            raise ValueError("batch >= 1 and k_future >= 0")
+        if out is None:
+            out = torch.empty(batch, self.OW, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and tuple(out.shape) == (batch, self.OW) and out.dtype == torch.float32
+        if self.archived == 0:
+            return out[:0]
+        _native.check(self._L.grx_her_episode_sample(ctypes.byref(self._her_args(out)), self.ep_rows.data_ptr(), self.ep_acts.data_ptr(), self.ep_meta.data_ptr(),
+                                                     self.ep_count.data_ptr(), self.E, self.STRATEGIES[strategy], int(k_future), self._sample_seed, self._sample_calls, batch,
+                                                     out.data_ptr(), self._sample_valid.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._sample_calls += 1
+        return out
+
+    def store_views(self):
+        """(rows [E, T+1, W], actions [E, T+1, act_dim], meta [E, 4] int32 = {len, world, first_row, 0}, count [1] int64): the device tensors of the store"""
+        return self.ep_rows, self.ep_acts, self.ep_meta, self.ep_count

@@ -440,6 +440,48 @@ typedef struct grx_her_append_args {
 } grx_her_append_args;
 int grx_her_append(const grx_her_append_args* args, void* stream);
 
+/* The episode store: an archive of FINISHED episodes, episode-major, for a learner that relabels old experience afresh at every gradient step and for the strategies that
+ * need the episode's end ("final", "episode"; "future" over the whole episode).  E slots, horizon T:
+ *     ep_rows [E, T+1, W]   the packed rows of the episode, row 0 first
+ *     ep_acts [E, T+1, ad]  ep_acts[e, j] = the action that led to row j (row 0: zero)
+ *     ep_meta [E, 4] int32  {len, world, first_row, 0}: len = the number of transitions L, 0 <= L <= T, 0 = empty
+ *     ep_count [1] int64    episodes archived so far; device memory, advanced on the device
+ * grx_her_archive moves the episodes that ended in a step out of the ring.  It is issued AFTER that step and BEFORE the grx_her_append of that step, on the same stream: it
+ * must see the ring before row t_prev + 1 overwrites row t_prev - T, and `start` before the reset worlds are re-marked.  The ended worlds come as grx_her_append_args gives
+ * them (list with count or *count_dev, clamped to [0, n_worlds]).  final_rows (optional): the terminal rows, row j of list position j (final_compact != 0) or of world
+ * list[j] (final_compact == 0), with step_action [n_worlds, ad], the actions of this step, which are not in the ring yet.  For list position j, w = list[j], s = 1 with
+ * terminal rows else 0:
+ *     a0 = max(start[w], t_prev - T + s, 0);  L = t_prev - a0 + s;  slot = (ep_count + j) % E
+ *     ep_rows[slot, i] = ring row (a0 + i) % (T+1) of w, i = 0 .. t_prev - a0;  ep_acts likewise for i >= 1, ep_acts[slot, 0] = 0
+ *     ep_rows[slot, L] = terminal row, ep_acts[slot, L] = step_action[w]                  (s = 1)
+ *     ep_meta[slot] = {L, w, a0, 0}
+ * An entry outside [0, n_worlds) takes its slot with len 0 ({0, entry, 0, 0}); so does a world with L <= 0; neither copies anything.  episodes >= n_worlds: one call never
+ * writes a slot twice.  Two launches: the copies, then one thread that adds the count to ep_count.  A host-known count of 0 launches nothing. */
+typedef struct grx_her_archive_args {
+  const float *rows, *acts;            /* the ring: [T+1, n_worlds, W], [T+1, n_worlds, act_dim] */
+  const int* start;                    /* [n_worlds]: episode_start BEFORE this step's marks */
+  const int* list; const int* count_dev;
+  int count, n_worlds, T, W, act_dim;
+  int t_prev;                          /* absolute index of the newest ring row */
+  int final_compact;
+  const float* final_rows; const float* step_action;
+  float *ep_rows, *ep_acts; int* ep_meta; long long* ep_count;
+  long long episodes;                  /* E */
+} grx_her_archive_args;
+int grx_her_archive(const grx_her_archive_args* args, void* stream);
+/* `batch` relabelled transitions drawn from the store, in grx_her_relabel's row format, in ONE kernel (the structure of grx_her_draw_relabel).  args gives T, W, obs_dim,
+ * goal_dim, act_dim and the reward parameters; its pointers are ignored.  Sample b: stream state ((seed * KEY_SEED + call * KEY_CALL) ^ 0x455049534F444553) + b, one output
+ * discarded; F = min(*ep_count, episodes); up to 64 uniform slots e = ((z >> 32) * F) >> 32 until len[e] > 0, then a linear probe of at most F steps; r, r2 the next
+ * outputs, u0 = (r >> 40) 2^-24, u1 = ((r >> 16) & 0xFFFFFF) 2^-24 in fp32; L = len[e], t = min((int)(u0 L), L - 1); the goal row g is
+ *     strategy 0 (future)   min(t + 1 + (int)(u1 (L - t)), L)
+ *     strategy 1 (final)    L
+ *     strategy 2 (episode)  min((int)(u1 (L + 1)), L)
+ * and the episode's own goal is kept iff (r2 >> 40) (k_future + 1) >= k_future 2^24 (an integer compare).  Row: [obs_t | achieved_t | goal | action_t | reward | obs_t+1 |
+ * achieved_t+1 | success] from ep_rows[e, t], ep_rows[e, t + 1], ep_acts[e, t + 1], goal = achieved of ep_rows[e, g] or desired of ep_rows[e, t].  F == 0 or no filled
+ * slot: valid[0] = 0 and out is zero-filled; else valid[0] = batch. */
+int grx_her_episode_sample(const grx_her_args* args, const float* ep_rows, const float* ep_acts, const int* ep_meta, const long long* ep_count, int64_t episodes,
+                           int strategy, int k_future, uint64_t seed, uint64_t call, int64_t batch, float* out, int* valid, void* stream);
+
 /* Episode reset of a COMPACTED list of maze worlds (maze/point_maze.py:377-390 / ant_maze_v5.py reset_model, maze_v4.py:299-358: qpos = init_qpos with
  * xy <- the drawn reset position, qvel = 0, new goal, observation of the reset state): one kernel writes state, goal, obs / achieved / success and the
  * packed row of the n_reset worlds idx[0..n_reset).  The draws (generate_reset_pos / generate_target_goal) stay on the host; stage = [n_reset, 4] rows
