@@ -175,6 +175,8 @@ def lib():
         L.grx_fetch_sample_resets_device.argtypes = [vp, vp, ci, ci, ci, cd, cd, vp, vp, cd, vp, vp]
         L.grx_adroit_sample_resets_device.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]
         L.grx_maze_sample_resets_device.argtypes = [vp, vp, ci, vp, ci, vp, ci, cd, cd, vp, vp, vp, vp]
+        L.grx_maze_sample_resets_list.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, cd, cd, vp, vp]
+        L.grx_maze_reset_rows_list.argtypes = [vp, vp, ci, vp, vp]
         _lib = L
     return _lib
 

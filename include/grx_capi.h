@@ -362,7 +362,14 @@ int grx_uniform_rows_device(uint64_t* states, const unsigned char* mask, int n, 
  * reward = their count, tasks_to_complete / episode_task_completions updates, terminated (every task of the episode completed), TimeLimit truncation, and the
  * autoreset decision: reset_now[w] = 1 for the worlds whose state rows were just rewound to init_qpos / zero velocity (mode 2 same_step: done in this step; mode 1
  * next_step: done in the previous one) -- the caller draws their observation noise (grx_uniform_rows_device with reset_now as mask) and runs the masked forward launch.
- * Nothing is read back: KitchenVecEnv.step(output="torch") has no host synchronisation. */
+ * Nothing is read back: KitchenVecEnv.step(output="torch") has no host synchronisation.
+ * stepped [N] or NULL (= every world): the worlds the step launch covered.  Only a stepped world is scored: its completion bits are read, elapsed advances, terminated /
+ * truncated can be set; a world that was not stepped reports reward 0, no step completions and both flags 0, and its counters stay.  A PENDING world (mode 1 and
+ * needs_reset[w] != 0 on entry) is rewound in this call and reports reward 0 WHATEVER stepped[w] says, and its needs_reset is cleared.  The mode 1 caller masks the pending
+ * worlds out of the step launch and passes stepped[w] = !needs_reset[w] (KitchenVecEnv does): the pending world is then not scored at all -- flags 0, counters untouched
+ * before the rewind -- which is the reference's reset step.  With stepped[w] != 0 (or stepped NULL) a pending world's step is still scored into step_completions,
+ * terminated and truncated before the rewind; its reward is 0 all the same and a `done` found this way does not make it pending again.
+ * In modes 0 and 2 needs_reset is neither read nor written; final_info is written in mode 2 only, for the worlds that are done. */
 typedef struct grx_kitchen_book {
   const int* completed; const unsigned char* stepped;
   int *tasks_to_complete, *episode_completions, *elapsed, *step_completions;
