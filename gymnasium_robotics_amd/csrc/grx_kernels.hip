@@ -5,7 +5,7 @@
 // and write HBM exactly once.  Worlds are independent: no inter-workgroup communication.
 //
 // Build: this ONE source is compiled either as a single translation unit (no GRX_TU_* macro: the profiling variant) or, for the product
-// library, four times in parallel with -DGRX_TU_FETCH / -DGRX_TU_HAND / -DGRX_TU_POINT / -DGRX_TU_ADROIT / -DGRX_TU_KITCHEN / -DGRX_TU_API (one family of kernel
+// library, six times in parallel with -DGRX_TU_FETCH / -DGRX_TU_HAND / -DGRX_TU_POINT / -DGRX_TU_ADROIT / -DGRX_TU_KITCHEN / -DGRX_TU_API (one family of kernel
 // instantiations each; __graft_entry__.build links the objects).  Every unit has its own copy of the constant-memory model descriptors
 // (g_grx_models is static): grx_model_create uploads a descriptor to each of them through grx_tu_*_prepare.
 #if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_API)
@@ -36,6 +36,7 @@
 #include "grx_kitchen_task.h"
 #include "grx_host_model.h"
 #include "grx_copy.h"
+#include "grx_step_frame.h"
 
 static_assert(sizeof(grx_fetch_task) == sizeof(GrxFetchTask), "grx_fetch_task must mirror GrxFetchTask");
 static_assert(sizeof(grx_fetch_buffers) == sizeof(GrxFetchBuffers), "grx_fetch_buffers must mirror GrxFetchBuffers");
@@ -54,8 +55,7 @@ static_assert(sizeof(grx_kitchen_buffers) == sizeof(GrxKitchenBuffers), "grx_kit
 __device__ __forceinline__ void grx_load_world(const GrxModel& m, const GrxFetchBuffers& b, GrxCtx& c, int w, float* lds, int words, int lane_) {
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;  // also zeroes the structurally-zero part of M
   __syncthreads();
-  for (int i = lane_; i < m.nq; i += 64) c.qpos[i] = b.qpos[(size_t)w * m.nq + i];
-  for (int i = lane_; i < m.nv; i += 64) { c.qvel[i] = b.qvel[(size_t)w * m.nv + i]; c.qacc_ws[i] = b.qacc_ws[(size_t)w * m.nv + i]; }
+  grx_state_load(c, b.qpos, (size_t)w * m.nq, b.qvel, (size_t)w * m.nv, b.qacc_ws, (size_t)w * m.nv, m.nq, m.nv, lane_);
   for (int i = lane_; i < 7 * m.nmocap; i += 64) {
     int k = i / 7, e = i - 7 * k; float v = b.mocap[(size_t)w * 7 * m.nmocap + i];
     if (e < 3) c.mocap_pos[3 * k + e] = v; else c.mocap_quat[4 * k + e - 3] = v;
@@ -67,68 +67,8 @@ __device__ __forceinline__ void grx_load_world(const GrxModel& m, const GrxFetch
 // last cleared the buffer (sticky: a capacity overflow in step 17 is still visible after step 50)
 __device__ __forceinline__ int grx_status_word(int old, int now) { now &= 15; return now | ((((old >> 16) | now) & 0xFFFF) << 16); }   // GRX_ST_SOFT and above are internal
 
-// ---- the overflow lane (include/grx_capi.h, grx_overflow_lane)
-// both kernels, before the simulation: the fast kernel may hand the world over at the first overflowing substep (grx_lane_claim, csrc/grx_engine.h), both watch the soft thresholds
-__device__ __forceinline__ void grx_lane_setup(const GrxLane& L, GrxCtx& c, int w, bool stepping) {
-  c.bail = (stepping && L.entry_count != nullptr) ? 1 : 0;
-  if (c.bail) { c.lane_entry_count = L.entry_count; c.lane_entry_list = L.entry_list; c.lane_entry_cap = L.entry_cap; c.lane_world = w; c.lane_ready = L.ready; c.lane_ready_cap = L.ready_cap; }
-  if (stepping && (L.list != nullptr || L.entry_count != nullptr)) { c.soft_maxefc = L.soft_maxefc; c.soft_jpool = L.soft_jpool; c.soft_maxcon = L.soft_maxcon; }
-}
-// fast kernel, after the simulation: true = the world claimed a re-run on the large tables: the caller returns WITHOUT writing anything of it
-__device__ __forceinline__ bool grx_lane_overflowed(const GrxCtx& c) { return c.bail == 2; }
-// append w to the lane of the next step (both kernels); a full list (next_cap: the grid of the next step's launch) leaves the world on the fast kernel
-__device__ __forceinline__ void grx_lane_append(const GrxLane& L, int w) {
-  const int idx = atomicAdd(L.next_count, 1);
-  if (idx < L.next_cap) { L.next_list[idx] = w; L.next_flags[w] = 1; }
-}
-// fast kernel, after a step that did NOT overflow but came within the soft thresholds of a capacity: the result is committed as usual and the world moves to the
-// lane for the next steps -- before it can overflow, so that entering the lane costs no serialised re-run
-__device__ __forceinline__ void grx_lane_join(const GrxLane& L, const GrxCtx& c, int w, int lane_) {
-  if (L.entry_count == nullptr || L.next_list == nullptr || lane_ != 0 || !(c.cnt[2] & GRX_ST_SOFT)) return;
-  L.ttl[w] = (signed char)L.ttl_init;
-  grx_lane_append(L, w);
-}
-// large-table kernel: the world's ticket (it stays in the lane while it is within the soft thresholds, and ttl_init steps longer); st < 0: the world was not part of this
-// step (masked out: it waits for its reset) and keeps its place
-__device__ __forceinline__ void grx_lane_ticket(const GrxLane& L, int st, int w, int lane_) {   // st: the world's status flags of this step, -1 = it was not stepped (by value: taking the context's address would keep the whole GrxCtx in scratch memory)
-  if (L.list == nullptr || lane_ != 0) return;
-  int t = L.ttl[w];
-  if (st >= 0) { t = (st & GRX_ST_SOFT) ? L.ttl_init : (t > 0 ? t - 1 : 0); L.ttl[w] = (signed char)t; }
-  else if (t <= 0) t = 1;
-  if (t > 0) grx_lane_append(L, w);
-}
-// ---- entrants without the serialised re-run (include/grx_capi.h, grx_overflow_lane.ready / progress / poll_*).  The worlds that overflow are the heaviest of the batch and
-// their re-run used to start when the fast launch had ENDED (hand + touch: 2 ms in 60 % of the steps, a hand jammed into the door 5 - 9 ms).  The standing lane launch now
-// carries poll_grid extra workgroups; workgroup p sleeps until entry p of THIS step's entry list is published (ready[p] == 1), claims it (-> 2) and steps the world on the
-// large tables while the fast launch is still running.  It gives up when every workgroup of the fast launch has ended (progress == progress_total) or after a bounded number
-// of polls; whatever is unclaimed then is taken by the entry launch behind the fast kernel, as before.  Nothing waits for anything that is not already submitted.
-__device__ __forceinline__ void grx_lane_progress(const GrxLane& L) { if (L.progress && threadIdx.x == 0) atomicAdd(L.progress, 1); }   // fast kernel: this workgroup has ended
-// entry launch (list == the step's entry list): 1 = entry e was taken by a polling workgroup
-__device__ __forceinline__ int grx_lane_taken(const GrxLane& L, int e) {
-  if (!L.ready || L.poll_grid != 0 || e >= L.ready_cap) return 0;
-  int r = 0;
-  if (threadIdx.x == 0) r = atomicCAS(L.ready + e, 1, 2) != 1;
-  return __builtin_amdgcn_readfirstlane(r);
-}
-// polling workgroup p of the standing launch: the world to step, or -1
-__device__ __forceinline__ int grx_lane_poll(const GrxLane& L, int p) {
-  if (!L.ready || p >= L.ready_cap) return -1;
-  int w = -1;
-  if (threadIdx.x == 0) {
-    for (int it = 0; it < 40000; it++) {      // bounded: ~40000 x 2 us
-      int r = __hip_atomic_load(L.ready + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (r == 0 && __hip_atomic_load(L.progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= L.progress_total)
-        r = __hip_atomic_load(L.ready + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // the fast launch has ended: one last look
-      else if (r == 0) { __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); continue; }
-      if (r == 1 && atomicCAS(L.ready + p, 1, 2) == 1) { __threadfence(); w = ((volatile const int*)L.poll_list)[p]; }
-      break;
-    }
-  }
-  return __builtin_amdgcn_readfirstlane(w);
-}
 __device__ __forceinline__ void grx_store_world(const GrxModel& m, const GrxFetchTask& t, const GrxFetchBuffers& b, GrxCtx& c, int w, int lane_, int keep_outcome = 0) {
-  for (int i = lane_; i < m.nq; i += 64) b.qpos[(size_t)w * m.nq + i] = c.qpos[i];
-  for (int i = lane_; i < m.nv; i += 64) { b.qvel[(size_t)w * m.nv + i] = c.qvel[i]; b.qacc_ws[(size_t)w * m.nv + i] = c.qacc_ws[i]; }
+  grx_state_store(c, b.qpos, (size_t)w * m.nq, b.qvel, (size_t)w * m.nv, b.qacc_ws, (size_t)w * m.nv, m.nq, m.nv, lane_);
   for (int i = lane_; i < 7 * m.nmocap; i += 64) {
     int k = i / 7, e = i - 7 * k;
     b.mocap[(size_t)w * 7 * m.nmocap + i] = (e < 3) ? c.mocap_pos[3 * k + e] : c.mocap_quat[4 * k + e - 3];
@@ -166,26 +106,8 @@ __device__ long long g_grx_world_span[2 * 16384];
 extern "C" int grx_profile_world_spans(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_grx_world_span), sizeof(long long) * 2 * n); }
 #endif
 
-// World <-> workgroup mapping.  The dispatcher deals workgroups round-robin to the 8 XCDs, each with its own L2, so with w = blockIdx.x
-// the rows of neighbouring worlds (88-B qpos rows, 100-B obs rows, 4-B reward / flag entries: several worlds per 128-B line) are
-// fetched by up to 8 L2s and written back as 8 partial lines.  The grid is rounded up to a multiple of 8 and XCD k takes the
-// k-th contiguous slice of the worlds, so a line is read and merged in one L2 (rocprofv3 FETCH_SIZE / WRITE_SIZE: profiles/).
-static inline unsigned grx_grid_for(int n_worlds) { return (unsigned)((n_worlds + 7) & ~7); }
+static inline unsigned grx_grid_for(int n_worlds) { return (unsigned)((n_worlds + 7) & ~7); }   // world <-> workgroup: grx_slot_world (grx_step_frame.h)
 #define GRX_LANE_GRID 64u   // default workgroups of a large-table launch of the overflow lane (grx_overflow_lane.grid): they walk the compacted list
-static __device__ __forceinline__ int grx_world_of_block() { return (int)((blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3)); }
-// the same index re-derived after the substep loop from the (architected) workgroup id: the epilogue's addresses are then computed
-// there instead of being kept -- as 64-bit VGPR pairs spilled to scratch -- across the whole simulation
-static __device__ __forceinline__ unsigned grx_block_late() { unsigned bx = blockIdx.x; asm volatile("" : "+s"(bx)); return bx; }
-// (split step: `parts` workgroups per world, workgroup index = part * G + slot with G = gridDim.x / parts)
-static __device__ __forceinline__ int grx_world_of_slot_late(const int* order, int parts) {
-  unsigned bx = blockIdx.x; asm volatile("" : "+s"(bx));
-  const unsigned G = parts > 1 ? gridDim.x / (unsigned)parts : gridDim.x, slot = parts > 1 ? bx % G : bx;
-  return order ? order[slot] : (int)((slot & 7u) * (G >> 3) + (slot >> 3));
-}
-static __device__ __forceinline__ int grx_world_of_block_late() {
-  unsigned bx = blockIdx.x; asm volatile("" : "+s"(bx));
-  return (int)((bx & 7u) * (gridDim.x >> 3) + (bx >> 3));
-}
 
 // Model shapes.  A step kernel specialised for a shape has all layout dims as compile-time constants: the LDS carve folds
 // into immediate offsets of the ds_read/ds_write instructions (no address arithmetic, no pointer SGPRs) and the loops over
@@ -248,21 +170,7 @@ typedef GrxShape<31, 30, 20, 26, 25, 24, 0, 0, 24, 0, 256, 4080, 92, 64, 1, 2> G
 #endif
 // one world's env.step().  LANE: called from the list-walking loop of the large-table kernel (w comes from the list; see grx_overflow_lane)
 // SPLIT (include/grx_capi.h, grx_fetch_buffers.split_parts): `part` of `parts` workgroups of this world, each running its share of the substeps; 0 of 1 = the whole step.
-// How a part of a split step hands the world to the next one (MI355X_MICROARCH.md, workgroup dispatch / hand-off forms): the carrier row is written with write-through (volatile = sc0 sc1)
-// stores, drained with s_waitcnt vmcnt(0), then the flag word is stored the same way; the reader polls the flag and reads the row with L1-bypassing (volatile) loads.  Valid for any
-// workgroup -> XCD placement, and without an agent-scope release: `__threadfence()` writes back EVERY dirty line of the XCD's L2 (buffer_wbl2) -- the scratch of all resident waves --
-// once per part and wave: that was 19 MB of write-back per launch of 4 096 worlds (PMC traffic 3.9x -> 10.6x algorithmic) and what made a third and fourth part cost more than they
-// saved.  -DGRX_SPLIT_AGENT_FENCES restores the fences (A/B: tools/ab_split_fences.sh).
-#ifdef GRX_SPLIT_AGENT_FENCES
-#define GRX_SPLIT_ROW float
-#define GRX_SPLIT_DRAIN() __threadfence()
-#define GRX_SPLIT_ACQUIRE() __threadfence()
-#else
-#define GRX_SPLIT_ROW volatile float
-#define GRX_SPLIT_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define GRX_SPLIT_ACQUIRE() asm volatile("" ::: "memory")
-#endif
-#define GRX_SPLIT_SPIN_LIMIT (1 << 22)   // polls (~64 cycles each: > 100 ms) before a part gives its predecessor up: never reached while workgroups of an XCD start in index order
+// The protocol: grx_step_frame.h; the carrier is the world's hand-off row, which also carries the flags of the earlier parts (2 state words: progress, time).
 template <class S, bool LANE>
 __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTask& t, const GrxFetchBuffers& b, const int w, int n_worlds, int words, float* lds, const int lane_,
                                                      const int part = 0, const int parts = 1) {
@@ -270,35 +178,18 @@ __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTa
   if (b.mask && !b.mask[w]) { if (LANE) grx_lane_ticket(b.lane, -1, w, lane_); return; }
   if (!LANE && b.lane.skip && b.lane.skip[w]) return;   // in the overflow lane: stepped by the large-table kernel
   const bool split = !LANE && parts > 1, last_part = part == parts - 1;
-  if (split && part > 0) {   // wait for the part before this one (it was dispatched earlier on the same XCD: it is running or done)
-    volatile int* st = b.split_state + 2 * (size_t)w;
-    int v = 0;
-    for (int spins = 0; spins < GRX_SPLIT_SPIN_LIMIT; spins++) {
-      v = __builtin_amdgcn_readfirstlane(st[0]);
-      if (v == part || v < 0) break;
-      __builtin_amdgcn_s_sleep(8);
-    }
-    if (v != part) {   // the earlier part booked the world's re-run (v < 0), or never came (v < part: flagged): nothing to do here; the last part leaves the word clean
-      if (lane_ == 0) { if (v >= 0) b.status[w] |= GRX_ST_BADNUM | (GRX_ST_BADNUM << 16); if (last_part) st[0] = 0; }
-      return;
-    }
-    GRX_SPLIT_ACQUIRE();
-  }
+  if (split && part > 0 && !grx_split_wait<1>(b.split_state + 2 * (size_t)w, b.status, w, part, last_part, lane_)) return;
   const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
   grx_lane_setup(b.lane, c, w, true);
   if (b.handoff && c.bail && !split) { c.handoff = b.handoff; c.handoff_stride = b.handoff_stride; c.handoff_large = b.handoff_large; }   // this launch can hand a world off mid-step (it has an entry list to claim from)
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-  if (lane_ == 0) { for (int k = 0; k < GRX_NPROF; k++) prof_s[k] = 0; prof_s[GRX_NPROF] = clock64(); if (w < 16384) g_grx_world_span[2 * w] = wall_clock64(); }
-#endif
+  GRX_PROF_BEGIN(c, lane_);
 #ifndef GRX_COST_MODEL
-  if (b.cost && lane_ == 0) b.cost[w] = (int)wall_clock64();   // start stamp (100 MHz), parked in the cost slot itself: nothing stays live across the substep loop
+  grx_cost_start(b.cost, w, lane_);
 #endif
-#if defined(GRX_WORLD_SPAN) && !defined(GRX_PROFILE)
+#if defined(GRX_PROFILE) || defined(GRX_WORLD_SPAN)
   if (lane_ == 0 && w < 16384) g_grx_world_span[2 * w] = wall_clock64();
 #endif
   grx_load_world(m, b, c, w, lds, words, lane_);
@@ -320,9 +211,7 @@ __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTa
       o += nu;
       for (int i = lane_; i < 7 * nmo; i += 64) { const int k = i / 7, e = i - 7 * k; const float v = row[o + i]; if (e < 3) c.mocap_pos[3 * k + e] = v; else c.mocap_quat[4 * k + e - 3] = v; }
       o += 7 * nmo;
-      for (int i = lane_; i < nq; i += 64) c.qpos[i] = row[o + i];
-      o += nq;
-      for (int i = lane_; i < nv; i += 64) { c.qvel[i] = row[o + i]; c.qacc_ws[i] = row[o + nv + i]; }
+      grx_state_load(c, row, o, row, o + nq, row, o + nq + nv, nq, nv, lane_);
       if (lane_ == 0) { c.cnt[2] |= ((volatile const int*)row)[1]; ((volatile int*)row)[0] = 0; }   // the flags of the substeps the other kernel ran; the row is consumed
       __syncthreads();
       c.resume_first = (split && part > 0) ? 0 : 1;   // (a part of a split step ended at a substep BOUNDARY: the next substep normalises the free-joint quaternions as the plain step does)
@@ -331,7 +220,7 @@ __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTa
   }
   const int total_ = t.n_substeps + (t.block_gripper ? 1 : 0), s_end = (split && !last_part) ? ((part + 1) * total_) / parts : -1;
   GrxFetch<S>::grx_fetch_sim_world(&m, &t, &c, aux_in, b.action + (size_t)w * 4, lane_, s0, s_end);
-  const int wl = LANE ? w : grx_world_of_slot_late(b.order, parts);
+  const int wl = LANE ? w : grx_slot_world_late(b.order, parts);
   if (split && !last_part) {   // an earlier part of a split step: the state goes to the world's row, nothing else is written
     volatile int* st = b.split_state + 2 * (size_t)wl;
     if (grx_lane_overflowed(c)) { if (lane_ == 0) st[0] = -1; }      // the re-run on the large tables is booked: the later parts return
@@ -344,14 +233,12 @@ __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTa
       o += nu;
       for (int i = lane_; i < 7 * nmo; i += 64) { const int k = i / 7, e = i - 7 * k; row[o + i] = (e < 3) ? c.mocap_pos[3 * k + e] : c.mocap_quat[4 * k + e - 3]; }
       o += 7 * nmo;
-      for (int i = lane_; i < nq; i += 64) row[o + i] = c.qpos[i];
-      o += nq;
-      for (int i = lane_; i < nv; i += 64) { row[o + i] = c.qvel[i]; row[o + nv + i] = c.qacc_ws[i]; }
+      grx_state_store(c, row, o, row, o + nq, row, o + nq + nv, nq, nv, lane_);
       if (lane_ == 0) { ((volatile int*)row)[1] = c.cnt[2]; ((volatile int*)row)[0] = s_end + 1; }
       GRX_SPLIT_DRAIN();
       __syncthreads();
       if (lane_ == 0) {
-        if (b.cost) { const int t0 = ((volatile int*)b.cost)[wl]; st[1] = (part > 0 ? st[1] : 0) + (((int)wall_clock64() - t0) >> 3); }
+        if (b.cost) st[1] = (part > 0 ? st[1] : 0) + grx_cost_since(b.cost, wl);
         GRX_SPLIT_DRAIN();
         st[0] = part + 1;
       }
@@ -376,18 +263,16 @@ __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTa
 #ifdef GRX_COST_MODEL
   if (b.cost && lane_ == 0) b.cost[wl] = 12 * c.cnt[6] + 24 * c.cnt[0];
 #else
-  if (b.cost && lane_ == 0) { const int t0 = ((volatile int*)b.cost)[wl]; b.cost[wl] = (((int)wall_clock64() - t0) >> 3) + (split ? ((volatile int*)b.split_state)[2 * (size_t)wl + 1] : 0); }
+  if (b.cost && lane_ == 0) grx_cost_stop(b.cost, wl, split ? ((volatile int*)b.split_state)[2 * (size_t)wl + 1] : 0);
 #endif
 #endif
   if (split && lane_ == 0) ((volatile int*)b.split_state)[2 * (size_t)wl] = 0;   // the last part leaves the world's word clean for the next launch
-#if defined(GRX_WORLD_SPAN) && !defined(GRX_PROFILE)
+  GRX_PROF_END(c, lane_);
+#if defined(GRX_PROFILE) || defined(GRX_WORLD_SPAN)
   if (lane_ == 0 && wl < 16384) g_grx_world_span[2 * wl + 1] = wall_clock64();
 #endif
 #ifdef GRX_PROFILE
-  GRX_TICK(&c, GRX_P_OTHER);
-  if (lane_ == 0) for (int k = 0; k < GRX_NPROF; k++) atomicAdd((unsigned long long*)&g_grx_prof[k], (unsigned long long)c.prof[k]);  // summed over worlds
-  if (lane_ == 0 && w < 16384) g_grx_world_span[2 * w + 1] = wall_clock64();
-  if (lane_ == 0 && w < 4096) for (int k = 0; k < GRX_NPROF; k++) g_grx_world_prof[w * GRX_NPROF + k] = (int)c.prof[k];
+  if (lane_ == 0 && wl < 4096) for (int k = 0; k < GRX_NPROF; k++) g_grx_world_prof[wl * GRX_NPROF + k] = (int)c.prof[k];   // per-world rows (tools/straggler_probe.py)
 #endif
 }
 template <class S>
@@ -395,9 +280,9 @@ __global__ void __launch_bounds__(64, GRX_FETCH_WAVES(S))
 grx_fetch_step_kernel(int mslot, GrxFetchTask t, GrxFetchBuffers b, int n_worlds, int words) {
   extern __shared__ float lds[];
   const int lane_ = threadIdx.x;
-  const int parts = b.split_parts > 1 ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup: grx_world_of_block)
+  const int parts = b.split_parts > 1 ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup)
   const unsigned G = gridDim.x / (unsigned)parts, part = blockIdx.x / G, slot = blockIdx.x - part * G;   // slot and slot + G, slot + 2 G ... share blockIdx.x mod 8: one XCD, one L2 for all parts of a world; ONE call site of the step (code size, compile time)
-  grx_fetch_step_world<S, false>(mslot, t, b, b.order ? b.order[slot] : (int)((slot & 7u) * (G >> 3) + (slot >> 3)), n_worlds, words, lds, lane_, (int)part, parts);
+  grx_fetch_step_world<S, false>(mslot, t, b, grx_slot_world(b.order, slot, G), n_worlds, words, lds, lane_, (int)part, parts);
   grx_lane_progress(b.lane);   // (launches with polling workgroups behind them: this workgroup has ended)
 }
 // the large-table kernel of the overflow lane (grx_overflow_lane): a small fixed grid walks the compacted list of worlds; generic shape only
@@ -424,20 +309,17 @@ template <class S>
 __global__ void __launch_bounds__(64, GRX_FETCH_WAVES(S))
 grx_fetch_forward_kernel(int mslot, GrxFetchTask t, GrxFetchBuffers b, int n_worlds, int words, int nstep) {
   extern __shared__ float lds[];
-  const int w = grx_world_of_block(), lane_ = threadIdx.x;
+  const int w = grx_slot_world(nullptr, blockIdx.x, gridDim.x), lane_ = threadIdx.x;
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
   const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-#endif
+  GRX_PROF_BEGIN(c, lane_);
   grx_load_world(m, b, c, w, lds, words, lane_);
   { const int total = nstep > 0 ? nstep : 1; for (int s = 0; s < total; s++) GrxEngine<S>::grx_forward_euler(&m, &c, nstep > 0, lane_); }
-  const int wl = grx_world_of_block_late();
+  const int wl = grx_slot_world_late(nullptr, 1);
   GrxFetch<S>::grx_fetch_outputs(&m, &t, &c, b.aux + (size_t)wl * 8, b.obs + (size_t)wl * t.obs_dim, b.achieved + (size_t)wl * 3, lane_);
   __syncthreads();
   grx_store_world(m, t, b, c, wl, lane_);
@@ -466,10 +348,7 @@ grx_fetch_reset_kernel(int mslot, GrxFetchTask t, GrxFetchBuffers b, GrxFetchRes
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-#endif
+  GRX_PROF_BEGIN(c, lane_);
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;
   __syncthreads();
   for (int i = lane_; i < m.nq; i += 64) c.qpos[i] = r.init_qpos[i];
@@ -497,58 +376,34 @@ __global__ void __launch_bounds__(64, S::kFixed ? 3 : 2)
 grx_point_step_kernel(int mslot, GrxPointTask t, GrxPointBuffers b, int n_worlds, int words) {
   extern __shared__ float lds[];
   const int lane_ = threadIdx.x;
-  // SPLIT STEP (include/grx_capi.h grx_point_buffers.split_parts; the Fetch family's: grx_fetch_buffers.split_parts): P workgroups per world, workgroup part * G + slot running the
-  // substeps [part T / P, (part + 1) T / P) of the slot's world.  The carrier is the world's own state row: at a substep boundary qpos / qvel / warm start are the whole state.
+  // SPLIT STEP (include/grx_capi.h grx_point_buffers.split_parts; protocol: grx_step_frame.h).  The carrier is the world's own state row: at a substep boundary qpos / qvel /
+  // warm start are the whole state; 2 state words (progress, flags), no time, and no part ever books a re-run.
   const int parts = b.split_parts > 1 ? b.split_parts : 1;
-  const unsigned G = gridDim.x / (unsigned)parts, part = blockIdx.x / G, slot = blockIdx.x - part * G;   // slot, slot + G, ... share blockIdx.x mod 8: one XCD (one L2) for all parts of a world
-  const int w = (int)((slot & 7u) * (G >> 3) + (slot >> 3));
+  const unsigned G = gridDim.x / (unsigned)parts, part = blockIdx.x / G, slot = blockIdx.x - part * G;
+  const int w = grx_slot_world(nullptr, slot, G);
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
   const bool split = parts > 1, last_part = (int)part == parts - 1;
-  if (split && part > 0) {   // wait for the part before this one (dispatched earlier on the same XCD: running or done)
-    volatile int* st = b.split_state + 2 * (size_t)w;
-    int v = 0;
-    for (int spins = 0; spins < GRX_SPLIT_SPIN_LIMIT; spins++) {
-      v = __builtin_amdgcn_readfirstlane(st[0]);
-      if (v == (int)part) break;
-      __builtin_amdgcn_s_sleep(8);
-    }
-    if (v != (int)part) {   // the earlier part never came: flagged; the last part leaves the words clean
-      if (lane_ == 0) { b.status[w] |= GRX_ST_BADNUM | (GRX_ST_BADNUM << 16); if (last_part) { st[0] = 0; st[1] = 0; } }
-      return;
-    }
-    GRX_SPLIT_ACQUIRE();
-  }
+  if (split && part > 0 && !grx_split_wait<2>(b.split_state + 2 * (size_t)w, b.status, w, (int)part, last_part, lane_)) return;
   const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-  if (lane_ == 0) { for (int k = 0; k < GRX_NPROF; k++) prof_s[k] = 0; prof_s[GRX_NPROF] = clock64(); }
-#endif
+  GRX_PROF_BEGIN(c, lane_);
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;
   __syncthreads();
-  if (split && part > 0) {   // rows the part before this one wrote on another CU during this launch: cache-bypassing loads, ordered behind its flag by the fence above
+  if (split && part > 0) {   // rows the part before this one wrote on another CU during this launch: cache-bypassing loads, ordered behind its flag by the wait above
     volatile const float *vq = b.qpos + (size_t)w * m.nq, *vv = b.qvel + (size_t)w * m.nv, *va = b.qacc_ws + (size_t)w * m.nv;
-    for (int i = lane_; i < m.nq; i += 64) c.qpos[i] = vq[i];
-    for (int i = lane_; i < m.nv; i += 64) { c.qvel[i] = vv[i]; c.qacc_ws[i] = va[i]; }
-  } else {
-  for (int i = lane_; i < m.nq; i += 64) c.qpos[i] = b.qpos[(size_t)w * m.nq + i];
-  for (int i = lane_; i < m.nv; i += 64) { c.qvel[i] = b.qvel[(size_t)w * m.nv + i]; c.qacc_ws[i] = b.qacc_ws[(size_t)w * m.nv + i]; }
-  }
+    grx_state_load(c, vq, 0, vv, 0, va, 0, m.nq, m.nv, lane_);
+  } else grx_state_load(c, b.qpos, (size_t)w * m.nq, b.qvel, (size_t)w * m.nv, b.qacc_ws, (size_t)w * m.nv, m.nq, m.nv, lane_);
   __syncthreads();
   const int s0 = split ? ((int)part * t.n_substeps) / parts : 0, s1 = split ? (((int)part + 1) * t.n_substeps) / parts : t.n_substeps;
   GrxPoint<S>::grx_point_sim_world(&m, &t, &c, b.action + (size_t)w * m.nu, lane_, s0, s1);
-  unsigned bx_ = blockIdx.x; asm volatile("" : "+s"(bx_));   // (re-derived, not kept live across the simulation)
-  const unsigned Gl = gridDim.x / (unsigned)parts, sl = bx_ % Gl;
-  const int wl = (int)((sl & 7u) * (Gl >> 3) + (sl >> 3));
+  const int wl = grx_slot_world_late(nullptr, parts);   // (re-derived, not kept live across the simulation)
   if (split && !last_part) {   // an earlier part: the state row IS the carrier; the flags of its substeps travel in the world's second word
     __syncthreads();
     GRX_SPLIT_ROW *rq = b.qpos + (size_t)wl * m.nq, *rv = b.qvel + (size_t)wl * m.nv, *ra = b.qacc_ws + (size_t)wl * m.nv;
-    for (int i = lane_; i < m.nq; i += 64) rq[i] = c.qpos[i];
-    for (int i = lane_; i < m.nv; i += 64) { rv[i] = c.qvel[i]; ra[i] = c.qacc_ws[i]; }
+    grx_state_store(c, rq, 0, rv, 0, ra, 0, m.nq, m.nv, lane_);
     GRX_SPLIT_DRAIN();
     __syncthreads();
     if (lane_ == 0) {
@@ -559,13 +414,11 @@ grx_point_step_kernel(int mslot, GrxPointTask t, GrxPointBuffers b, int n_worlds
     }
     return;
   }
-  if (split && lane_ == 0) { volatile int* st = b.split_state + 2 * (size_t)wl; c.cnt[2] |= st[1]; st[0] = 0; st[1] = 0; }   // the flags of the earlier parts; the words are clean for the next launch
-  if (split) __syncthreads();
+  if (split) grx_split_collect<2>(c, b.split_state + 2 * (size_t)wl, lane_);
   float* obs = b.obs + (size_t)wl * (m.nq + m.nv - (t.agent ? 2 : 0)); float* ach = b.achieved + (size_t)wl * 2;
   GrxPoint<S>::grx_point_outputs(&m, &t, &c, obs, ach, lane_);
   __syncthreads();
-  for (int i = lane_; i < m.nq; i += 64) b.qpos[(size_t)wl * m.nq + i] = c.qpos[i];
-  for (int i = lane_; i < m.nv; i += 64) { b.qvel[(size_t)wl * m.nv + i] = c.qvel[i]; b.qacc_ws[(size_t)wl * m.nv + i] = c.qacc_ws[i]; }
+  grx_state_store(c, b.qpos, (size_t)wl * m.nq, b.qvel, (size_t)wl * m.nv, b.qacc_ws, (size_t)wl * m.nv, m.nq, m.nv, lane_);
   if (lane_ == 0) {
     const double d = grx_goal_distance2(ach, b.goal + (size_t)wl * 2);
     int succ = d <= t.goal_radius;
@@ -583,10 +436,7 @@ grx_point_step_kernel(int mslot, GrxPointTask t, GrxPointBuffers b, int n_worlds
       row[od + 4] = grx_maze_reward(d, t.goal_radius, t.sparse_reward); row[od + 5] = (d <= t.goal_radius) ? 1.0f : 0.0f;
     }
   }
-#ifdef GRX_PROFILE
-  GRX_TICK(&c, GRX_P_OTHER);
-  if (lane_ == 0) for (int k = 0; k < GRX_NPROF; k++) atomicAdd((unsigned long long*)&g_grx_prof[k], (unsigned long long)c.prof[k]);
-#endif
+  GRX_PROF_END(c, lane_);
 }
 
 // Shadow hand reach env.step() (or mj_forward + outputs when forward_only): one wavefront per world, same engine
@@ -599,31 +449,14 @@ __device__ __forceinline__ void grx_hand_step_world(int mslot, const GrxHandTask
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) { if (in_lane) grx_lane_ticket(b.lane, -1, w, lane_); return; }
   if (!in_lane && forward_only != 1 && b.lane.skip && b.lane.skip[w]) return;   // in the overflow lane: stepped by the large-table kernel (reset-time forward passes cover every masked world)
-  // SPLIT STEP (include/grx_capi.h grx_hand_buffers.split_parts; see grx_adroit_step_world): part `part` of `parts` workgroups of this world, each running its share of the substeps (plain step launches only)
+  // SPLIT STEP (include/grx_capi.h grx_hand_buffers.split_parts; protocol: grx_step_frame.h): part `part` of `parts` workgroups of this world, each running its share of the substeps (plain step launches only)
   const bool split = parts > 1, last_part = part == parts - 1;
-  if (split && part > 0) {
-    volatile int* st = b.split_state + 4 * (size_t)w;
-    int v = 0;
-    for (int spins = 0; spins < GRX_SPLIT_SPIN_LIMIT; spins++) {
-      v = __builtin_amdgcn_readfirstlane(st[0]);
-      if (v == part || v < 0) break;
-      __builtin_amdgcn_s_sleep(8);
-    }
-    if (v != part) {   // the earlier part booked the world's re-run (v < 0), or never came (flagged): nothing to do here; the last part leaves the words clean
-      if (lane_ == 0) { if (v >= 0) b.status[w] |= GRX_ST_BADNUM | (GRX_ST_BADNUM << 16); if (last_part) { st[0] = 0; st[1] = 0; st[2] = 0; } }
-      return;
-    }
-    GRX_SPLIT_ACQUIRE();
-  }
+  if (split && part > 0 && !grx_split_wait<3>(b.split_state + 4 * (size_t)w, b.status, w, part, last_part, lane_)) return;
   const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-  if (lane_ == 0) { for (int k = 0; k < GRX_NPROF; k++) prof_s[k] = 0; prof_s[GRX_NPROF] = clock64(); }
-#endif
+  GRX_PROF_BEGIN(c, lane_);
   const int nq = S::kFixed ? S::NQ : m.nq, nv = S::kFixed ? S::NV : m.nv, nu = S::kFixed ? S::NU : m.nu;
   // REPEAT launches (grx_hand_step_repeat: forward_only carries the count, >= 2): that many consecutive env.step()s of the same action rows without leaving the kernel -- each one
   // the whole body below, state rows written and read back exactly as between two launches (bit-identical to them), so a reset's ten settle steps (manipulate.py:205-224) are
@@ -635,14 +468,14 @@ __device__ __forceinline__ void grx_hand_step_world(int mslot, const GrxHandTask
   float* obs = b.obs + (size_t)w * od; float* ach = b.achieved + (size_t)w * gd; float* palm = b.palm + (size_t)w * 3;
   for (int rep = 0; rep < nrep; rep++) {
   if (rep > 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }   // the rows this wave wrote in the previous repetition are read back below: its stores have reached the L2, this CU's L1 is invalidated (no release fence: that would write back the whole L2, see GRX_SPLIT_DRAIN)
-  if (b.cost && lane_ == 0) b.cost[w] = (int)wall_clock64();   // start stamp, parked in the cost slot (see grx_fetch_step_kernel)
+  grx_cost_start(b.cost, w, lane_);
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;
   __syncthreads();
   if (split && part > 0) {   // the row the part before this one wrote on another CU during this launch: cache-bypassing loads
     volatile const float* row = b.split_rows + (size_t)w * b.split_stride;
     for (int i = lane_; i < nq; i += 64) c.qpos[i] = row[i];
     for (int i = lane_; i < nv; i += 64) { c.qvel[i] = row[nq + i]; c.qacc_ws[i] = row[nq + nv + i]; }
-  } else {
+  } else {   // (written out: with grx_state_load / _store here the register allocation of these kernels moves, profiles/kernel_resources_step_frame.txt)
   for (int i = lane_; i < nq; i += 64) c.qpos[i] = b.qpos[(size_t)w * nq + i];
   for (int i = lane_; i < nv; i += 64) { c.qvel[i] = b.qvel[(size_t)w * nv + i]; c.qacc_ws[i] = b.qacc_ws[(size_t)w * nv + i]; }
   }
@@ -655,11 +488,11 @@ __device__ __forceinline__ void grx_hand_step_world(int mslot, const GrxHandTask
     GrxHand<S>::grx_hand_step_world(&m, &t, &c, b.action + (size_t)w * nu, obs, ach, palm, lane_, s0, s1, !split || last_part);
   }
   __syncthreads();
-  if (split && !last_part) {   // an earlier part: the state goes to the world's carrier row (write-through + drained flag: GRX_SPLIT_DRAIN), nothing else is written
+  if (split && !last_part) {   // an earlier part: the state goes to the world's carrier row (written out), nothing else is written
     volatile int* st = b.split_state + 4 * (size_t)w;
     if (grx_lane_overflowed(c)) { if (lane_ == 0) st[0] = -1; }      // the re-run on the large tables is booked: the later parts return
     else {
-      GRX_SPLIT_ROW* row = b.split_rows + (size_t)w * b.split_stride;
+      GRX_SPLIT_ROW* row = b.split_rows + (size_t)w * b.split_stride;   // (no barrier of its own: the one above)
       for (int i = lane_; i < nq; i += 64) row[i] = c.qpos[i];
       for (int i = lane_; i < nv; i += 64) { row[nq + i] = c.qvel[i]; row[nq + nv + i] = c.qacc_ws[i]; }
       GRX_SPLIT_DRAIN();
@@ -673,13 +506,9 @@ __device__ __forceinline__ void grx_hand_step_world(int mslot, const GrxHandTask
     }
     return;
   }
-  int earlier = 0;
-  if (split) {   // the last part: the flags and the measured time of the earlier parts; the words are clean for the next launch
-    if (lane_ == 0) { volatile int* st = b.split_state + 4 * (size_t)w; c.cnt[2] |= st[1]; earlier = st[2]; st[0] = 0; st[1] = 0; st[2] = 0; }
-    __syncthreads();
-  }
+  const int earlier = split ? grx_split_collect<3>(c, b.split_state + 4 * (size_t)w, lane_) : 0;   // the last part: the flags and the measured time of the earlier parts
   if (grx_lane_overflowed(c)) {   // capacity overflow: keep nothing (obs / achieved are outputs only), re-run on the large tables
-    if (lane_ == 0 && b.cost) { const int t0 = ((volatile int*)b.cost)[w]; b.cost[w] = (((int)wall_clock64() - t0) >> 3) + earlier; }
+    if (lane_ == 0 && b.cost) grx_cost_stop(b.cost, w, earlier);
     return;
   }
   if (in_lane) grx_lane_ticket(b.lane, c.cnt[2] & 0xFFFF, w, lane_); else if (!forward_only) grx_lane_join(b.lane, c, w, lane_);
@@ -697,7 +526,7 @@ __device__ __forceinline__ void grx_hand_step_world(int mslot, const GrxHandTask
       b.success[w] = (d < t.distance_threshold) ? 1 : 0;
     }
     b.status[w] = grx_status_word(b.status[w], c.cnt[2]);
-    if (b.cost) { const int t0 = ((volatile int*)b.cost)[w]; b.cost[w] = (((int)wall_clock64() - t0) >> 3) + earlier; }   // measured duration of this world, 80 ns units (see grx_fetch_step_kernel)
+    if (b.cost) grx_cost_stop(b.cost, w, earlier);
   }
   if (b.packed) {   // [obs | achieved | desired | reward | success] row for the cross-rank gather
     float* row = b.packed + (size_t)w * (od + 2 * gd + 2);
@@ -707,19 +536,16 @@ __device__ __forceinline__ void grx_hand_step_world(int mslot, const GrxHandTask
     if (lane_ == 0) { row[od + 2 * gd] = b.reward[w]; row[od + 2 * gd + 1] = b.success[w] ? 1.0f : 0.0f; }
   }
   }   // repetitions
-#ifdef GRX_PROFILE
-  GRX_TICK(&c, GRX_P_OTHER);
-  if (lane_ == 0) for (int k = 0; k < GRX_NPROF; k++) atomicAdd((unsigned long long*)&g_grx_prof[k], (unsigned long long)c.prof[k]);
-#endif
+  GRX_PROF_END(c, lane_);
 }
 template <class S>
 __global__ void __launch_bounds__(64, (S::kFixed && S::JP <= 512) ? GRX_HANDREACH_WAVES : 2)   // third wave per SIMD only where the LDS footprint lets more than 8 worlds share a CU (HandReach); the object models sit at 8
 grx_hand_step_kernel(int mslot, GrxHandTask t, GrxHandBuffers b, int n_worlds, int words, int forward_only) {
   extern __shared__ float lds[];
   const int lane_ = threadIdx.x;
-  const int parts = (b.split_parts > 1 && forward_only == 0) ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup: grx_world_of_block)
+  const int parts = (b.split_parts > 1 && forward_only == 0) ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup)
   const unsigned G = gridDim.x / (unsigned)parts, part = blockIdx.x / G, slot = blockIdx.x - part * G;   // slot, slot + G, ... share blockIdx.x mod 8; ONE call site of the step (code size, compile time)
-  grx_hand_step_world<S>(mslot, t, b, b.order ? b.order[slot] : (int)((slot & 7u) * (G >> 3) + (slot >> 3)), n_worlds, words, forward_only, lds, lane_, false, (int)part, parts);
+  grx_hand_step_world<S>(mslot, t, b, grx_slot_world(b.order, slot, G), n_worlds, words, forward_only, lds, lane_, false, (int)part, parts);
   grx_lane_progress(b.lane);
 }
 // the large-table kernel of the overflow lane (grx_overflow_lane): a small fixed grid walks the compacted list of worlds; generic shape only
@@ -727,10 +553,7 @@ template <class S>
 __global__ void __launch_bounds__(64, 2)
 grx_hand_lane_kernel(int mslot, GrxHandTask t, GrxHandBuffers b, int n_worlds, int words) {   // one workgroup per entry of the compacted list (see grx_fetch_lane_kernel)
   extern __shared__ float lds[];
-  const int e = blockIdx.x, nstand = (int)gridDim.x - b.lane.poll_grid;
-  if (e >= nstand) { const int w = grx_lane_poll(b.lane, e - nstand); if (w >= 0) grx_hand_step_world<S>(mslot, t, b, w, n_worlds, words, 0, lds, (int)threadIdx.x, true); return; }
-  if (e >= *b.lane.count || grx_lane_taken(b.lane, e)) return;
-  grx_hand_step_world<S>(mslot, t, b, b.lane.list[e], n_worlds, words, 0, lds, (int)threadIdx.x, true);
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_hand_step_world<S>(mslot, t, b, w, n_worlds, words, 0, lds, (int)threadIdx.x, true); });
 }
 
 // AdroitHandHammer env.step() (or, forward_only, the reset-time mj_forward + observation): one wavefront per world, same engine + the noslip pass
@@ -772,32 +595,17 @@ __device__ __forceinline__ void grx_adroit_step_world(int mslot, const GrxAdroit
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) { if (in_lane) grx_lane_ticket(b.lane, -1, w, lane_); return; }
   if (!in_lane && !forward_only && b.lane.skip && b.lane.skip[w]) return;   // in the overflow lane: stepped by the large-table kernel (reset-time forward passes cover every masked world)
-  // SPLIT STEP (include/grx_capi.h grx_adroit_buffers.split_parts; mechanism: grx_fetch_buffers.split_parts): part `part` of `parts` workgroups of this world, each running its share of the
-  // frame_skip substeps; the carrier is the world's row of split_rows (the state rows stay untouched until the last part, so a world that exceeds a table is re-run from them as usual)
+  // SPLIT STEP (include/grx_capi.h grx_adroit_buffers.split_parts; protocol: grx_step_frame.h): part `part` of `parts` workgroups of this world, each running its share of the
+  // frame_skip substeps; the carrier is the world's row of split_rows (the state rows stay untouched until the last part, so a world that exceeds a table is re-run from them as usual).
+  // Written out in this family: the state rows and the carrier publish, as in the hand and Kitchen, and the last part's collect with the cost stamp -- through
+  // grx_split_collect / grx_cost_* the generic lane kernel spills one more VGPR (profiles/kernel_resources_step_frame.txt).
   const bool split = parts > 1, last_part = part == parts - 1;
-  if (split && part > 0) {
-    volatile int* st = b.split_state + 4 * (size_t)w;
-    int v = 0;
-    for (int spins = 0; spins < GRX_SPLIT_SPIN_LIMIT; spins++) {
-      v = __builtin_amdgcn_readfirstlane(st[0]);
-      if (v == part || v < 0) break;
-      __builtin_amdgcn_s_sleep(8);
-    }
-    if (v != part) {   // the earlier part booked the world's re-run (v < 0), or never came (flagged): nothing to do here; the last part leaves the words clean
-      if (lane_ == 0) { if (v >= 0) b.status[w] |= GRX_ST_BADNUM | (GRX_ST_BADNUM << 16); if (last_part) { st[0] = 0; st[1] = 0; st[2] = 0; } }
-      return;
-    }
-    GRX_SPLIT_ACQUIRE();
-  }
+  if (split && part > 0 && !grx_split_wait<3>(b.split_state + 4 * (size_t)w, b.status, w, part, last_part, lane_)) return;
   const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-  if (lane_ == 0) { for (int k = 0; k < GRX_NPROF; k++) prof_s[k] = 0; prof_s[GRX_NPROF] = clock64(); }
-#endif
+  GRX_PROF_BEGIN(c, lane_);
   const int nq = S::kFixed ? S::NQ : m.nq, nv = S::kFixed ? S::NV : m.nv, nu = S::kFixed ? S::NU : m.nu;
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;
   __syncthreads();
@@ -821,7 +629,7 @@ __device__ __forceinline__ void grx_adroit_step_world(int mslot, const GrxAdroit
   int wl;
   if (in_lane) wl = w;
   else if (b.compact) wl = (int)b.compact[blockIdx.x];
-  else { const unsigned bx = grx_block_late(), G = gridDim.x / (unsigned)parts, sl = split ? bx % G : bx; wl = b.order ? b.order[sl] : (int)((sl & 7u) * (G >> 3) + (sl >> 3)); }   // (recomputed, not kept live across the simulation)
+  else wl = grx_slot_world_late(b.order, parts);   // (recomputed, not kept live across the simulation)
   if (split && !last_part) {   // an earlier part: the state goes to the world's carrier row (write-through + drained flag: GRX_SPLIT_DRAIN), nothing else is written
     volatile int* st = b.split_state + 4 * (size_t)wl;
     if (grx_lane_overflowed(c)) { if (lane_ == 0) st[0] = -1; }      // the re-run on the large tables is booked: the later parts return
@@ -854,19 +662,16 @@ __device__ __forceinline__ void grx_adroit_step_world(int mslot, const GrxAdroit
   for (int i = lane_; i < nq; i += 64) b.qpos[(size_t)wl * nq + i] = c.qpos[i];
   for (int i = lane_; i < nv; i += 64) { b.qvel[(size_t)wl * nv + i] = c.qvel[i]; b.qacc_ws[(size_t)wl * nv + i] = c.qacc_ws[i]; }
   if (lane_ == 0) b.status[wl] = grx_status_word(b.status[wl], c.cnt[2]);
-#ifdef GRX_PROFILE
-  GRX_TICK(&c, GRX_P_OTHER);
-  if (lane_ == 0) for (int k = 0; k < GRX_NPROF; k++) atomicAdd((unsigned long long*)&g_grx_prof[k], (unsigned long long)c.prof[k]);
-#endif
+  GRX_PROF_END(c, lane_);
 }
 template <class S>
 __global__ void __launch_bounds__(64, 2)
 grx_adroit_step_kernel(int mslot, GrxAdroitTask t, GrxAdroitBuffers b, int n_worlds, int words, int forward_only) {
   extern __shared__ float lds[];
   const int lane_ = threadIdx.x;
-  const int parts = (b.split_parts > 1 && !b.compact && !forward_only) ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup: grx_world_of_block)
+  const int parts = (b.split_parts > 1 && !b.compact && !forward_only) ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup)
   const unsigned G = gridDim.x / (unsigned)parts, part = blockIdx.x / G, slot = blockIdx.x - part * G;   // slot, slot + G, ... share blockIdx.x mod 8; ONE call site of the step (code size, compile time)
-  const int w = b.compact ? ((int)blockIdx.x < b.n_compact ? (int)b.compact[blockIdx.x] : n_worlds) : (b.order ? b.order[slot] : (int)((slot & 7u) * (G >> 3) + (slot >> 3)));
+  const int w = b.compact ? ((int)blockIdx.x < b.n_compact ? (int)b.compact[blockIdx.x] : n_worlds) : grx_slot_world(b.order, slot, G);
   grx_adroit_step_world<S>(mslot, t, b, w, n_worlds, words, forward_only, lds, lane_, false, (int)part, parts);
   grx_lane_progress(b.lane);
 }
@@ -894,31 +699,14 @@ __device__ __forceinline__ void grx_kitchen_step_world(int mslot, const GrxKitch
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) { if (in_lane) grx_lane_ticket(b.lane, -1, w, lane_); return; }
   if (!in_lane && !forward_only && b.lane.skip && b.lane.skip[w]) return;   // in the overflow lane: stepped by the large-table kernel (reset-time forward passes cover every masked world)
-  // SPLIT STEP (include/grx_capi.h grx_kitchen_buffers.split_parts; see grx_adroit_step_world): part `part` of `parts` workgroups of this world, each running its share of the 40 substeps
+  // SPLIT STEP (include/grx_capi.h grx_kitchen_buffers.split_parts; protocol: grx_step_frame.h): part `part` of `parts` workgroups of this world, each running its share of the 40 substeps
   const bool split = parts > 1, last_part = part == parts - 1;
-  if (split && part > 0) {
-    volatile int* st = b.split_state + 4 * (size_t)w;
-    int v = 0;
-    for (int spins = 0; spins < GRX_SPLIT_SPIN_LIMIT; spins++) {
-      v = __builtin_amdgcn_readfirstlane(st[0]);
-      if (v == part || v < 0) break;
-      __builtin_amdgcn_s_sleep(8);
-    }
-    if (v != part) {   // the earlier part booked the world's re-run (v < 0), or never came (flagged): nothing to do here; the last part leaves the words clean
-      if (lane_ == 0) { if (v >= 0) b.status[w] |= GRX_ST_BADNUM | (GRX_ST_BADNUM << 16); if (last_part) { st[0] = 0; st[1] = 0; st[2] = 0; } }
-      return;
-    }
-    GRX_SPLIT_ACQUIRE();
-  }
+  if (split && part > 0 && !grx_split_wait<3>(b.split_state + 4 * (size_t)w, b.status, w, part, last_part, lane_)) return;
   const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
-#ifdef GRX_PROFILE
-  __shared__ long long prof_s[GRX_NPROF + 1];
-  c.prof = prof_s; c.prof_last = prof_s + GRX_NPROF;
-  if (lane_ == 0) { for (int k = 0; k < GRX_NPROF; k++) prof_s[k] = 0; prof_s[GRX_NPROF] = clock64(); }
-#endif
+  GRX_PROF_BEGIN(c, lane_);
   const int nq = S::kFixed ? S::NQ : m.nq, nv = S::kFixed ? S::NV : m.nv;
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;
   __syncthreads();
@@ -926,7 +714,7 @@ __device__ __forceinline__ void grx_kitchen_step_world(int mslot, const GrxKitch
     volatile const float* row = b.split_rows + (size_t)w * b.split_stride;
     for (int i = lane_; i < nq; i += 64) c.qpos[i] = row[i];
     for (int i = lane_; i < nv; i += 64) { c.qvel[i] = row[nq + i]; c.qacc_ws[i] = row[nq + nv + i]; }
-  } else {
+  } else {   // (written out: with grx_state_load / _store here the register allocation of these kernels moves, profiles/kernel_resources_step_frame.txt)
   for (int i = lane_; i < nq; i += 64) c.qpos[i] = b.qpos[(size_t)w * nq + i];
   for (int i = lane_; i < nv; i += 64) { c.qvel[i] = b.qvel[(size_t)w * nv + i]; c.qacc_ws[i] = b.qacc_ws[(size_t)w * nv + i]; }
   }
@@ -940,11 +728,11 @@ __device__ __forceinline__ void grx_kitchen_step_world(int mslot, const GrxKitch
   }
   grx_lane_setup(b.lane, c, w, !forward_only);
   const bool timed = b.cost && !forward_only && !in_lane;   // cost-ordered dispatch (include/grx_capi.h grx_kitchen_buffers.order / .cost): the start stamp (100 MHz) is parked in the cost slot itself
-  if (timed && lane_ == 0) b.cost[w] = (int)wall_clock64();
+  if (timed) grx_cost_start(b.cost, w, lane_);
   const int s0 = split ? (part * t.n_substeps) / parts : 0, s1 = split ? ((part + 1) * t.n_substeps) / parts : t.n_substeps;
   if (forward_only) GrxEngine<S>::grx_forward_euler(&m, &c, 0, lane_);
   else GrxKitchen<S>::grx_kitchen_sim_world(&m, &t, &c, b.action + (size_t)w * GRX_KITCHEN_NROBOT, last, lane_, s0, s1);
-  if (split && !last_part) {   // an earlier part: the state goes to the world's carrier row (write-through + drained flag: GRX_SPLIT_DRAIN), nothing else is written
+  if (split && !last_part) {   // an earlier part: the state goes to the world's carrier row (written out), nothing else is written
     volatile int* st = b.split_state + 4 * (size_t)w;
     if (grx_lane_overflowed(c)) { if (lane_ == 0) st[0] = -1; }      // the re-run on the large tables is booked: the later parts return
     else {
@@ -963,12 +751,8 @@ __device__ __forceinline__ void grx_kitchen_step_world(int mslot, const GrxKitch
     }
     return;
   }
-  int earlier = 0;
-  if (split) {   // the last part: the flags and the measured time of the earlier parts; the words are clean for the next launch
-    if (lane_ == 0) { volatile int* st = b.split_state + 4 * (size_t)w; c.cnt[2] |= st[1]; earlier = st[2]; st[0] = 0; st[1] = 0; st[2] = 0; }
-    __syncthreads();
-  }
-  if (timed && lane_ == 0) { const int t0 = ((volatile int*)b.cost)[w]; b.cost[w] = (((int)wall_clock64() - t0) >> 3) + earlier; }   // measured duration of this world, 80 ns units (a world that overflowed a table too: it ran up to there)
+  const int earlier = split ? grx_split_collect<3>(c, b.split_state + 4 * (size_t)w, lane_) : 0;   // the last part: the flags and the measured time of the earlier parts
+  if (timed && lane_ == 0) grx_cost_stop(b.cost, w, earlier);   // measured duration of this world, 80 ns units (a world that overflowed a table too: it ran up to there)
   if (grx_lane_overflowed(c)) return;   // capacity overflow: keep nothing (last_qpos included), re-run on the large tables
   if (in_lane) grx_lane_ticket(b.lane, c.cnt[2] & 0xFFFF, w, lane_); else if (!forward_only) grx_lane_join(b.lane, c, w, lane_);
   GrxKitchen<S>::grx_kitchen_outputs(&m, &t, &c, b.noise ? b.noise + (size_t)w * t.obs_dim : nullptr, b.obs + (size_t)w * t.obs_dim, last, b.completed + w, lane_);
@@ -976,9 +760,8 @@ __device__ __forceinline__ void grx_kitchen_step_world(int mslot, const GrxKitch
   for (int i = lane_; i < nq; i += 64) b.qpos[(size_t)w * nq + i] = c.qpos[i];
   for (int i = lane_; i < nv; i += 64) { b.qvel[(size_t)w * nv + i] = c.qvel[i]; b.qacc_ws[(size_t)w * nv + i] = c.qacc_ws[i]; }
   if (lane_ == 0) b.status[w] = grx_status_word(b.status[w], c.cnt[2]);
+  GRX_PROF_END(c, lane_);
 #ifdef GRX_PROFILE
-  GRX_TICK(&c, GRX_P_OTHER);
-  if (lane_ == 0) for (int k = 0; k < GRX_NPROF; k++) atomicAdd((unsigned long long*)&g_grx_prof[k], (unsigned long long)c.prof[k]);
   if (lane_ == 0 && w < 4096 && !forward_only) for (int k = 0; k < GRX_NPROF; k++) g_grx_world_prof[w * GRX_NPROF + k] = (int)c.prof[k];   // per-world rows (tools/straggler_probe.py): lane worlds included
 #endif
 }
@@ -987,9 +770,9 @@ __global__ void __launch_bounds__(64, 2)
 grx_kitchen_step_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_worlds, int words, int forward_only) {
   extern __shared__ float lds[];
   const int lane_ = threadIdx.x;
-  const int parts = (b.split_parts > 1 && !forward_only) ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup: grx_world_of_block)
+  const int parts = (b.split_parts > 1 && !forward_only) ? b.split_parts : 1;      // (one part: G = the grid, part 0, slot = the workgroup)
   const unsigned G = gridDim.x / (unsigned)parts, part = blockIdx.x / G, slot = blockIdx.x - part * G;   // slot, slot + G, ... share blockIdx.x mod 8; ONE call site of the step (code size, compile time)
-  grx_kitchen_step_world<S>(mslot, t, b, b.order ? b.order[slot] : (int)((slot & 7u) * (G >> 3) + (slot >> 3)), n_worlds, words, forward_only, lds, lane_, false, (int)part, parts);
+  grx_kitchen_step_world<S>(mslot, t, b, grx_slot_world(b.order, slot, G), n_worlds, words, forward_only, lds, lane_, false, (int)part, parts);
   grx_lane_progress(b.lane);
 }
 // the large-table kernel of the overflow lane (grx_overflow_lane): a small fixed grid walks the compacted list of worlds; generic shape only
@@ -997,10 +780,7 @@ template <class S>
 __global__ void __launch_bounds__(64, 2)
 grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_worlds, int words) {   // one workgroup per entry of the compacted list (see grx_fetch_lane_kernel)
   extern __shared__ float lds[];
-  const int e = blockIdx.x, nstand = (int)gridDim.x - b.lane.poll_grid;
-  if (e >= nstand) { const int w = grx_lane_poll(b.lane, e - nstand); if (w >= 0) grx_kitchen_step_world<S>(mslot, t, b, w, n_worlds, words, 0, lds, (int)threadIdx.x, true); return; }
-  if (e >= *b.lane.count || grx_lane_taken(b.lane, e)) return;
-  grx_kitchen_step_world<S>(mslot, t, b, b.lane.list[e], n_worlds, words, 0, lds, (int)threadIdx.x, true);
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_kitchen_step_world<S>(mslot, t, b, w, n_worlds, words, 0, lds, (int)threadIdx.x, true); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1020,8 +800,28 @@ static hipError_t grx_raise_lds_limit(const void* fn, int bytes) {
 static hipError_t grx_upload_descriptor(const GrxModel* g, int slot) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), g, sizeof(GrxModel), sizeof(GrxModel) * (size_t)slot, hipMemcpyHostToDevice);
 }
-#define GRX_LDS(KERNEL) do { hipError_t e_ = grx_raise_lds_limit((const void*)(KERNEL), bytes); if (e_ != hipSuccess) return (int)e_; } while (0)
+// The entry points of the family units, declared once for every unit (the API unit calls them; each is defined in the unit that instantiates the family's kernels).
 // grx_tu_*_prepare: returns a hipError_t (0 = ok); *shape <- id of the shape-specialised kernels that serve the model (unchanged if none)
+extern "C" {
+int grx_tu_fetch_prepare(const GrxModel* g, int bytes, int slot, int* shape);
+int grx_tu_point_prepare(const GrxModel* g, int bytes, int slot, int* shape);
+int grx_tu_hand_prepare(const GrxModel* g, int bytes, int slot, int* shape);
+int grx_tu_adroit_prepare(const GrxModel* g, int bytes, int slot, int* shape);
+int grx_tu_kitchen_prepare(const GrxModel* g, int bytes, int slot, int* shape);
+// kind 0: env.step, 1: forward (nstep), 2: compacted reset
+int grx_tu_fetch_launch(int kind, int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxFetchTask* t, const GrxFetchBuffers* b, const GrxFetchResetArgs* r, int n, int words, int nstep);
+int grx_tu_point_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxPointTask* t, const GrxPointBuffers* b, int n, int words);
+int grx_tu_hand_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxHandTask* t, const GrxHandBuffers* b, int n, int words, int forward_only);
+int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxAdroitTask* t, const GrxAdroitBuffers* b, int n, int words, int forward_only);
+int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words, int forward_only);
+}
+// Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
+// overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
+// that matches (`found`); Point, Hand and Kitchen let the LAST match win; a lane shape that matches overrides a step shape, except in Fetch, where it serves only a model that
+// no step shape matched.
+#define GRX_LDS(KERNEL) do { hipError_t e_ = grx_raise_lds_limit((const void*)(KERNEL), bytes); if (e_ != hipSuccess) return (int)e_; } while (0)
+// inside grx_tu_*_launch: KERNEL<SHAPE> on `grid` workgroups of one wavefront, the model's dynamic LDS; the kernel's arguments behind (slot, task, buffers) follow
+#define GRX_LAUNCH_STEP(KERNEL, SHAPE, ...) hipLaunchKernelGGL(KERNEL<SHAPE>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *t, *b, __VA_ARGS__)
 
 #if GRX_TU_FETCH
 #define GRX_FETCH_SHAPES(X) X(1, GrxShapeFetchPick) X(2, GrxShapeFetchObject) X(7, GrxShapeFetchPuck) X(3, GrxShapeFetchArm)
@@ -1033,29 +833,27 @@ extern "C" int grx_tu_fetch_prepare(const GrxModel* g, int bytes, int slot, int*
 #undef X
   if (found == 1) GRX_LDS(grx_fetch_lane_kernel<GrxShapeFetchPick>);   // today's FetchPickAndPlace kernel as the standing lane of the fast one (round 6)
   if (!found && grx_shape_matches<GrxShapeFetchPickFast>(*g)) { found = 8; GRX_LDS(grx_fetch_step_kernel<GrxShapeFetchPickFast>); }   // step kernel only
-  if (!found && grx_shape_matches<GrxShapeFetchPickLane>(*g)) { found = 101; GRX_LDS(grx_fetch_lane_kernel<GrxShapeFetchPickLane>); }   // ids >= 100: lane kernel only (everything else of such a model runs generic)
+  if (!found && grx_shape_matches<GrxShapeFetchPickLane>(*g)) { found = 101; GRX_LDS(grx_fetch_lane_kernel<GrxShapeFetchPickLane>); }
   if (found) *shape = found;
   return (int)grx_upload_descriptor(g, slot);
 }
-// kind 0: env.step, 1: forward (nstep), 2: compacted reset
 extern "C" int grx_tu_fetch_launch(int kind, int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxFetchTask* t, const GrxFetchBuffers* b,
                                    const GrxFetchResetArgs* r, int n, int words, int nstep) {
-  const dim3 g(grid), blk(64); hipStream_t st = (hipStream_t)stream;
   if (kind == 0 && b->lane.list) {
-    if (shape == 101) hipLaunchKernelGGL(grx_fetch_lane_kernel<GrxShapeFetchPickLane>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
-    else if (shape == 1) hipLaunchKernelGGL(grx_fetch_lane_kernel<GrxShapeFetchPick>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
-    else hipLaunchKernelGGL(grx_fetch_lane_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
+    if (shape == 101) GRX_LAUNCH_STEP(grx_fetch_lane_kernel, GrxShapeFetchPickLane, n, words);
+    else if (shape == 1) GRX_LAUNCH_STEP(grx_fetch_lane_kernel, GrxShapeFetchPick, n, words);
+    else GRX_LAUNCH_STEP(grx_fetch_lane_kernel, GrxShapeAny, n, words);
     return (int)hipGetLastError();
   }
   if (shape == 8) {   // the fast FetchPickAndPlace model: its shape exists as a step kernel only
     if (kind != 0) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(grx_fetch_step_kernel<GrxShapeFetchPickFast>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
+    GRX_LAUNCH_STEP(grx_fetch_step_kernel, GrxShapeFetchPickFast, n, words);
     return (int)hipGetLastError();
   }
 #define GRX_FETCH_GO(SHAPE) do { \
-    if (kind == 0) hipLaunchKernelGGL(grx_fetch_step_kernel<SHAPE>, g, blk, lds_bytes, st, slot, *t, *b, n, words); \
-    else if (kind == 1) hipLaunchKernelGGL(grx_fetch_forward_kernel<SHAPE>, g, blk, lds_bytes, st, slot, *t, *b, n, words, nstep); \
-    else hipLaunchKernelGGL(grx_fetch_reset_kernel<SHAPE>, g, blk, lds_bytes, st, slot, *t, *b, *r, n, words); } while (0)
+    if (kind == 0) GRX_LAUNCH_STEP(grx_fetch_step_kernel, SHAPE, n, words); \
+    else if (kind == 1) GRX_LAUNCH_STEP(grx_fetch_forward_kernel, SHAPE, n, words, nstep); \
+    else GRX_LAUNCH_STEP(grx_fetch_reset_kernel, SHAPE, *r, n, words); } while (0)
   switch (shape) {   // the specialised kernels are bit-identical to the generic one (same source, dims folded)
 #define X(ID, SHAPE) case ID: GRX_FETCH_GO(SHAPE); break;
     GRX_FETCH_SHAPES(X)
@@ -1077,12 +875,11 @@ extern "C" int grx_tu_point_prepare(const GrxModel* g, int bytes, int slot, int*
   return (int)grx_upload_descriptor(g, slot);
 }
 extern "C" int grx_tu_point_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxPointTask* t, const GrxPointBuffers* b, int n, int words) {
-  const dim3 g(grid), blk(64); hipStream_t st = (hipStream_t)stream;
   switch (shape) {
-#define X(ID, SHAPE) case ID: hipLaunchKernelGGL(grx_point_step_kernel<SHAPE>, g, blk, lds_bytes, st, slot, *t, *b, n, words); break;
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_point_step_kernel, SHAPE, n, words); break;
     GRX_POINT_SHAPES(X)
 #undef X
-    default: hipLaunchKernelGGL(grx_point_step_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
+    default: GRX_LAUNCH_STEP(grx_point_step_kernel, GrxShapeAny, n, words);
   }
   return (int)hipGetLastError();
 }
@@ -1090,100 +887,108 @@ extern "C" int grx_tu_point_launch(int shape, unsigned grid, size_t lds_bytes, v
 
 #if GRX_TU_HAND
 #define GRX_HAND_SHAPES(X) X(4, GrxShapeHandReach) X(6, GrxShapeHandBlockTouch) X(8, GrxShapeHandEgg) X(9, GrxShapeHandEggTouch) X(5, GrxShapeHandBlock)
+#define GRX_HAND_LANES(X) X(106, GrxShapeHandBlockTouchLane)
 extern "C" int grx_tu_hand_prepare(const GrxModel* g, int bytes, int slot, int* shape) {
   GRX_LDS(grx_hand_step_kernel<GrxShapeAny>); GRX_LDS(grx_hand_lane_kernel<GrxShapeAny>);
 #define X(ID, SHAPE) if (grx_shape_matches<SHAPE>(*g)) { *shape = ID; GRX_LDS(grx_hand_step_kernel<SHAPE>); }
   GRX_HAND_SHAPES(X)
 #undef X
-  if (grx_shape_matches<GrxShapeHandBlockTouchLane>(*g)) { *shape = 106; GRX_LDS(grx_hand_lane_kernel<GrxShapeHandBlockTouchLane>); }   // ids >= 100: lane kernel only
+#define X(ID, SHAPE) if (grx_shape_matches<SHAPE>(*g)) { *shape = ID; GRX_LDS(grx_hand_lane_kernel<SHAPE>); }
+  GRX_HAND_LANES(X)
+#undef X
   return (int)grx_upload_descriptor(g, slot);
 }
 extern "C" int grx_tu_hand_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxHandTask* t, const GrxHandBuffers* b, int n, int words,
                                   int forward_only) {
-  const dim3 g(grid), blk(64); hipStream_t st = (hipStream_t)stream;
   if (b->lane.list) {
-    if (shape == 106) hipLaunchKernelGGL(grx_hand_lane_kernel<GrxShapeHandBlockTouchLane>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
-    else hipLaunchKernelGGL(grx_hand_lane_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
+    switch (shape) {
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_hand_lane_kernel, SHAPE, n, words); break;
+      GRX_HAND_LANES(X)
+#undef X
+      default: GRX_LAUNCH_STEP(grx_hand_lane_kernel, GrxShapeAny, n, words);
+    }
     return (int)hipGetLastError();
   }
   switch (shape) {
-#define X(ID, SHAPE) case ID: hipLaunchKernelGGL(grx_hand_step_kernel<SHAPE>, g, blk, lds_bytes, st, slot, *t, *b, n, words, forward_only); break;
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_hand_step_kernel, SHAPE, n, words, forward_only); break;
     GRX_HAND_SHAPES(X)
 #undef X
-    default: hipLaunchKernelGGL(grx_hand_step_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words, forward_only);
+    default: GRX_LAUNCH_STEP(grx_hand_step_kernel, GrxShapeAny, n, words, forward_only);
   }
   return (int)hipGetLastError();
 }
 #endif
 #if GRX_TU_ADROIT
+#define GRX_ADROIT_SHAPES(X) X(20, GrxShapeAdroitHammer) X(21, GrxShapeAdroitDoor) X(22, GrxShapeAdroitPen) X(23, GrxShapeAdroitRelocate)
+#define GRX_ADROIT_LANES(X) X(121, GrxShapeAdroitDoorLane) X(123, GrxShapeAdroitRelocateLane)
 extern "C" int grx_tu_adroit_prepare(const GrxModel* g, int bytes, int slot, int* shape) {
   GRX_LDS(grx_adroit_step_kernel<GrxShapeAny>); GRX_LDS(grx_adroit_lane_kernel<GrxShapeAny>);
-#define GRX_ADROIT_SHAPES(X) X(20, GrxShapeAdroitHammer) X(21, GrxShapeAdroitDoor) X(22, GrxShapeAdroitPen) X(23, GrxShapeAdroitRelocate)
   int found = 0;
 #define X(ID, SHAPE) if (!found && grx_shape_matches<SHAPE>(*g)) { found = ID; GRX_LDS(grx_adroit_step_kernel<SHAPE>); }
   GRX_ADROIT_SHAPES(X)
 #undef X
   if (found) *shape = found;
-  if (grx_shape_matches<GrxShapeAdroitDoorLane>(*g)) { *shape = 121; GRX_LDS(grx_adroit_lane_kernel<GrxShapeAdroitDoorLane>); }            // ids >= 100: lane kernel only
-  if (grx_shape_matches<GrxShapeAdroitRelocateLane>(*g)) { *shape = 123; GRX_LDS(grx_adroit_lane_kernel<GrxShapeAdroitRelocateLane>); }
+#define X(ID, SHAPE) if (grx_shape_matches<SHAPE>(*g)) { *shape = ID; GRX_LDS(grx_adroit_lane_kernel<SHAPE>); }
+  GRX_ADROIT_LANES(X)
+#undef X
   return (int)grx_upload_descriptor(g, slot);
 }
 extern "C" int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxAdroitTask* t, const GrxAdroitBuffers* b, int n, int words,
                                     int forward_only) {
-  const dim3 g(grid), blk(64); hipStream_t st = (hipStream_t)stream;
   if (b->lane.list) {
-    if (shape == 121) hipLaunchKernelGGL(grx_adroit_lane_kernel<GrxShapeAdroitDoorLane>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
-    else if (shape == 123) hipLaunchKernelGGL(grx_adroit_lane_kernel<GrxShapeAdroitRelocateLane>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
-    else hipLaunchKernelGGL(grx_adroit_lane_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
+    switch (shape) {
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_adroit_lane_kernel, SHAPE, n, words); break;
+      GRX_ADROIT_LANES(X)
+#undef X
+      default: GRX_LAUNCH_STEP(grx_adroit_lane_kernel, GrxShapeAny, n, words);
+    }
     return (int)hipGetLastError();
   }
   switch (shape) {
-#define X(ID, SHAPE) case ID: hipLaunchKernelGGL(grx_adroit_step_kernel<SHAPE>, g, blk, lds_bytes, st, slot, *t, *b, n, words, forward_only); break;
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_adroit_step_kernel, SHAPE, n, words, forward_only); break;
     GRX_ADROIT_SHAPES(X)
 #undef X
-    default: hipLaunchKernelGGL(grx_adroit_step_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words, forward_only);
+    default: GRX_LAUNCH_STEP(grx_adroit_step_kernel, GrxShapeAny, n, words, forward_only);
   }
   return (int)hipGetLastError();
 }
 #endif
 #if GRX_TU_KITCHEN
+#define GRX_KITCHEN_SHAPES(X) X(30, GrxShapeKitchen)
+#define GRX_KITCHEN_LANES(X) X(130, GrxShapeKitchenLane)
 extern "C" int grx_tu_kitchen_prepare(const GrxModel* g, int bytes, int slot, int* shape) {
   GRX_LDS(grx_kitchen_step_kernel<GrxShapeAny>); GRX_LDS(grx_kitchen_lane_kernel<GrxShapeAny>);
-  if (grx_shape_matches<GrxShapeKitchen>(*g)) { *shape = 30; GRX_LDS(grx_kitchen_step_kernel<GrxShapeKitchen>); }
-  if (grx_shape_matches<GrxShapeKitchenLane>(*g)) { *shape = 130; GRX_LDS(grx_kitchen_lane_kernel<GrxShapeKitchenLane>); }   // ids >= 100: lane kernel only
+#define X(ID, SHAPE) if (grx_shape_matches<SHAPE>(*g)) { *shape = ID; GRX_LDS(grx_kitchen_step_kernel<SHAPE>); }
+  GRX_KITCHEN_SHAPES(X)
+#undef X
+#define X(ID, SHAPE) if (grx_shape_matches<SHAPE>(*g)) { *shape = ID; GRX_LDS(grx_kitchen_lane_kernel<SHAPE>); }
+  GRX_KITCHEN_LANES(X)
+#undef X
   return (int)grx_upload_descriptor(g, slot);
 }
 extern "C" int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words,
                                      int forward_only) {
-  const dim3 g(grid), blk(64); hipStream_t st = (hipStream_t)stream;
   if (b->lane.list) {
-    if (shape == 130) hipLaunchKernelGGL(grx_kitchen_lane_kernel<GrxShapeKitchenLane>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
-    else hipLaunchKernelGGL(grx_kitchen_lane_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words);
+    switch (shape) {
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_kitchen_lane_kernel, SHAPE, n, words); break;
+      GRX_KITCHEN_LANES(X)
+#undef X
+      default: GRX_LAUNCH_STEP(grx_kitchen_lane_kernel, GrxShapeAny, n, words);
+    }
     return (int)hipGetLastError();
   }
-  if (shape == 30) hipLaunchKernelGGL(grx_kitchen_step_kernel<GrxShapeKitchen>, g, blk, lds_bytes, st, slot, *t, *b, n, words, forward_only);
-  else hipLaunchKernelGGL(grx_kitchen_step_kernel<GrxShapeAny>, g, blk, lds_bytes, st, slot, *t, *b, n, words, forward_only);
+  switch (shape) {
+#define X(ID, SHAPE) case ID: GRX_LAUNCH_STEP(grx_kitchen_step_kernel, SHAPE, n, words, forward_only); break;
+    GRX_KITCHEN_SHAPES(X)
+#undef X
+    default: GRX_LAUNCH_STEP(grx_kitchen_step_kernel, GrxShapeAny, n, words, forward_only);
+  }
   return (int)hipGetLastError();
 }
 #endif
 #undef GRX_LDS
 
 #if GRX_TU_API
-extern "C" int grx_tu_adroit_prepare(const GrxModel* g, int bytes, int slot, int* shape);
-extern "C" int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxAdroitTask* t, const GrxAdroitBuffers* b, int n, int words,
-                                    int forward_only);
-extern "C" int grx_tu_kitchen_prepare(const GrxModel* g, int bytes, int slot, int* shape);
-extern "C" int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words,
-                                     int forward_only);
-extern "C" int grx_tu_fetch_prepare(const GrxModel* g, int bytes, int slot, int* shape);
-extern "C" int grx_tu_point_prepare(const GrxModel* g, int bytes, int slot, int* shape);
-extern "C" int grx_tu_hand_prepare(const GrxModel* g, int bytes, int slot, int* shape);
-extern "C" int grx_tu_fetch_launch(int kind, int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxFetchTask* t, const GrxFetchBuffers* b,
-                                   const GrxFetchResetArgs* r, int n, int words, int nstep);
-extern "C" int grx_tu_point_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxPointTask* t, const GrxPointBuffers* b, int n, int words);
-extern "C" int grx_tu_hand_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxHandTask* t, const GrxHandBuffers* b, int n, int words,
-                                  int forward_only);
-
 extern "C" __global__ void __launch_bounds__(256)
 grx_goal_reward_kernel(const float* __restrict__ ag, const float* __restrict__ dg, long long B, int dim, double thr, int sparse, float* __restrict__ out) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < B; i += (long long)gridDim.x * blockDim.x)
@@ -1432,6 +1237,22 @@ extern "C" int grx_model_dim(const grx_model* m, const char* name) {
   return -1;
 }
 
+// A split step (grx_*_buffers.split_parts > 1, protocol: grx_step_frame.h) of a launch it applies to (`eligible`; any other launch runs whole: split_parts <- 0): it needs
+// its state words, carrier rows of `need` words where the family has them (need 0: none), and parts that run whole substeps (at most 8: the parts of a world share an XCD).
+// what / limit: the family's wording of the two errors.
+static int grx_split_check(const char* who, int& split_parts, bool eligible, const int* split_state, const float* rows, int stride, int need, int n_substeps, const char* what, const char* limit) {
+  if (split_parts <= 1 || !eligible) { split_parts = 0; return 0; }
+  if (!split_state || (need > 0 && (!rows || stride < need))) return fail(std::string(who) + ": a split step needs " + what);
+  if (split_parts > n_substeps || split_parts > 8) return fail(std::string(who) + ": split_parts <= " + limit);
+  return 0;
+}
+// workgroups of a step launch: the lane's grid for a lane launch, one per entry of a compacted launch (compact_n > 0), else one per world (rounded up to the 8 XCDs) and part
+static unsigned grx_step_grid(const GrxLane& lane, int compact_n, int split_parts, int n_worlds) {
+  if (lane.list) return (unsigned)(lane.grid > 0 ? lane.grid : GRX_LANE_GRID);
+  if (compact_n > 0) return (unsigned)compact_n;
+  return (split_parts > 1 ? (unsigned)split_parts : 1u) * grx_grid_for(n_worlds);
+}
+
 static int check_buffers(const grx_fetch_buffers* b) {
   if (!b || !b->qpos || !b->qvel || !b->qacc_ws || !b->mocap || !b->aux || !b->goal || !b->obs || !b->achieved || !b->reward ||
       !b->success || !b->status)
@@ -1449,13 +1270,10 @@ extern "C" int grx_fetch_step(const grx_model* m, const grx_fetch_task* task, co
   if (b.lane.list && m->shape != 0 && m->shape != 1 && m->shape < 100) return fail("grx_fetch_step: a lane launch needs a model with a lane kernel (the generic kernel, FetchPickAndPlace's own shape, or its large-table shape)");
   if (m->shape == 8 && !(b.handoff && b.lane.entry_count && b.lane.entry_list && b.handoff_stride >= grx_handoff_words(m->dev.nq, m->dev.nv, m->dev.nu, m->dev.nmocap)))
     return fail("grx_fetch_step: the fast FetchPickAndPlace kernel carries no hull routine: it needs hand-off rows (handoff, handoff_stride) and an entry list to hand hull worlds to");
-  if (b.split_parts > 1) {
-    if (b.lane.list || m->shape == 8) return fail("grx_fetch_step: split_parts applies to the step launch of a full kernel (not to a lane launch, not to the hull-less fast kernel)");
-    if (!b.split_state || !b.handoff || b.handoff_stride < grx_handoff_words(m->dev.nq, m->dev.nv, m->dev.nu, m->dev.nmocap)) return fail("grx_fetch_step: a split step needs split_state [N, 2] and hand-off rows (handoff, handoff_stride) as carrier");
-    if (b.split_parts > 8) return fail("grx_fetch_step: split_parts <= 8");
-  } else b.split_parts = 0;
-  const unsigned split_mul = b.split_parts > 1 ? (unsigned)b.split_parts : 1u;
-  const int e = grx_tu_fetch_launch(0, m->shape, (b.lane.list ? (unsigned)(b.lane.grid > 0 ? b.lane.grid : GRX_LANE_GRID) : split_mul * grx_grid_for(n_worlds)), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, nullptr, n_worlds, m->words, 0);
+  if (b.split_parts > 1 && (b.lane.list || m->shape == 8)) return fail("grx_fetch_step: split_parts applies to the step launch of a full kernel (not to a lane launch, not to the hull-less fast kernel)");
+  if (grx_split_check("grx_fetch_step", b.split_parts, true, b.split_state, b.handoff, b.handoff_stride, grx_handoff_words(m->dev.nq, m->dev.nv, m->dev.nu, m->dev.nmocap), 8,
+                      "split_state [N, 2] and hand-off rows (handoff, handoff_stride) as carrier", "8")) return -1;
+  const int e = grx_tu_fetch_launch(0, m->shape, grx_step_grid(b.lane, 0, b.split_parts, n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, nullptr, n_worlds, m->words, 0);
   if (e) return fail(std::string("grx_fetch_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -1494,11 +1312,8 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
   if (n_worlds <= 0) return 0;
   GrxPointTask t; memcpy(&t, task, sizeof(t));
   GrxPointBuffers b; memcpy(&b, buf, sizeof(b));
-  if (b.split_parts > 1) {
-    if (!b.split_state) return fail("grx_point_step: a split step needs split_state [N, 2]");
-    if (b.split_parts > t.n_substeps || b.split_parts > 8) return fail("grx_point_step: split_parts <= min(frame_skip, 8): a part runs whole substeps");
-  } else b.split_parts = 0;
-  const int e = grx_tu_point_launch(m->shape, (b.split_parts > 1 ? (unsigned)b.split_parts : 1u) * grx_grid_for(n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words);
+  if (grx_split_check("grx_point_step", b.split_parts, true, b.split_state, nullptr, 0, 0, t.n_substeps, "split_state [N, 2]", "min(frame_skip, 8): a part runs whole substeps")) return -1;
+  const int e = grx_tu_point_launch(m->shape, grx_step_grid(GrxLane{}, 0, b.split_parts, n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words);
   if (e) return fail(std::string("grx_point_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -1519,12 +1334,9 @@ extern "C" int grx_hand_step(const grx_model* m, const grx_hand_task* task, cons
     for (int k = 0; k < GRX_HAND_NTIPS; k++) if (t.site[k] < 0 || t.site[k] >= m->dev.nsite) return fail("grx_hand_step: fingertip site out of range");
   if (t.palm_body < 0 || t.palm_body >= m->dev.nbody) return fail("grx_hand_step: palm body out of range");
   if (b.lane.list && m->shape != 0 && m->shape < 100) return fail("grx_hand_step: the large-table launch of the overflow lane needs a model that runs on the generic kernel (capacities that match no specialised shape)");
-  const bool split = b.split_parts > 1 && forward_only == 0 && !b.lane.list;      // plain step launches only (not forward-only, not a repeat launch, not the lane's)
-  if (split) {
-    if (!b.split_state || !b.split_rows || b.split_stride < m->dev.nq + 2 * m->dev.nv) return fail("grx_hand_step: a split step needs split_state [N, 4] and carrier rows split_rows [N, split_stride >= nq + 2 nv]");
-    if (b.split_parts > t.n_substeps || b.split_parts > 8) return fail("grx_hand_step: split_parts <= min(n_substeps, 8): a part runs whole substeps");
-  } else b.split_parts = 0;
-  const int e = grx_tu_hand_launch(m->shape, (b.lane.list ? (unsigned)(b.lane.grid > 0 ? b.lane.grid : GRX_LANE_GRID) : (split ? (unsigned)b.split_parts : 1u) * grx_grid_for(n_worlds)), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words, forward_only);
+  if (grx_split_check("grx_hand_step", b.split_parts, forward_only == 0 && !b.lane.list, b.split_state, b.split_rows, b.split_stride, m->dev.nq + 2 * m->dev.nv, t.n_substeps,   // plain step launches only (not forward-only, not a repeat launch, not the lane's)
+                      "split_state [N, 4] and carrier rows split_rows [N, split_stride >= nq + 2 nv]", "min(n_substeps, 8): a part runs whole substeps")) return -1;
+  const int e = grx_tu_hand_launch(m->shape, grx_step_grid(b.lane, 0, b.split_parts, n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words, forward_only);
   if (e) return fail(std::string("grx_hand_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -1557,12 +1369,9 @@ extern "C" int grx_adroit_step(const grx_model* m, const grx_adroit_task* task, 
   if (t.kind == GRX_ADROIT_RELOCATE && !buf->target) return fail("grx_adroit_step: the relocate task needs the target buffer");
   if (b.lane.list && m->shape != 0 && m->shape < 100) return fail("grx_adroit_step: the large-table launch of the overflow lane needs a model that runs on the generic kernel (capacities that match no specialised shape)");
   if (b.compact && (b.n_compact <= 0 || b.lane.list)) return fail("grx_adroit_step: a compacted launch needs n_compact > 0 and is not a lane launch");
-  const bool split = b.split_parts > 1 && !b.compact && !forward_only && !b.lane.list;      // step launches only
-  if (split) {
-    if (!b.split_state || !b.split_rows || b.split_stride < m->dev.nq + 2 * m->dev.nv) return fail("grx_adroit_step: a split step needs split_state [N, 4] and carrier rows split_rows [N, split_stride >= nq + 2 nv]");
-    if (b.split_parts > t.n_substeps || b.split_parts > 8) return fail("grx_adroit_step: split_parts <= min(frame_skip, 8): a part runs whole substeps");
-  } else b.split_parts = 0;
-  const int e = grx_tu_adroit_launch(m->shape, (b.lane.list ? (unsigned)(b.lane.grid > 0 ? b.lane.grid : GRX_LANE_GRID) : (b.compact ? (unsigned)b.n_compact : (split ? (unsigned)b.split_parts : 1u) * grx_grid_for(n_worlds))), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words, forward_only);
+  if (grx_split_check("grx_adroit_step", b.split_parts, !b.compact && !forward_only && !b.lane.list, b.split_state, b.split_rows, b.split_stride, g.nq + 2 * g.nv, t.n_substeps,   // step launches only
+                      "split_state [N, 4] and carrier rows split_rows [N, split_stride >= nq + 2 nv]", "min(frame_skip, 8): a part runs whole substeps")) return -1;
+  const int e = grx_tu_adroit_launch(m->shape, grx_step_grid(b.lane, b.compact ? b.n_compact : 0, b.split_parts, n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words, forward_only);
   if (e) return fail(std::string("grx_adroit_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
@@ -1602,12 +1411,9 @@ extern "C" int grx_kitchen_step(const grx_model* m, const grx_kitchen_task* task
     if (!grx_planes_static(m)) return fail("grx_kitchen_step: the skin list needs static plane geoms");
   }
   if (b.lane.list && m->shape != 0 && m->shape < 100) return fail("grx_kitchen_step: the large-table launch of the overflow lane needs a model that runs on the generic kernel (capacities that match no specialised shape)");
-  const bool split = b.split_parts > 1 && !forward_only && !b.lane.list;      // step launches only
-  if (split) {
-    if (!b.split_state || !b.split_rows || b.split_stride < g.nq + 2 * g.nv) return fail("grx_kitchen_step: a split step needs split_state [N, 4] and carrier rows split_rows [N, split_stride >= nq + 2 nv]");
-    if (b.split_parts > t.n_substeps || b.split_parts > 8) return fail("grx_kitchen_step: split_parts <= min(n_substeps, 8): a part runs whole substeps");
-  } else b.split_parts = 0;
-  const int e = grx_tu_kitchen_launch(m->shape, (b.lane.list ? (unsigned)(b.lane.grid > 0 ? b.lane.grid : GRX_LANE_GRID) : (split ? (unsigned)b.split_parts : 1u) * grx_grid_for(n_worlds)), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words, forward_only);
+  if (grx_split_check("grx_kitchen_step", b.split_parts, !forward_only && !b.lane.list, b.split_state, b.split_rows, b.split_stride, g.nq + 2 * g.nv, t.n_substeps,   // step launches only
+                      "split_state [N, 4] and carrier rows split_rows [N, split_stride >= nq + 2 nv]", "min(n_substeps, 8): a part runs whole substeps")) return -1;
+  const int e = grx_tu_kitchen_launch(m->shape, grx_step_grid(b.lane, 0, b.split_parts, n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &t, &b, n_worlds, m->words, forward_only);
   if (e) return fail(std::string("grx_kitchen_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
