@@ -128,8 +128,12 @@ GRX_MEM void grx_capsule_capsule(const GrxModel* m, GrxCtx* c, int pair, int g1,
   const float* c1 = c->gxpos + 3 * g1; const float* R1 = c->gxmat + 9 * g1; const float* c2 = c->gxpos + 3 * g2; const float* R2 = c->gxmat + 9 * g2;
   const float r1 = m->geom_size[3 * g1], h1 = m->geom_size[3 * g1 + 1], r2 = m->geom_size[3 * g2], h2 = m->geom_size[3 * g2 + 1];
   const float a1[3] = {R1[2], R1[5], R1[8]}, a2[3] = {R2[2], R2[5], R2[8]}, w[3] = {c1[0] - c2[0], c1[1] - c2[1], c1[2] - c2[2]};
-  const float b = dot3f(a1, a2), d = dot3f(a1, w), e = dot3f(a2, w), den = 1.0f - b * b;
-  float x1 = den > GRX_MINVAL ? (b * e - d) / den : 0.0f;
+  // den = 1 - b^2 = |a1 x a2|^2 and b e - d = -(a2 x (a1 x a2)) . w, both through the cross product: in fp32 1 - b * b carries an absolute error of 1e-7, which IS den
+  // at 3e-4 rad between the axes (b even rounds to 1), and such a pair got the contact of the parallel branch, mid-capsule, instead of the clamped end the closest
+  // points are at; the cross product keeps a relative error of 1e-7 / |a1 x a2|
+  float cr[3], pa[3]; cross3f(cr, a1, a2); cross3f(pa, a2, cr);
+  const float b = dot3f(a1, a2), d = dot3f(a1, w), e = dot3f(a2, w), den = dot3f(cr, cr);
+  float x1 = den > GRX_MINVAL ? -dot3f(pa, w) / den : 0.0f;
   x1 = fminf(h1, fmaxf(-h1, x1));
   float x2 = b * x1 + e;
   if (x2 > h2) { x2 = h2; x1 = fminf(h1, fmaxf(-h1, b * x2 - d)); }

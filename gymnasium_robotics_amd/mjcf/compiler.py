@@ -575,6 +575,10 @@ class MjcfCompiler:
         else:
             a = self._attrs(elem, "joint", childclass)
         jt = JNT_TYPES[a.get("type", "hinge")]
+        if jt == JNT_BALL:
+            # the tables below size a ball joint (4 qpos, 3 dofs), but neither the engine nor the oracle has one: kinematics, integrator and limit rows know free, slide
+            # and hinge only and would move the quaternion's first word like a slide coordinate
+            raise NotImplementedError("ball joints: the engine and the oracle have free, slide and hinge joints only")
         ang = self.angle_scale if jt in (JNT_HINGE, JNT_BALL) else 1.0
         rng = _floats(a.get("range"), 2, [0, 0])
         if "limited" in a and a["limited"] != "auto":
