@@ -177,6 +177,12 @@ def lib():
         L.grx_maze_sample_resets_device.argtypes = [vp, vp, ci, vp, ci, vp, ci, cd, cd, vp, vp, vp, vp]
         L.grx_maze_sample_resets_list.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, cd, cd, vp, vp]
         L.grx_maze_reset_rows_list.argtypes = [vp, vp, ci, vp, vp]
+        L.grx_normstat_geometry.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.grx_normstat_layout.argtypes = [ci, ci, ctypes.POINTER(ctypes.c_int64)]
+        L.grx_normstat_update.argtypes = [vp, vp, ctypes.c_int64, ci, ci, ci, vp, cd, vp]
+        L.grx_normstat_refresh.argtypes = [vp, ci, ci, cd, vp]
+        L.grx_normstat_apply_batch.argtypes = [vp, vp, ctypes.c_int64, ci, ci, ci, ci, ctypes.c_float, vp, vp]
+        L.grx_normstat_apply_packed.argtypes = [vp, vp, ctypes.c_int64, ci, ci, ci, ctypes.c_float, vp, vp]
         _lib = L
     return _lib
 
@@ -212,6 +218,7 @@ def check(rc: int):
 EXPORTED_SYMBOLS = [
     "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_dim",
     "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
+    "grx_normstat_geometry", "grx_normstat_layout", "grx_normstat_update", "grx_normstat_refresh", "grx_normstat_apply_batch", "grx_normstat_apply_packed",
 ]
 
 

@@ -31,6 +31,7 @@
 #include "grx_env.h"
 #include "grx_replay.h"
 #include "grx_episodes.h"
+#include "grx_norm.h"
 #include "grx_copy.h"
 
 namespace {
@@ -286,6 +287,7 @@ struct grx_env {
   // for an attached replay (grx_env_replay.inc): the worlds whose packed row of the last step is the first row of a new episode, as a device index list -- its length on
   // the host, or in device memory where step_count_dev is set -- and the counts of step / reset + set_state calls that order the replay's calls against the handle's
   grx_replay* replay = nullptr;
+  grx_norm* norm = nullptr;      // the attached normalizer (grx_env_norm.inc), or none
   const int* step_list = nullptr;
   const int* step_count_dev = nullptr;
   int step_count = 0;
@@ -639,6 +641,7 @@ extern "C" int grx_env_create(const char* desc_path, int num_envs, int device, c
 extern "C" int grx_env_destroy(grx_env* e) {
   if (!e) return fail(GRX_ENV_EINVAL, "grx_env_destroy: NULL handle");
   if (e->replay) return fail(GRX_ENV_EINVAL, "grx_env_destroy: a replay is attached to the handle: grx_replay_destroy first");
+  if (e->norm) return fail(GRX_ENV_EINVAL, "grx_env_destroy: a normalizer is attached to the handle: grx_norm_destroy first");
   delete e;
   return 0;
 }
@@ -902,3 +905,4 @@ extern "C" int grx_env_set_state(grx_env* e, const void* host, size_t bytes) {
 
 #include "grx_env_replay.inc"
 #include "grx_env_episodes.inc"
+#include "grx_env_norm.inc"

@@ -2582,4 +2582,7 @@ extern "C" int grx_maze_reset_rows_list(const grx_maze_reset_args* args, const i
   return 0;
 }
 
+// running observation / goal statistics of HER batches and their application (grx_normstat_*)
+#include "grx_normstat.h"
+
 #endif  // GRX_TU_API

@@ -6,7 +6,8 @@
 writes the environment description file grx_env_create reads.  The file is built from the packaged model (models/*.npz) alone:
 no GPU, no asset tree.  This module also holds the ctypes loader of libgrx_env.so, struct mirrors of grx_env.h and a parser of the
 section tables both files use, and the struct mirrors of grx_replay.h (the HER replay attached to a handle: ReplayConfig, ReplayBatch) and of grx_episodes.h (the
-store of finished episodes attached to a replay: EpisodesConfig, EpisodesBatch).
+store of finished episodes attached to a replay: EpisodesConfig, EpisodesBatch) and of grx_norm.h (the observation / goal normalizer attached to a handle: NormConfig,
+NormStateHeader and the helpers of its state blob).
 
 Container (little endian; the description file and the state blob of grx_env_get_state share it):
 
@@ -54,6 +55,7 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libgrx_env.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_env.h")
 REPLAY_HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_replay.h")
 EPISODES_HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_episodes.h")
+NORM_HEADER_PATH = os.path.join(_HERE, "..", "include", "grx_norm.h")
 _lib = None
 
 AUTORESET = {"next_step": 0, "same_step": 1, "disabled": 2}
@@ -248,6 +250,49 @@ class EpisodesBatch(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_void_p), ("batch", ctypes.c_int64), ("valid", ctypes.c_void_p)]
 
 
+# ------------------------------------------------------------------ grx_norm.h mirrors
+NORM_MAGIC, NORM_VERSION = b"GRXNORM\0", 1
+
+
+class NormConfig(ctypes.Structure):
+    _fields_ = [("eps", ctypes.c_double), ("clip", ctypes.c_float)]
+
+
+class NormStateHeader(ctypes.Structure):
+    """the first 40 bytes of a grx_norm_get_state blob; sum[D] f64, sumsq[D] f64, count i64, skipped i64 follow (D = obs_dim + goal_dim)"""
+    _fields_ = [("magic", ctypes.c_char * 8), ("version", ctypes.c_uint32), ("obs_dim", ctypes.c_int32), ("goal_dim", ctypes.c_int32), ("zero0", ctypes.c_uint32),
+                ("eps", ctypes.c_double), ("clip", ctypes.c_float), ("zero1", ctypes.c_uint32)]
+
+
+def norm_state_size(obs_dim, goal_dim):
+    return ctypes.sizeof(NormStateHeader) + 16 * (obs_dim + goal_dim) + 16
+
+
+def pack_norm_state(obs_dim, goal_dim, eps, clip, total, sumsq, count, skipped):
+    """the blob grx_norm_set_state reads (her.Normalizer.state_dict holds the same fields)"""
+    D = obs_dim + goal_dim
+    total, sumsq = np.ascontiguousarray(total, np.float64).reshape(D), np.ascontiguousarray(sumsq, np.float64).reshape(D)
+    h = NormStateHeader(NORM_MAGIC, NORM_VERSION, obs_dim, goal_dim, 0, float(eps), float(clip), 0)
+    return bytes(h) + total.tobytes() + sumsq.tobytes() + struct.pack("<qq", int(count), int(skipped))
+
+
+def parse_norm_state(blob):
+    """-> dict(obs_dim, goal_dim, eps, clip, sum, sumsq, count, skipped) of a grx_norm_get_state blob"""
+    blob = bytes(blob)
+    hs = ctypes.sizeof(NormStateHeader)
+    if len(blob) < hs:
+        raise ValueError("normalizer state blob shorter than its header")
+    h = NormStateHeader.from_buffer_copy(blob[:hs])
+    if bytes(h.magic).ljust(8, b"\0") != NORM_MAGIC or h.version != NORM_VERSION:
+        raise ValueError("not a version-1 normalizer state blob")
+    D = h.obs_dim + h.goal_dim
+    if len(blob) != norm_state_size(h.obs_dim, h.goal_dim):
+        raise ValueError(f"normalizer state blob of {len(blob)} bytes, expected {norm_state_size(h.obs_dim, h.goal_dim)}")
+    count, skipped = struct.unpack_from("<qq", blob, hs + 16 * D)
+    return dict(obs_dim=h.obs_dim, goal_dim=h.goal_dim, eps=h.eps, clip=h.clip, sum=np.frombuffer(blob, np.float64, D, hs).copy(),
+                sumsq=np.frombuffer(blob, np.float64, D, hs + 8 * D).copy(), count=count, skipped=skipped)
+
+
 def lib():
     """libgrx_env.so with its argument types (loads libgrx_hip.so first, through the package loader: one HIP runtime, the one torch uses)"""
     global _lib
@@ -287,6 +332,16 @@ def lib():
         L.grx_episodes_sample.argtypes = [vp, i64, ci, ci, P(EpisodesBatch), vp]
         L.grx_episodes_reseed.argtypes = [vp, u64]
         L.grx_episodes_store.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(i64)]
+        L.grx_norm_create.argtypes = [vp, P(NormConfig), P(vp)]
+        L.grx_norm_destroy.argtypes = [vp]
+        L.grx_norm_dims.argtypes = [vp, P(ci), P(ci), P(ci), P(ci)]
+        L.grx_norm_update.argtypes = [vp, vp, i64, vp, vp]
+        L.grx_norm_apply_batch.argtypes = [vp, vp, i64, vp, vp]
+        L.grx_norm_policy_input.argtypes = [vp, P(vp), vp]
+        L.grx_norm_stats.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(ci)]
+        L.grx_norm_state_size.argtypes = [vp, P(ctypes.c_size_t)]
+        L.grx_norm_get_state.argtypes = [vp, vp, ctypes.c_size_t]
+        L.grx_norm_set_state.argtypes = [vp, vp, ctypes.c_size_t]
         _lib = L
     return _lib
 

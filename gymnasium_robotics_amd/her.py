@@ -355,3 +355,118 @@ class EpisodicHerReplay(HerReplay):
     def store_views(self):
         """(rows [E, T+1, W], actions [E, T+1, act_dim], meta [E, 4] int32 = {len, world, first_row, 0}, count [1] int64): the device tensors of the store"""
         return self.ep_rows, self.ep_acts, self.ep_meta, self.ep_count
+
+
+class Normalizer:
+    """Running per-component mean and standard deviation of observations and goals, kept on the device from relabelled HER batches, and their application -- the
+    normaliser of the DDPG + HER recipe (Andrychowicz et al. 2017; Plappert et al. 2018): (x - mean) / std clipped to +-clip.
+
+        norm = Normalizer(buf)                       # a HerReplay / EpisodicHerReplay, or the environment itself
+        rows = buf.relabel(batch=256)
+        norm.update(rows)                            # obs_t and the relabelled goal of every row -> fp64 sums; mean / inv_std refreshed (two launches)
+        x = norm.normalize(rows)                     # obs and goal columns normalised, action / reward / success copied (one launch; out=rows: in place)
+        actor_in = norm.policy_input(env.packed)     # [N, obs_dim + goal_dim] = [norm(obs) | norm(desired)]
+
+    A thin caller of the grx_normstat entry points of libgrx_hip.so (include/grx_capi.h), which define the arithmetic: sums in fp64 in a fixed order with no floating-point
+    atomics (bit-identical from run to run), a row with a non-finite tracked value skipped and counted, a NaN input staying a NaN.  `valid` is the device word of a C-side
+    batch (grx_replay_batch.valid): zero means "this slot holds nothing" and is read by the kernels."""
+
+    def __init__(self, replay_or_env, eps: float = 1e-2, clip: float = 5.0):
+        src = replay_or_env
+        if isinstance(src, HerReplay):
+            self.device, self.obs_dim, self.goal_dim, self.act_dim, self.W = src.device, src.obs_dim, src.goal_dim, src.act_dim, src.W
+        else:
+            self.device, self.W = src.device, int(src.packed.shape[1])
+            self.goal_dim = int(src.single_observation_space["desired_goal"].shape[0])
+            self.obs_dim = self.W - 2 * self.goal_dim - 2
+            self.act_dim = int(src.single_action_space.shape[0])
+        if not (eps > 0 and clip > 0):
+            raise ValueError("eps and clip must be positive")
+        self.eps, self.clip = float(eps), float(clip)
+        self.D = self.obs_dim + self.goal_dim
+        self.OW = 2 * self.obs_dim + 3 * self.goal_dim + self.act_dim + 2
+        self._L = _native.lib()
+        lay = (ctypes.c_int64 * 8)()
+        _native.check(self._L.grx_normstat_layout(self.obs_dim, self.goal_dim, lay))
+        self._block = torch.zeros(int(lay[7]), dtype=torch.uint8, device=self.device)      # the stat block: statistics, then the update's workspace
+        view = lambda off, n, size, dtype: self._block[int(off): int(off) + n * size].view(dtype)
+        self.sum, self.sumsq = view(lay[0], self.D, 8, torch.float64), view(lay[1], self.D, 8, torch.float64)
+        self._count, self._skipped = view(lay[2], 1, 8, torch.int64), view(lay[3], 1, 8, torch.int64)
+        self.mean, self.inv_std = view(lay[4], self.D, 4, torch.float32), view(lay[5], self.D, 4, torch.float32)
+        self._refresh()
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _refresh(self):
+        _native.check(self._L.grx_normstat_refresh(self._block.data_ptr(), self.obs_dim, self.goal_dim, self.eps, self._stream()))
+
+    def _check_rows(self, rows, width, what):
+        if not (rows.dim() == 2 and rows.shape[1] == width and rows.dtype == torch.float32 and rows.is_contiguous() and rows.device == self._block.device):
+            raise ValueError(f"{what}: a contiguous float32 [batch, {width}] tensor on {self._block.device} is expected")
+
+    def update(self, rows: torch.Tensor, valid: Optional[torch.Tensor] = None):
+        """add replay rows [batch, OW] to the statistics; valid: None or a device int32 [1] whose zero means "nothing in this slot" (decided by the kernels)"""
+        self._check_rows(rows, self.OW, "update")
+        if len(rows) == 0:      # the empty view of HerReplay.relabel when nothing can be sampled
+            return
+        if valid is not None and not (valid.dtype == torch.int32 and valid.numel() >= 1 and valid.device == self._block.device):
+            raise ValueError("update: valid is a device int32 [1] tensor")
+        _native.check(self._L.grx_normstat_update(self._block.data_ptr(), rows.data_ptr(), len(rows), self.OW, self.obs_dim, self.goal_dim,
+                                                  valid.data_ptr() if valid is not None else None, self.eps, self._stream()))
+
+    def normalize(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """replay rows with the observation and goal columns normalised and clipped, the others copied; out=rows normalises in place"""
+        self._check_rows(rows, self.OW, "normalize")
+        if out is None:
+            out = torch.empty_like(rows)
+        self._check_rows(out, self.OW, "normalize(out=)")
+        if out.shape != rows.shape:
+            raise ValueError("normalize: out has another batch size")
+        if len(rows):
+            _native.check(self._L.grx_normstat_apply_batch(self._block.data_ptr(), rows.data_ptr(), len(rows), self.OW, self.obs_dim, self.goal_dim, self.act_dim, self.clip,
+                                                           out.data_ptr(), self._stream()))
+        return out
+
+    def policy_input(self, packed: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[n, obs_dim + goal_dim] = [norm(obs) | norm(desired)] of packed environment rows (env.packed)"""
+        self._check_rows(packed, self.W, "policy_input")
+        if out is None:
+            out = torch.empty(len(packed), self.D, dtype=torch.float32, device=self.device)
+        self._check_rows(out, self.D, "policy_input(out=)")
+        if len(out) != len(packed):
+            raise ValueError("policy_input: out has another number of rows")
+        if len(packed):
+            _native.check(self._L.grx_normstat_apply_packed(self._block.data_ptr(), packed.data_ptr(), len(packed), self.W, self.obs_dim, self.goal_dim, self.clip,
+                                                            out.data_ptr(), self._stream()))
+        return out
+
+    @property
+    def std(self) -> torch.Tensor:
+        return 1.0 / self.inv_std
+
+    @property
+    def count(self) -> int:
+        """rows counted so far (reads the device word: waits for the stream)"""
+        return int(self._count.item())
+
+    @property
+    def skipped(self) -> int:
+        """rows left out because a tracked value was not finite (reads the device word)"""
+        return int(self._skipped.item())
+
+    def state_dict(self) -> dict:
+        """what a resumed run needs: the fields of the C ABI's state blob (env_capi.pack_norm_state)"""
+        return dict(obs_dim=self.obs_dim, goal_dim=self.goal_dim, eps=self.eps, clip=self.clip, sum=self.sum.cpu(), sumsq=self.sumsq.cpu(), count=self.count, skipped=self.skipped)
+
+    def load_state_dict(self, state: dict):
+        if (int(state["obs_dim"]), int(state["goal_dim"])) != (self.obs_dim, self.goal_dim):
+            raise ValueError(f"state of dimensions ({state['obs_dim']}, {state['goal_dim']}), normalizer of ({self.obs_dim}, {self.goal_dim})")
+        if not (state["eps"] > 0 and state["clip"] > 0):
+            raise ValueError("eps and clip must be positive")
+        self.eps, self.clip = float(state["eps"]), float(state["clip"])
+        self.sum.copy_(torch.as_tensor(state["sum"], dtype=torch.float64).reshape(self.D))
+        self.sumsq.copy_(torch.as_tensor(state["sumsq"], dtype=torch.float64).reshape(self.D))
+        self._count.fill_(int(state["count"]))
+        self._skipped.fill_(int(state["skipped"]))
+        self._refresh()      # mean / inv_std by the refresh code of update

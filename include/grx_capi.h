@@ -618,6 +618,35 @@ int grx_maze_sample_resets_device(uint64_t* states, const int* idx, int n, const
 /* The same draws for a list whose LENGTH is in device memory (count [1]; see grx_maze_episode_end): max_n bounds the grid, entries at or beyond *count draw nothing. */
 int grx_maze_sample_resets_list(uint64_t* states, const int* idx, const int* count, int max_n, const double* goal_xy, int n_goal, const double* reset_xy, int n_reset,
                                 double noise_range, double scaling, float* stage, void* stream);
+
+/* Running observation / goal statistics of HER batches and their application -- the normaliser of the DDPG + HER recipe (Andrychowicz et al. 2017; Plappert et al. 2018):
+ * per-component mean and standard deviation kept from the relabelled transitions, normalised values clipped.  The env-level calls of include/grx_norm.h are thin callers
+ * of these; the prefix differs (normstat) because both libraries are loaded into one process.
+ *
+ * A stat block for (obs_dim, goal_dim), D = obs_dim + goal_dim <= 256 columns, is ONE zero-filled device allocation of layout[7] bytes, 16-byte aligned, holding
+ *     sum[D] f64 | sumsq[D] f64 | count[1] i64 | skipped[1] i64 | mean[D] f32 | inv_std[D] f32 | the update's workspace
+ * at the byte offsets layout[0..5] (layout[6]: bytes up to the workspace).  Columns 0 .. obs_dim-1 are the observation statistics, the rest the goal statistics.
+ * Of a replay row [obs_t | achieved_t | goal | action_t | reward | obs_t+1 | achieved_t+1 | success] the update tracks obs_t and the relabelled goal.
+ *
+ * update: the rows are summed in fp64 (each fp32 value converted, its square formed in fp64, where it is exact).  A row with a non-finite value in a tracked column
+ * contributes to no column and adds one to skipped; other columns are not looked at.  valid: device int32[1] or NULL; valid[0] == 0 leaves the whole block unchanged --
+ * the zero-filled slot of grx_her_sample_relabel / grx_her_episode_sample -- and is read on the device.  No floating-point atomics: chunk k of rows_per_group rows goes
+ * to workgroup k % max_groups, a workgroup sums its chunks in ascending order, the partial sums are added in a fixed order by a second one-workgroup launch, so the result
+ * is bit-identical from run to run.  That launch then refreshes, in fp64, mean = sum / count, var = sumsq / count - mean^2, std = sqrt(max(eps^2, var)), and stores mean
+ * and 1 / std rounded to fp32 (count == 0: mean 0, inv_std 1).  refresh: that last step alone -- once after the allocation was zero-filled (inv_std 1, not 0, before
+ * the first batch) and after the sums were written by a copy (a restored checkpoint).  Rows may start at any 4-byte boundary; row_width <= 8192.
+ *
+ * apply: y = (x - mean[c]) * inv_std[c] in fp32 in that order, then clipped to [-clip, clip]; a NaN stays a NaN, +-inf clips.  apply_batch writes out [batch, row_width]
+ * (out == rows allowed; row_width = 2 obs_dim + 3 goal_dim + act_dim + 2 <= 4096): obs_t and obs_t+1 with the observation statistics, achieved_t, goal and achieved_t+1
+ * with the goal statistics, action / reward / success copied.  apply_packed writes out [n, D] = [norm(obs) | norm(desired)] from packed env rows
+ * [obs | achieved | desired | reward | success] of width packed_width: the actor's input.  All pointers but layout / geometry outputs are device pointers. */
+int grx_normstat_geometry(int* rows_per_group, int* max_groups);
+int grx_normstat_layout(int obs_dim, int goal_dim, int64_t* layout);
+int grx_normstat_update(void* stats, const float* rows, int64_t batch, int row_width, int obs_dim, int goal_dim, const int32_t* valid, double eps, void* stream);
+int grx_normstat_refresh(void* stats, int obs_dim, int goal_dim, double eps, void* stream);
+int grx_normstat_apply_batch(const void* stats, const float* rows, int64_t batch, int row_width, int obs_dim, int goal_dim, int act_dim, float clip, float* out,
+                             void* stream);
+int grx_normstat_apply_packed(const void* stats, const float* packed, int64_t n, int packed_width, int obs_dim, int goal_dim, float clip, float* out, void* stream);
 const char* grx_last_error(void);
 
 #ifdef __cplusplus
