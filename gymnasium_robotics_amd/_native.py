@@ -22,7 +22,7 @@ class OverflowLaneStruct(ctypes.Structure):
 class FetchBuffersStruct(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in (
         "qpos", "qvel", "qacc_ws", "mocap", "aux", "goal", "action", "obs", "achieved", "reward", "success", "status", "mask", "order", "cost", "packed", "hullcache", "handoff")] + [
-        ("handoff_stride", ctypes.c_int), ("handoff_large", ctypes.c_int), ("split_state", ctypes.c_void_p), ("split_parts", ctypes.c_int), ("split_pad_", ctypes.c_int), ("lane", OverflowLaneStruct)]
+        ("handoff_stride", ctypes.c_int), ("handoff_large", ctypes.c_int), ("split_state", ctypes.c_void_p), ("split_parts", ctypes.c_int), ("sites_every_substep", ctypes.c_int), ("lane", OverflowLaneStruct)]
 
 
 class FetchResetArgsStruct(ctypes.Structure):
@@ -216,7 +216,7 @@ def check(rc: int):
 
 
 EXPORTED_SYMBOLS = [
-    "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_dim",
+    "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_hull_pair_records", "grx_model_dim",
     "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
     "grx_normstat_geometry", "grx_normstat_layout", "grx_normstat_update", "grx_normstat_refresh", "grx_normstat_apply_batch", "grx_normstat_apply_packed",
 ]
@@ -235,8 +235,9 @@ def acquire_model(H, I, F, device_index):
     """handle of the model packed as (H, I, F) on `device_index`: created on first use, reference-counted afterwards (release_model)"""
     import hashlib
 
-    # (GRX_NO_HULLCELLS changes what grx_model_create derives from the tables -- the A/B switch of the hulls' support-candidate lists -- so it is part of the key)
-    key = (int(device_index), hashlib.sha1(H.tobytes() + I.tobytes() + F.tobytes()).hexdigest(), os.environ.get("GRX_NO_HULLCELLS") is not None)
+    # (GRX_NO_HULLCELLS / GRX_NO_HULLPAIR_RECORDS change what grx_model_create derives from the tables -- the A/B switches of the hulls' support-candidate lists and of the
+    # hull-pair records -- so they are part of the key)
+    key = (int(device_index), hashlib.sha1(H.tobytes() + I.tobytes() + F.tobytes()).hexdigest(), os.environ.get("GRX_NO_HULLCELLS") is not None, os.environ.get("GRX_NO_HULLPAIR_RECORDS") is not None)
     with _MODEL_LOCK:
         ent = _MODELS.get(key)
         if ent is None:

@@ -62,22 +62,48 @@ GRX_MEM int grx_gate_clear(const GrxModel* m, const GrxCtx* c, int gi) {
 // the queued hull-vs-convex pairs of this pass, one after the other, all lanes on each (wave-uniform code)
 GRX_MEM void grx_mesh_pairs(const GrxModel* m, GrxCtx* c, const int* queue, int nq, int lane_) {
   for (int e = 0; e < nq; e++) {
-    const int pair = queue[e], g1 = m->pair_geom1[pair], g2 = m->pair_geom2[pair];
-    const float margin = m->pair_margin[pair];
+    const int pair = queue[e];
+    int g1, g2, adr1, adr2;
+    float margin;
     GrxMprPairW q;
+    // Everything the set-up needs from the model comes from ONE record per pair (GrxModel::reci_hpair / recf_hpair): one volley of wave-uniform loads instead of a walk through
+    // ~25 single-word tables two to three levels deep (pair_geom -> geom_type / geom_size / geom_hulladr / geom_cellbase -> the mesh tables' bases), each level behind its own wait,
+    // in every substep of exactly the worlds that end a Fetch launch.  The record's words ARE those table entries (tests/test_cpu_hull_pair_records.py): same values, same arithmetic.
+    const bool rec_ = m->reci_hpair != nullptr;
+    if (rec_) {
+#if GRX_ON_DEVICE
+      const int pu = __builtin_amdgcn_readfirstlane(pair);   // the queue lives in LDS: tell the compiler that the record's address is wave-uniform
+#else
+      const int pu = pair;
+#endif
+      const int* PI = m->reci_hpair + GRX_RHI * pu; const float* PF = m->recf_hpair + GRX_RHF * pu;
+      g1 = PI[0]; g2 = PI[1]; q.t1 = PI[2]; q.t2 = PI[3]; adr1 = PI[4]; q.n1 = PI[5]; adr2 = PI[6]; q.n2 = PI[7];
+      const int cb1 = PI[8], cb2 = PI[9], fl = PI[10];
+      margin = PF[0];
+      for (int k = 0; k < 3; k++) { q.s1[k] = PF[1 + k]; q.s2[k] = PF[4 + k]; }
+      q.nbr1 = (q.t1 == 7 && (fl & 1)) ? m->mesh_nbr + (size_t)4 * GRX_NBR_RECS * adr1 : nullptr;
+      q.nbr2 = (q.t2 == 7 && (fl & 1)) ? m->mesh_nbr + (size_t)4 * GRX_NBR_RECS * adr2 : nullptr;
+      q.cell1 = cb1 >= 0 ? m->mesh_cellhdr + 2 * (size_t)cb1 : nullptr;
+      q.cell2 = cb2 >= 0 ? m->mesh_cellhdr + 2 * (size_t)cb2 : nullptr;
+    } else {   // a model created without the records (GRX_NO_HULLPAIR_RECORDS): the table walk
+      g1 = m->pair_geom1[pair]; g2 = m->pair_geom2[pair]; margin = m->pair_margin[pair];
+      q.t1 = m->geom_type[g1]; q.t2 = m->geom_type[g2];
+      for (int k = 0; k < 3; k++) { q.s1[k] = m->geom_size[3 * g1 + k]; q.s2[k] = m->geom_size[3 * g2 + k]; }
+      adr1 = q.t1 == 7 ? m->geom_hulladr[g1] : 0; q.n1 = q.t1 == 7 ? m->geom_hullnum[g1] : 0;
+      adr2 = q.t2 == 7 ? m->geom_hulladr[g2] : 0; q.n2 = q.t2 == 7 ? m->geom_hullnum[g2] : 0;
+      q.nbr1 = (q.t1 == 7 && m->mesh_nbr) ? m->mesh_nbr + (size_t)4 * GRX_NBR_RECS * adr1 : nullptr;
+      q.nbr2 = (q.t2 == 7 && m->mesh_nbr) ? m->mesh_nbr + (size_t)4 * GRX_NBR_RECS * adr2 : nullptr;
+      q.cell1 = (q.t1 == 7 && m->mesh_cellhdr && m->geom_cellbase[g1] >= 0) ? m->mesh_cellhdr + 2 * (size_t)m->geom_cellbase[g1] : nullptr;
+      q.cell2 = (q.t2 == 7 && m->mesh_cellhdr && m->geom_cellbase[g2] >= 0) ? m->mesh_cellhdr + 2 * (size_t)m->geom_cellbase[g2] : nullptr;
+    }
     for (int k = 0; k < 9; k++) { q.R1[k] = c->gxmat[9 * g1 + k]; q.R2[k] = c->gxmat[9 * g2 + k]; }
-    q.t1 = m->geom_type[g1]; q.t2 = m->geom_type[g2]; q.hm = 0.5f * margin; q.lane = lane_;
-    for (int k = 0; k < 3; k++) { q.s1[k] = m->geom_size[3 * g1 + k]; q.s2[k] = m->geom_size[3 * g2 + k]; q.c21[k] = (MF)c->gxpos[3 * g2 + k] - (MF)c->gxpos[3 * g1 + k]; }
-    q.v1 = q.t1 == 7 ? m->mesh_vert + 3 * m->geom_hulladr[g1] : m->mesh_vert; q.n1 = q.t1 == 7 ? m->geom_hullnum[g1] : 0;
-    q.v2 = q.t2 == 7 ? m->mesh_vert + 3 * m->geom_hulladr[g2] : m->mesh_vert; q.n2 = q.t2 == 7 ? m->geom_hullnum[g2] : 0;
-    q.aadr1 = m->mesh_adjadr + (q.t1 == 7 ? m->geom_hulladr[g1] : 0); q.anum1 = m->mesh_adjnum + (q.t1 == 7 ? m->geom_hulladr[g1] : 0);
-    q.aadr2 = m->mesh_adjadr + (q.t2 == 7 ? m->geom_hulladr[g2] : 0); q.anum2 = m->mesh_adjnum + (q.t2 == 7 ? m->geom_hulladr[g2] : 0); q.adj = m->mesh_adj;
+    q.hm = 0.5f * margin; q.lane = lane_;
+    for (int k = 0; k < 3; k++) q.c21[k] = (MF)c->gxpos[3 * g2 + k] - (MF)c->gxpos[3 * g1 + k];
+    q.v1 = m->mesh_vert + 3 * adr1; q.v2 = m->mesh_vert + 3 * adr2;
+    q.aadr1 = m->mesh_adjadr + adr1; q.anum1 = m->mesh_adjnum + adr1;
+    q.aadr2 = m->mesh_adjadr + adr2; q.anum2 = m->mesh_adjnum + adr2; q.adj = m->mesh_adj;
     q.pts = (GrxMprPt*)(c->Jp + 192);
-    q.nbr1 = (q.t1 == 7 && m->mesh_nbr) ? m->mesh_nbr + (size_t)4 * GRX_NBR_RECS * m->geom_hulladr[g1] : nullptr;
-    q.nbr2 = (q.t2 == 7 && m->mesh_nbr) ? m->mesh_nbr + (size_t)4 * GRX_NBR_RECS * m->geom_hulladr[g2] : nullptr;
     q.hint = 0; q.hk = 0;
-    q.cell1 = (q.t1 == 7 && m->mesh_cellhdr && m->geom_cellbase[g1] >= 0) ? m->mesh_cellhdr + 2 * (size_t)m->geom_cellbase[g1] : nullptr;
-    q.cell2 = (q.t2 == 7 && m->mesh_cellhdr && m->geom_cellbase[g2] >= 0) ? m->mesh_cellhdr + 2 * (size_t)m->geom_cellbase[g2] : nullptr;
     q.cellrec = m->mesh_cellrec;
 #if GRX_DEVICE_PROFILE
     q.prof = c->prof;
@@ -93,9 +119,9 @@ GRX_MEM void grx_mesh_pairs(const GrxModel* m, GrxCtx* c, const int* queue, int 
       const int hints = (int)mc[5 * slot + 4];
       int h1 = (hints & 4095) - 1, h2 = (hints >> 12) - 1;
       MF sw[3], sb[3], dl[3], r[3];
-      if (q.t1 == 7) { mulMatTVec3f(dl, q.R1, d); h1 = grx_mesh_support_hint(m, m->geom_hulladr[g1], q.n1, dl, h1, r, lane_, q.cell1); mulMatVec3f(sw, q.R1, r); }
+      if (q.t1 == 7) { mulMatTVec3f(dl, q.R1, d); h1 = grx_mesh_support_hint(m, adr1, q.n1, dl, h1, r, lane_, q.cell1); mulMatVec3f(sw, q.R1, r); }
       else grx_geom_support(q.R1, q.s1, q.t1, d, sw);
-      if (q.t2 == 7) { mulMatTVec3f(dl, q.R2, nd); h2 = grx_mesh_support_hint(m, m->geom_hulladr[g2], q.n2, dl, h2, r, lane_, q.cell2); mulMatVec3f(sb, q.R2, r); }
+      if (q.t2 == 7) { mulMatTVec3f(dl, q.R2, nd); h2 = grx_mesh_support_hint(m, adr2, q.n2, dl, h2, r, lane_, q.cell2); mulMatVec3f(sb, q.R2, r); }
       else grx_geom_support(q.R2, q.s2, q.t2, nd, sb);
       MF sv = 0.0f;   // v . d of the Minkowski support point (see grx_mpr_support)
       for (int k = 0; k < 3; k++) sv += ((sw[k] + d[k] * q.hm) - (sb[k] + q.c21[k] - d[k] * q.hm)) * d[k];

@@ -284,6 +284,8 @@ GRX_MEM int grx_mesh_support_hint(const GrxModel* m, int adr, int n, const MF* d
   const float* verts = m->mesh_vert + 3 * adr;
   // The guess is verified in the scan's arithmetic (fp32): this routine only serves the re-check of a cached separating direction, whose test keeps 1e-6 of
   // slack -- ten times what a tie between fp32 projections can hide.  The portal search proper goes through grx_mesh_support (fp64 tie-break).
+  // (Measured and not kept: the same test on the 16 neighbour records of the guess, one coalesced fetch instead of this adjacency walk -- no difference on the Fetch launch
+  // (profiles/ab_fetch_hull_records.txt, row no_nbr_check).)
   const HF dl[3] = {(HF)dlm[0], (HF)dlm[1], (HF)dlm[2]};
   if (hint >= 0 && hint < n) {
     const int aa = m->mesh_adjadr[adr + hint], an = m->mesh_adjnum[adr + hint];

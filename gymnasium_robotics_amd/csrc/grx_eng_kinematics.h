@@ -121,7 +121,7 @@ GRX_MEM void grx_kinematics(const GrxModel* m, GrxCtx* c, int lane_) {
       for (int e = 0; e < 3; e++) { c->janchor[3 * j + e] = ta[e] + c->xpos[3 * par + e]; c->jaxis[3 * j + e] = tx[e]; }
     }
   }
-  FOR_LANES {
+  if (c->sites) FOR_LANES {   // site frames: nothing inside a substep reads them, so a caller that knows its readers asks for them only in the pass those follow (GrxCtx::sites)
     for (int i = lane; i < GRX_NSC; i += 64) {
       int b = m->site_bodyid[i];
       float lpv[3] = {m->site_pos[3 * i], m->site_pos[3 * i + 1], m->site_pos[3 * i + 2]}, lqv[4] = {m->site_quat[4 * i], m->site_quat[4 * i + 1], m->site_quat[4 * i + 2], m->site_quat[4 * i + 3]}, v[3], R[9], Rw[9];

@@ -169,6 +169,10 @@ struct GrxModel {
   // margin - gap, are formed here in the same arithmetic), so results are bit-identical to the table walk.  Layouts: the GRX_R* enums below.
   const int *reci_body, *reci_jnt, *reci_pair, *reci_chain, *reci_weld, *reci_act, *reci_dof, *reci_mpair;
   const float *recf_body, *recf_jnt, *recf_pair, *recf_weld, *recf_eq, *recf_act, *recf_dof, *recf_ten, *recf_mpair;
+  // hull-pair records (grx_mesh_pairs): what the set-up of a queued hull-vs-convex pair walked ~25 single-word tables for, indexed by candidate pair like the queue; both null
+  // when the model was created with GRX_NO_HULLPAIR_RECORDS set (the A/B and test switch: the routine then takes the table walk)
+  const int* reci_hpair;
+  const float* recf_hpair;
 };
 // record strides (words) and field offsets
 enum { GRX_RBI = 16, GRX_RBF = 16,    // body (kinematics): I mocapid, jntadr, jntnum, jt0 (type of the ONLY joint, else -1), qa0 (qpos address of the first joint), flags (1: shift child, 2: free or mocap body),
@@ -182,6 +186,8 @@ enum { GRX_RBI = 16, GRX_RBF = 16,    // body (kinematics): I mocapid, jntadr, j
        GRX_RAI = 8, GRX_RAF = 12,     // actuator: I qposadr / dofadr of its joint, ctrllimited, gaintype, biastype, forcelimited, -, -;  F gear, ctrlrange[2], gainprm[3], biasprm[3], forcerange[2], -
        GRX_RDI = 8, GRX_RDF = 16,     // dof: I qposadr / type / dofadr of its joint, cvelstart, body of that dof, last dof of that body, bodyid, -;  F damping, stiffness, springref, armature, row-parameter block [4, 14) of its friction-loss row, -, -
        GRX_RMI = 4,                   // mass-matrix entry: I i, j, body of dof i, -;  F (one word) armature of dof i
+       GRX_RHI = 12, GRX_RHF = 8,     // hull pair (every candidate pair has one; a geom that is no hull has address, count 0 and cell base -1): I geom1, geom2, type1, type2, first hull vertex / vertex count of geom1, of geom2,
+                                      //   cell base of geom1, of geom2 (-1: no candidate lists), flags (1: neighbour records exist, 2: candidate lists exist), -;  F margin, size of geom1 [1, 4), size of geom2 [4, 7), -
        GRX_RTF = 12 };                // fixed tendon (row parameters): F row-parameter block, -, -
 enum { GRX_PRM_SOLREF = 0, GRX_PRM_SOLIMP = 2, GRX_PRM_MARGIN = 7, GRX_PRM_DA = 8, GRX_PRM_AUX = 9, GRX_PRM_DA2 = 10 };   // AUX: friction[0] of a contact pair, frictionloss of a dof
 #define GRX_NBR_RECS 16
@@ -232,6 +238,8 @@ struct GrxCtx {
   float* shift;      // models with a shift group: the world's offset t[3] and rotation q[4] (state, loaded with qpos); flag 1 = x + t, flag 2 = R(q) x + t
   float* minv;       // models with the noslip post-solver: M^-1 (nv x nv), formed once per substep
   float* hullhint;   // HBM, or null: 4 x (pair + 1, 16 words of support-vertex guesses) + a round-robin counter, kept across substeps and steps (grx_mesh_pairs)
+  int sites, sites_every;   // wave-uniform.  sites: grx_kinematics rebuilds the site frames (sxpos / sxmat) in this pass; 1 unless a caller that knows which pass its readers follow clears it (grx_fetch_sim_world: only
+                            // the pass grx_fetch_outputs reads).  sites_every: that caller leaves sites at 1 in every pass (GrxFetchBuffers::sites_every_substep)
   float* meshcache;  // models with hull-vs-convex pairs: 4 x (pair + 1, separating direction, the two support vertices) + the slot to evict next, kept across the substeps of a step (grx_mesh_pairs)
   int mslot;   // slot of this world's model in g_grx_models (GPU build)
   int bail;    // != 0: a step kernel that hands capacity overflows to a re-run at a larger capacity stops simulating at the first overflowing substep (nothing of this run is kept)
@@ -308,6 +316,7 @@ static int g_grx_solve_mode = 0;   // 0 normal, 1 Newton only, 2 Euler stage onl
 GRX_DEV void grx_ctx_carve(GrxCtx* c, float* base, const GrxDims d) {
   const GrxDims* m = &d;
   float* p = base;
+  c->sites = 1; c->sites_every = 0;
   c->hullhint = nullptr; c->skin = nullptr; c->skin_r = 0.0f; c->bail = 0; c->handoff = nullptr; c->handoff_stride = 0; c->handoff_large = 0; c->resume_first = 0; c->soft_maxefc = c->soft_jpool = c->soft_maxcon = 0; c->lane_entry_count = nullptr; c->lane_entry_list = nullptr; c->lane_entry_cap = 0; c->lane_world = 0; c->lane_ready = nullptr; c->lane_ready_cap = 0;
 #if defined(GRX_EMU) && defined(GRX_EMU_STAGEHOOK)   // test infrastructure (tools/emu_mixed.py): the field map of the working set
 #define GRX_CARVE_REC(field, n, isint) grx_emu_carve_rec(#field, (void*)p, (n), (isint));

@@ -39,7 +39,8 @@ struct GrxFetchBuffers {
   float* handoff;                        // [N, handoff_stride] or null: the worlds' mid-step hand-off rows (include/grx_capi.h; GrxCtx::handoff); word 0 of a row = substep + 1, 0 = none
   int handoff_stride, handoff_large;     // words per row (>= grx_handoff_words); handoff_large: entries claimed by THIS launch need the large tables (see grx_overflow_lane)
   int* split_state;                      // [N, 2] or null: split step (include/grx_capi.h): [2 w] = parts of world w done in this launch (< 0: aborted, re-run booked), [2 w + 1] = their measured duration
-  int split_parts, split_pad_;           // >= 2: the launch has split_parts workgroups per world, each running its share of the substeps (the hand-off rows carry the state between them)
+  int split_parts;                       // >= 2: the launch has split_parts workgroups per world, each running its share of the substeps (the hand-off rows carry the state between them)
+  int sites_every_substep;               // != 0: every pass of the step rebuilds the site frames (A/B and tests); 0: only the pass grx_fetch_outputs reads (grx_fetch_sim_world)
   GrxLane lane;                          // the overflow lane (include/grx_capi.h grx_overflow_lane): no dropped contacts
 };
 
@@ -145,9 +146,12 @@ GRX_MEM void grx_fetch_sim_world(const GrxModel* m, const GrxFetchTask* t, GrxCt
   if (s0 == 0) grx_fetch_set_action(m, t, c, aux_in, action, lane_);
   // n_substeps x mj_step, plus (block_gripper tasks) the _step_callback: zero the finger qpos and run one mj_forward.
   // One loop, one call site of the physics, so the loop body stays resident in the instruction cache.
-  const int total = s_end >= 0 ? s_end : t->n_substeps + (t->block_gripper ? 1 : 0);
+  // Site frames (GrxCtx::sites): in this family only grx_fetch_outputs reads them, after the LAST pass of the step -- the last substep, or the callback's forward pass -- so only
+  // that pass builds them (a part of a split step that stops before it builds none).
+  const int last = t->n_substeps + (t->block_gripper ? 1 : 0) - 1, total = s_end >= 0 ? s_end : last + 1;
   for (int s = s0; s < total; s++) {
     const int callback = (s == t->n_substeps);
+    c->sites = (c->sites_every || s == last) ? 1 : 0;
     if (callback) { LANE0 { c->qpos[t->jq_lf] = 0.0f; c->qpos[t->jq_rf] = 0.0f; } WAVE_SYNC(); }
     else E::grx_check_state(m, c, lane_);
     E::grx_forward_euler(m, c, !callback, lane_);
@@ -162,5 +166,6 @@ GRX_MEM void grx_fetch_sim_world(const GrxModel* m, const GrxFetchTask* t, GrxCt
     }
     if (c->bail && grx_lane_claim(c, lane_)) break;   // a capacity overflowed and the re-run on the large tables is booked: this run will be discarded
   }
+  c->sites = 1;
 }
 };  // struct GrxFetch

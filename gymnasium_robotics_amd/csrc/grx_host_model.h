@@ -20,7 +20,7 @@ struct GrxPackedModel {
   int off_mesh_nbr = -1;      // offset of the derived neighbour-record table inside f (-1: the model has no hulls)
   int off_cellhdr = -1, off_cellbase = -1, off_cellrec = -1;   // derived support-candidate lists (GrxModel::mesh_cellhdr / geom_cellbase inside i, mesh_cellrec inside f; -1: none)
   // derived per-stage record tables (GrxModel::reci_* inside i, recf_* inside f; grx_build_records): offsets, and the [begin, end) ranges they occupy (re-uploaded after grx_model_set_table)
-  struct { int i_body, i_jnt, i_pair, i_chain, i_weld, i_act, i_dof, i_mpair, f_body, f_jnt, f_pair, f_weld, f_eq, f_act, f_dof, f_ten, f_mpair; } rec;
+  struct { int i_body, i_jnt, i_pair, i_chain, i_weld, i_act, i_dof, i_mpair, f_body, f_jnt, f_pair, f_weld, f_eq, f_act, f_dof, f_ten, f_mpair; int i_hpair, f_hpair; } rec;   // i_hpair / f_hpair: -1 = no hull-pair records
   int rec_i0 = 0, rec_i1 = 0, rec_f0 = 0, rec_f1 = 0;
   GrxModel proto;             // scalar members filled; pointers unset
 };
@@ -220,6 +220,7 @@ inline GrxModel grx_bind_model(const GrxPackedModel& p, const float* fbase, cons
   m.reci_act = ibase + p.rec.i_act; m.reci_dof = ibase + p.rec.i_dof; m.reci_mpair = ibase + p.rec.i_mpair;
   m.recf_body = fbase + p.rec.f_body; m.recf_jnt = fbase + p.rec.f_jnt; m.recf_pair = fbase + p.rec.f_pair; m.recf_weld = fbase + p.rec.f_weld; m.recf_eq = fbase + p.rec.f_eq;
   m.recf_act = fbase + p.rec.f_act; m.recf_dof = fbase + p.rec.f_dof; m.recf_ten = fbase + p.rec.f_ten; m.recf_mpair = fbase + p.rec.f_mpair;
+  m.reci_hpair = p.rec.i_hpair >= 0 ? ibase + p.rec.i_hpair : nullptr; m.recf_hpair = p.rec.f_hpair >= 0 ? fbase + p.rec.f_hpair : nullptr;
   return m;
 }
 
@@ -245,6 +246,9 @@ inline void grx_build_records(GrxPackedModel* out, bool allocate) {
     out->rec.i_act = AI(GRX_RAI * nu); out->rec.i_dof = AI(GRX_RDI * nv); out->rec.i_mpair = AI(GRX_RMI * nmp);
     out->rec.f_body = AF(GRX_RBF * nbody); out->rec.f_jnt = AF(GRX_RJF * njnt); out->rec.f_pair = AF(GRX_RPF * npair); out->rec.f_weld = AF(GRX_RWF * nweld); out->rec.f_eq = AF(GRX_REF * neq);
     out->rec.f_act = AF(GRX_RAF * nu); out->rec.f_dof = AF(GRX_RDF * nv); out->rec.f_ten = AF(GRX_RTF * nten); out->rec.f_mpair = AF(nmp);
+    // hull-pair records (GrxModel::reci_hpair / recf_hpair): models with a hull-vs-convex candidate pair only; GRX_NO_HULLPAIR_RECORDS leaves them out (grx_mesh_pairs then walks the tables)
+    out->rec.i_hpair = out->rec.f_hpair = -1;
+    if (d.nmeshpair > 0 && !getenv("GRX_NO_HULLPAIR_RECORDS")) { out->rec.i_hpair = AI(GRX_RHI * npair); out->rec.f_hpair = AF(GRX_RHF * npair); }
     out->rec_i1 = (int)out->i.size(); out->rec_f1 = (int)out->f.size();
   }
   const GrxModel h = grx_bind_model(*out, out->f.data(), out->i.data());
@@ -287,6 +291,22 @@ inline void grx_build_records(GrxPackedModel* out, bool allocate) {
     prm(F + 8, h.pair_solref + 2 * p, h.pair_solimp + 5 * p, F[2], tran, h.pair_friction[5 * p]);
     F[8 + GRX_PRM_DA2] = (float)h.pair_condim[p];   // the row-parameter pass tells condim 1 from the pyramidal ones here
     for (int k = 0; k < 3; k++) { F[20 + k] = h.geom_size[3 * g1 + k]; F[24 + k] = h.geom_size[3 * g2 + k]; }
+  }
+  if (out->rec.i_hpair >= 0) {
+    const int nhull = C("geom_hulladr") < C("geom_hullnum") ? C("geom_hulladr") : C("geom_hullnum");
+    for (int p = 0; p < npair; p++) {
+      int32_t* I = ri + out->rec.i_hpair + GRX_RHI * p; float* F = rf + out->rec.f_hpair + GRX_RHF * p;
+      const int g[2] = {h.pair_geom1[p], h.pair_geom2[p]};
+      I[0] = g[0]; I[1] = g[1];
+      for (int s_ = 0; s_ < 2; s_++) {
+        const int t = h.geom_type[g[s_]]; const bool hull = t == 7 && g[s_] < nhull;
+        I[2 + s_] = t; I[4 + 2 * s_] = hull ? h.geom_hulladr[g[s_]] : 0; I[5 + 2 * s_] = hull ? h.geom_hullnum[g[s_]] : 0;
+        I[8 + s_] = (hull && h.mesh_cellhdr && h.geom_cellbase[g[s_]] >= 0) ? h.geom_cellbase[g[s_]] : -1;
+        for (int k = 0; k < 3; k++) F[1 + 3 * s_ + k] = h.geom_size[3 * g[s_] + k];
+      }
+      I[10] = (h.mesh_nbr ? 1 : 0) | (h.mesh_cellhdr ? 2 : 0); I[11] = 0;
+      F[0] = h.pair_margin[p]; F[7] = 0.0f;
+    }
   }
   for (int w = 0; w < nweld; w++) {
     int32_t* I = ri + out->rec.i_weld + GRX_RWI * w; float* F = rf + out->rec.f_weld + GRX_RWF * w;

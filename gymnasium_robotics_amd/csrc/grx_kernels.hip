@@ -184,6 +184,7 @@ __device__ __forceinline__ void grx_fetch_step_world(int mslot, const GrxFetchTa
   c.mslot = mslot;
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
   grx_lane_setup(b.lane, c, w, true);
+  c.sites_every = b.sites_every_substep;
   if (b.handoff && c.bail && !split) { c.handoff = b.handoff; c.handoff_stride = b.handoff_stride; c.handoff_large = b.handoff_large; }   // this launch can hand a world off mid-step (it has an entry list to claim from)
   GRX_PROF_BEGIN(c, lane_);
 #ifndef GRX_COST_MODEL
@@ -1222,6 +1223,21 @@ extern "C" int grx_model_set_table(grx_model* m, const char* name, const double*
 }
 
 extern "C" int grx_model_lds_bytes(const grx_model* m) { return m ? m->words * 4 : -1; }
+
+// host only (no device is touched): the hull-pair records grx_model_create derives from these tables (GrxModel::reci_hpair / recf_hpair, layout GRX_RHI / GRX_RHF of csrc/grx_engine.h).
+// Returns the number of candidate pairs = records, 0 when the model gets none (no hull-vs-convex pair, or GRX_NO_HULLPAIR_RECORDS is set); the records are written when cap_pairs holds them all.
+extern "C" int grx_model_hull_pair_records(const int32_t* H, const int32_t* I, const double* F, int32_t* reci, float* recf, int cap_pairs) {
+  if (!H || !I || !F) return fail("grx_model_hull_pair_records: null argument");
+  GrxPackedModel pm;
+  grx_pack_model(H, I, F, &pm);
+  if (pm.rec.i_hpair < 0) return 0;
+  const int k = grx_find_table(pm, "pair_geom1"), npair = k >= 0 ? pm.cnt[k] : 0;
+  if (npair <= cap_pairs && reci && recf) {
+    memcpy(reci, pm.i.data() + pm.rec.i_hpair, sizeof(int32_t) * (size_t)GRX_RHI * npair);
+    memcpy(recf, pm.f.data() + pm.rec.f_hpair, sizeof(float) * (size_t)GRX_RHF * npair);
+  }
+  return npair;
+}
 
 extern "C" int grx_model_dim(const grx_model* m, const char* name) {
   if (!m) return -1;

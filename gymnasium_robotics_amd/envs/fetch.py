@@ -230,6 +230,9 @@ class FetchVecEnv(GoalVecEnv):
         self._bufs = self._make_bufs(*common, None, self.order, self.cost, self.packed, self.hullcache, self.handoff)
         self._bufs_masked = self._make_bufs(*common, self.mask, self.order, self.cost, self.packed, self.hullcache, self.handoff)
         self._bufs.handoff_stride = self._bufs_masked.handoff_stride = self._handoff_stride
+        # site frames only in the pass the outputs read (include/grx_capi.h grx_fetch_buffers.sites_every_substep); GRX_FETCH_SITES_EVERY_SUBSTEP=1: in every pass (A/B, tests)
+        sites_every = int(os.environ.get("GRX_FETCH_SITES_EVERY_SUBSTEP", "0") != "0")
+        self._bufs.sites_every_substep = self._bufs_masked.sites_every_substep = sites_every
         # SPLIT STEP (include/grx_capi.h grx_fetch_buffers.split_parts): the step launch has P workgroups per world, each running 1 / P of the substeps (the state travels through the
         # world's hand-off row): the launch's tail -- the duration of the LAST workgroup started, a whole world-step otherwise -- shrinks to 1 / P of it.  Bit-identical to the unsplit
         # launch (tests/test_gpu_fetch.py::test_split_step_is_the_plain_step).  GRX_FETCH_SPLIT=P (1: off); not combined with the hull-less fast kernel.
@@ -249,7 +252,7 @@ class FetchVecEnv(GoalVecEnv):
 
             def lane_bufs(m):
                 b = mk(*common, m, None, None, packed, hullcache, handoff)
-                b.handoff_stride = stride
+                b.handoff_stride, b.sites_every_substep = stride, sites_every
                 return b
 
             if handoff is not None:

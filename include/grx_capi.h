@@ -142,7 +142,9 @@ typedef struct grx_fetch_buffers {
    * earlier parts (cost).  Results are bit-identical to the unsplit launch (tests/test_gpu_fetch.py::test_split_step_is_the_plain_step).  Zeroed before the first launch. */
   int* split_state;                     /* [N, 2] or NULL */
   int split_parts;                      /* 0 / 1: one workgroup per world */
-  int split_pad_;
+  int sites_every_substep;              /* 0: the step builds the site frames only in the pass its outputs read (the last substep, or the block_gripper callback's forward pass); nothing inside a
+                                         * substep reads them.  != 0: in every pass, as the other families do (FetchVecEnv: GRX_FETCH_SITES_EVERY_SUBSTEP=1).  Bit-identical either way
+                                         * (tests/test_gpu_fetch_hull_records.py). */
   grx_overflow_lane lane;               /* capacity overflows are re-run on larger tables instead of dropping contacts: see grx_overflow_lane above and its LIMITS */
 } grx_fetch_buffers;
 
@@ -296,6 +298,12 @@ int grx_model_create(const int32_t* H, int nH, const int32_t* I, int nI, const d
 int grx_model_destroy(grx_model* m);
 int grx_model_set_table(grx_model* m, const char* name, const double* data, int n);
 int grx_model_lds_bytes(const grx_model* m);
+/* HULL-PAIR RECORDS.  grx_model_create gathers, for every candidate pair of a model with hull-vs-convex pairs, what the set-up of a queued hull pair reads from the model (geoms, types,
+ * margin, sizes, hull address / count, candidate-list base, which derived tables exist: 12 int + 8 float words per pair) into one record, so the set-up is one volley of loads
+ * instead of a walk through ~25 tables.  GRX_NO_HULLPAIR_RECORDS=1 in the environment
+ * at model creation leaves the records out and the set-up takes the table walk (A/B, tests); results are bit-identical.  This call is host-only: it returns the number of records these tables
+ * give (0: none) and copies them when cap_pairs holds them all (tests/test_cpu_hull_pair_records.py compares every field with the tables). */
+int grx_model_hull_pair_records(const int32_t* H, const int32_t* I, const double* F, int32_t* reci, float* recf, int cap_pairs);
 int grx_model_dim(const grx_model* m, const char* name);   /* "nq" "nv" "nu" "nbody" "nmocap" "ndevpair"; "shape" = id of the shape-specialised kernel (0 generic); "handtree"; -1 unknown */
 
 int grx_fetch_step(const grx_model* m, const grx_fetch_task* task, const grx_fetch_buffers* buf, int n_worlds, void* stream);
