@@ -15,7 +15,7 @@ Nothing here imports torch or loads the HIP library until an environment is cons
 """
 from typing import List
 
-__all__ = ["make_vec", "registered_env_ids", "env_family", "UnsupportedEnvError", "PipelinedVecEnv"]
+__all__ = ["make_vec", "registered_env_ids", "env_family", "UnsupportedEnvError", "PipelinedVecEnv", "BatchedSim"]
 
 
 class UnsupportedEnvError(KeyError):
@@ -111,4 +111,8 @@ def __getattr__(name):      # (lazy: the pipeline module is only needed by calle
         from .pipeline import PipelinedVecEnv
 
         return PipelinedVecEnv
+    if name == "BatchedSim":      # the physics alone for a caller's own MJCF model (sim.py)
+        from .sim import BatchedSim
+
+        return BatchedSim
     raise AttributeError(name)

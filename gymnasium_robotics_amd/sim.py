@@ -1,0 +1,279 @@
+"""BatchedSim: the physics alone -- ``mujoco.mj_step`` / ``mujoco.mj_forward`` for N worlds of a caller's own MJCF model on the device, with no task baked in.
+
+The reference's ``MujocoRobotEnv`` / ``MujocoFetchEnv`` (gymnasium_robotics/envs/robot_env.py:280-345) exist to be subclassed with one's own XML: the
+subclass writes ``data.ctrl`` / ``data.mocap_pos``, calls ``mj_step(model, data, nstep=n_substeps)`` (robot_env.py:341) and reads ``data.qpos``, ``data.site_xpos`` and
+``mujoco_utils.get_site_xvelp``.  This class is that loop for a batch: the state rows are device tensors the caller writes in place, ``step`` / ``forward`` enqueue one launch
+of the generic engine kernel (grx_sim_step, include/grx_capi.h) on torch's current stream, and the requested ``MjData`` fields are device tensors afterwards.
+
+    sim = grx.BatchedSim("my_robot.xml", num_worlds=4096, outputs=("site_xpos", "site_xvelp"))
+    sim.reset()
+    sim.ctrl[:] = policy(obs)                 # any torch op on the current stream
+    sim.step(nstep=20)
+    tip = sim.site_xpos[:, sim.site_id("tip")]
+
+Outputs are what ``MjData`` holds at that moment: after ``step`` the derived fields belong to the position / velocity stage of the LAST substep, before its integration (the
+one-substep-stale kinematics the reference's environments read after ``mj_step``), ``qpos`` / ``qvel`` are the integrated state; after ``forward`` they belong to the state as
+given.  ``site_xvelp`` / ``site_xvelr`` are the site Jacobian of that pass times the current ``qvel`` (``get_site_xvelp`` / ``get_site_xvelr``).
+
+``xpos`` / ``xquat`` index the COMPILED model's bodies: the compiler merges static children into their parents, ``sim.model.names["body"]`` maps the surviving names to rows.
+Sites keep their identity whatever body they end up on: they are the stable handle for "where is this point of my robot".
+
+Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, Jacobians, keyframes, per-world model edits.
+"""
+import ctypes
+
+import numpy as np
+
+from .mjcf import CompiledModel, compile_mjcf
+
+STATE = ("qpos", "qvel", "qacc_warmstart", "ctrl", "mocap_pos", "mocap_quat")
+OUTPUTS = ("xpos", "xquat", "site_xpos", "site_xmat", "site_xvelp", "site_xvelr", "sensordata", "ncon", "nefc")
+
+
+class BatchedSim:
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None):
+        """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
+        default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
+        again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
+        CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
+        keep_sites, mutate, ...).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        if int(num_worlds) < 1:
+            raise ValueError("num_worlds must be at least 1")
+        if overflow not in ("rerun", "flag"):
+            raise ValueError(f"overflow must be 'rerun' or 'flag', not {overflow!r}")
+        if isinstance(outputs, str):
+            outputs = (outputs,)
+        unknown = [o for o in outputs if o not in OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown output(s) {unknown}; the optional outputs are {OUTPUTS}")
+        if capacity is not None and not set(capacity) <= {"maxcon", "maxefc", "jpool"}:
+            raise ValueError(f"capacity takes maxcon, maxefc and jpool, not {sorted(set(capacity) - {'maxcon', 'maxefc', 'jpool'})}")
+        kw = dict(compile_kwargs or {})
+        if kw.get("origin") is not None or kw.get("shift_body") is not None:
+            raise ValueError("BatchedSim returns raw engine coordinates: compile the model in the MJCF's own frame (no origin) and without a shift group")
+        if isinstance(model, CompiledModel):
+            if kw:
+                raise ValueError("compile_kwargs apply to an MJCF path, not to a CompiledModel")
+            self.model = model.with_capacity(**capacity) if capacity else model
+        else:
+            self.model = compile_mjcf(str(model), capacity=capacity, **kw)
+        if self.model.origin.any():
+            raise ValueError("BatchedSim needs a model compiled in the MJCF's own frame (origin 0)")
+        m = self.model
+        self.num_worlds, self.device_name, self.overflow = int(num_worlds), device, overflow
+        self.outputs = tuple(o for o in OUTPUTS if o in outputs)
+        self.nq, self.nv, self.nu, self.nbody, self.nsite, self.nmocap = (m.dim(k) for k in ("nq", "nv", "nu", "nbody", "nsite", "nmocap"))
+        self.ntouch = len(np.asarray(m.tables.get("touch_body", [])).reshape(-1))
+        self.timestep = m.opt("timestep")
+        self._t = None      # the device tensors, made on first use
+        self._h = self._h_big = self.lane = None
+
+    # ------------------------------------------------------------------ names (CompiledModel.names / tables): no device needed
+    def _lookup(self, kind, name):
+        table = self.model.names.get(kind, {})
+        if name not in table:
+            raise KeyError(f"no {kind} named {name!r}; the compiled model's {kind} names are {sorted(table)}")
+        return int(table[name])
+
+    def body_id(self, name):
+        """row of `name` in xpos / xquat: a body of the COMPILED model (a static child merged into its parent has no row of its own)"""
+        return self._lookup("body", name)
+
+    def site_id(self, name):
+        return self._lookup("site", name)
+
+    def actuator_id(self, name):
+        return self._lookup("actuator", name)
+
+    def mocap_id(self, name):
+        """row of the mocap body `name` in mocap_pos / mocap_quat"""
+        return self._lookup("mocap", name)
+
+    def joint_qposadr(self, name):
+        return int(np.asarray(self.model.tables["jnt_qposadr"]).reshape(-1)[self._lookup("joint", name)])
+
+    def joint_dofadr(self, name):
+        return int(np.asarray(self.model.tables["jnt_dofadr"]).reshape(-1)[self._lookup("joint", name)])
+
+    # ------------------------------------------------------------------ device side
+    def _shapes(self):
+        n = self.num_worlds
+        return dict(qpos=(n, self.nq), qvel=(n, self.nv), qacc_warmstart=(n, self.nv), ctrl=(n, self.nu), mocap_pos=(n, self.nmocap, 3), mocap_quat=(n, self.nmocap, 4),
+                    xpos=(n, self.nbody, 3), xquat=(n, self.nbody, 4), site_xpos=(n, self.nsite, 3), site_xmat=(n, self.nsite, 9), site_xvelp=(n, self.nsite, 3),
+                    site_xvelr=(n, self.nsite, 3), sensordata=(n, self.ntouch), ncon=(n,), nefc=(n,))
+
+    def _ensure(self):
+        if self._t is not None:
+            return self._t
+        import torch
+
+        from . import _native
+        from .core import OverflowLane, create_rerun_model
+
+        self.device = torch.device(self.device_name)
+        if self.device.type != "cuda":
+            raise RuntimeError("BatchedSim runs on the GPU only (there is no CPU path)")
+        self._L = _native.lib()
+        dev_index = self.device.index or 0
+        H, I, F = self.model.pack()
+        self._h = _native.acquire_model(H, I, F, dev_index)
+        self.lds_bytes = self._L.grx_model_lds_bytes(self._h)
+        shapes = self._shapes()
+        t = {}
+        for k in STATE + self.outputs:
+            t[k] = torch.zeros(shapes[k], dtype=torch.int32 if k in ("ncon", "nefc") else torch.float32, device=self.device)
+        t["status_words"] = torch.zeros(self.num_worlds, dtype=torch.int32, device=self.device)
+        tb = self.model.tables
+        self._qpos0 = torch.from_numpy(np.asarray(tb["qpos0"], dtype=np.float32).reshape(-1)).to(self.device)
+        self._mocap_pos0 = torch.from_numpy(np.asarray(tb.get("mocap_pos0", np.zeros(0)), dtype=np.float32).reshape(self.nmocap, 3)).to(self.device)
+        self._mocap_quat0 = torch.from_numpy(np.asarray(tb.get("mocap_quat0", np.zeros(0)), dtype=np.float32).reshape(self.nmocap, 4)).to(self.device)
+        self._t = t
+        self._bufs = self._make_bufs(None)
+        if self.overflow == "rerun":
+            self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
+            if self._h_big is not None:
+                self.lane = OverflowLane(self.num_worlds, self.device, self.model, self._make_bufs, mode="entry")
+        t["qpos"][:] = self._qpos0
+        if self.nmocap:
+            t["mocap_pos"][:], t["mocap_quat"][:] = self._mocap_pos0, self._mocap_quat0
+        return t
+
+    def __getattr__(self, name):      # the device tensors: sim.qpos ... sim.site_xpos; an output that was not requested does not exist
+        if name.startswith("_"):
+            raise AttributeError(name)
+        if name in ("device", "lds_bytes"):      # known once the device side exists
+            self._ensure()
+            return self.__dict__[name]
+        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()):
+            return self._ensure()[name]
+        if name in OUTPUTS:
+            raise AttributeError(f"output {name!r} was not requested: BatchedSim(..., outputs={self.__dict__.get('outputs', ())})")
+        raise AttributeError(name)
+
+    def _make_bufs(self, mask):
+        from . import _native
+
+        t, b = self._t, _native.SimBuffersStruct()
+        ptr = lambda x: x.data_ptr() if x.numel() else None
+        b.qpos, b.qvel, b.qacc_ws = t["qpos"].data_ptr(), t["qvel"].data_ptr(), t["qacc_warmstart"].data_ptr()
+        b.ctrl, b.mocap_pos, b.mocap_quat = ptr(t["ctrl"]), ptr(t["mocap_pos"]), ptr(t["mocap_quat"])
+        for k in self.outputs:
+            setattr(b, k, ptr(t[k]))
+        b.status = t["status_words"].data_ptr()
+        b.mask = None if mask is None else mask.data_ptr()
+        return b
+
+    def _mask(self, mask):
+        if mask is None:
+            return None
+        import torch
+
+        m = torch.as_tensor(mask, device=self.device)
+        if m.shape != (self.num_worlds,):
+            raise ValueError(f"mask must have shape ({self.num_worlds},), not {tuple(m.shape)}")
+        return m.to(torch.uint8).contiguous()
+
+    def _launch(self, nstep, forward_only, mask):
+        import torch
+
+        from . import _native
+
+        self._ensure()
+        m = self._mask(mask)
+        self._mask_keep = m
+        with torch.cuda.device(self.device):
+            stream = lambda: ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream())))
+            self._bufs.mask = None if m is None else m.data_ptr()
+            if self.lane is None:
+                go(self._h)(self._bufs)
+            else:      # entry mode: the step launch lists the worlds that exceed a table and leaves them untouched; the launch behind it runs them on the large tables
+                self.lane.rerun_only(m, self._bufs, go(self._h), go(self._h_big))
+
+    def step(self, nstep=1, mask=None):
+        """mj_step(model, data, nstep) for every world (mask: only the worlds with a non-zero entry; the others keep state, outputs and status).  ctrl and the mocap poses are
+        held over the substeps.  Enqueues on torch's current stream and returns nothing; the tensors are valid until the next launch."""
+        if int(nstep) < 1:
+            raise ValueError("nstep must be at least 1")
+        self._launch(nstep, 0, mask)
+
+    def forward(self, mask=None):
+        """mj_forward: the derived fields of the state as given; qpos / qvel are left as they are, the warm start is updated"""
+        self._launch(0, 1, mask)
+
+    def reset(self, mask=None):
+        """mj_resetData for the masked worlds (all by default): qpos0, zero velocities / warm start / ctrl, the model's mocap poses; then forward()"""
+        import torch
+
+        t = self._ensure()
+        m = self._mask(mask)
+        sel = slice(None) if m is None else m.bool()
+        t["qpos"][sel] = self._qpos0
+        for k in ("qvel", "qacc_warmstart", "ctrl"):
+            t[k][sel] = 0.0
+        if self.nmocap:
+            t["mocap_pos"][sel], t["mocap_quat"][sel] = self._mocap_pos0, self._mocap_quat0
+        self.forward(mask)
+
+    # ------------------------------------------------------------------ status words (include/grx_capi.h grx_status_bits), as the env classes report them
+    @property
+    def status(self):
+        """int16 view [N]: the GRX_STATUS_* flags of the last launch (0 = healthy)"""
+        import torch
+
+        return self._ensure()["status_words"].view(torch.int16).view(-1, 2)[:, 0]
+
+    @property
+    def status_sticky(self):
+        """int16 view [N]: the same flags OR-accumulated over every launch since clear_status()"""
+        import torch
+
+        return self._ensure()["status_words"].view(torch.int16).view(-1, 2)[:, 1]
+
+    def status_counts(self):
+        st = (self._ensure()["status_words"] >> 16).cpu().numpy()
+        return {"badnum": int((st & 1 != 0).sum()), "con_overflow": int((st & 2 != 0).sum()), "efc_overflow": int((st & 4 != 0).sum()),
+                "factor": int((st & 8 != 0).sum()), "worlds": int(self.num_worlds)}
+
+    def clear_status(self):
+        self._ensure()["status_words"].zero_()
+
+    # ------------------------------------------------------------------ checkpoints
+    def get_state(self):
+        """the state rows and the status words as host arrays (synchronises); the outputs are not state: forward() rebuilds them"""
+        import torch
+
+        t = self._ensure()
+        torch.cuda.synchronize(self.device)
+        return {k: t[k].cpu().numpy().copy() for k in STATE + ("status_words",)}
+
+    def set_state(self, d):
+        import torch
+
+        t = self._ensure()
+        for k in STATE:
+            if k not in d:
+                raise ValueError(f"state lacks {k!r}")
+            if tuple(np.shape(d[k])) != tuple(t[k].shape):
+                raise ValueError(f"state row {k!r} has shape {tuple(np.shape(d[k]))}, this simulation holds {tuple(t[k].shape)}")
+        for k in STATE + (("status_words",) if "status_words" in d else ()):
+            t[k].copy_(torch.from_numpy(np.ascontiguousarray(d[k], dtype=np.int32 if k == "status_words" else np.float32)).to(self.device))
+
+    def close(self):
+        from . import _native
+
+        if self._t is not None:
+            import torch
+
+            torch.cuda.synchronize(self.device)
+        for k in ("_h", "_h_big"):
+            if self.__dict__.get(k):
+                _native.release_model(self.__dict__[k])
+                self.__dict__[k] = None
+        self.lane = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

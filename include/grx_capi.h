@@ -360,6 +360,37 @@ int grx_adroit_step(const grx_model* m, const grx_adroit_task* task, const grx_a
  * + FrankaRobot._get_obs + KitchenEnv._get_obs (59-vector with observation noise) + the per-task completion tests of compute_reward
  * (envs/franka_kitchen/franka_env.py:92-171, kitchen_env.py:340-384); forward_only != 0: the reset path (set_state -> mj_forward, _get_obs) */
 int grx_kitchen_step(const grx_model* m, const grx_kitchen_task* task, const grx_kitchen_buffers* buf, int n_worlds, int forward_only, void* stream);
+
+/* The TASK-FREE stepper: mujoco.mj_step(model, data, nstep) (envs/robot_env.py:341, nstep = n_substeps) or mujoco.mj_forward (forward_only != 0) for N worlds of ANY
+ * compiled model, and the MjData fields a MujocoRobotEnv / MujocoFetchEnv subclass reads afterwards.  No action mapping, observation or reward: ctrl and the mocap poses are
+ * state the caller writes (ctrl is held over the nstep substeps; the engine's actuation stage clamps to ctrlrange as mj_step does), mirrors struct GrxSimBuffers
+ * (csrc/grx_sim_task.h).  Runs on the generic kernels whatever the model.
+ * OUTPUTS are what MjData holds at that moment.  After nstep >= 1: qpos / qvel / qacc_ws are the integrated state, the derived fields are those of the position and velocity
+ * stage of the LAST substep, before its integration (the reference's environments read the same one-substep-stale kinematics after mj_step).  After forward_only: the fields of
+ * the state as given; qpos / qvel are not written, qacc_ws is.
+ *   xpos, xquat            data.xpos / data.xquat of the COMPILED model's bodies (static children are merged into their parents: CompiledModel.names["body"])
+ *   site_xpos, site_xmat   data.site_xpos / data.site_xmat                                  utils/mujoco_utils.py get_site_xpos / get_site_xmat
+ *   site_xvelp, site_xvelr mj_jacSite(model, data, site) @ data.qvel (current qvel)         utils/mujoco_utils.py get_site_xvelp / get_site_xvelr
+ *   sensordata             the touch sensors the compiler selected (touch_filter), raw      data.sensordata
+ *   ncon, nefc             contacts (at most the table's capacity) and constraint rows of the last pass
+ * OVERFLOW: `lane` zeroed = a world that exceeds a table goes on with the excess contacts dropped, GRX_STATUS_CON_OVERFLOW / _EFC_OVERFLOW say so.  Entry mode only
+ * (grx_overflow_lane): with entry_count / entry_list the launch leaves such a world untouched and lists it; a second call with `list` / `count` set, on a handle of the same
+ * model created with larger tables, runs the listed worlds again and writes their state, outputs and status.  skip, next_*, ttl, ready, progress and poll_* are not read.
+ * Returns -1 (grx_last_error) for a NULL model / buffers / state / status pointer, ctrl NULL with nu > 0, mocap_pos or mocap_quat NULL with nmocap > 0, n_worlds < 1,
+ * nstep < 1 without forward_only, a model compiled with an origin other than 0 (the outputs are raw engine coordinates) or with a per-world shift group.  Enqueues, never waits. */
+typedef struct grx_sim_buffers {
+  float *qpos, *qvel, *qacc_ws;            /* [N,nq] [N,nv] [N,nv]  in / out */
+  const float* ctrl;                       /* [N,nu]; NULL iff nu == 0 */
+  const float *mocap_pos, *mocap_quat;     /* [N,nmocap,3] [N,nmocap,4]; NULL iff nmocap == 0 */
+  float *xpos, *xquat, *site_xpos, *site_xmat, *site_xvelp, *site_xvelr, *sensordata;   /* optional outputs, NULL = not written: [N,nbody,3] [N,nbody,4] [N,nsite,3] [N,nsite,9] [N,nsite,3] [N,nsite,3] [N,ntouch] */
+  int *ncon, *nefc;                        /* [N] optional */
+  int* status;                             /* [N] */
+  const unsigned char* mask;               /* [N] or NULL */
+  grx_overflow_lane lane;                  /* zeroed: no re-run */
+} grx_sim_buffers;
+int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream);
+/* host only: out[0] = sizeof(grx_sim_buffers), out[1 ...] = the byte offset of each member in declaration order (the lane as one member); returns the number of values (19) */
+int grx_sim_layout(long long* out, int cap);
 /* `count` consecutive np_random.uniform(-1, 1) draws per listed world, float32 rows (states / idx as in grx_fetch_sample_resets; idx NULL = worlds 0..n-1).  HOST pointers. */
 int grx_sample_uniform_rows(uint64_t* states, const int64_t* idx, int n, int count, float* out);
 /* The same draws ON THE DEVICE: states [N,4] uint64 and out [N,count] float32 are DEVICE pointers, mask [N] uint8 or NULL selects the worlds whose streams advance

@@ -1,0 +1,62 @@
+"""Throughput of grx.BatchedSim (the generic engine kernel behind grx_sim_step) in env-steps/s: the arm scene of tests/sim_cases.py at `--worlds` worlds, one env-step =
+`--nstep` substeps, beside the AntMaze model stepped through the same door (same kernel, AntMaze's own table capacities and frame_skip).  One run, no repetition: a figure to
+size expectations by, not a benchmark (bench.py measures the flagship workload).
+
+    python tools/sim_probe.py --worlds 4096 --steps 200 --warmup 20 > profiles/sim_probe.txt"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def timed(sim, nstep, steps, warmup):
+    import torch
+
+    for _ in range(warmup):
+        sim.step(nstep)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        sim.step(nstep)
+    e1.record()
+    torch.cuda.synchronize()
+    return sim.num_worlds * steps / (e0.elapsed_time(e1) * 1e-3)
+
+
+def main():
+    import numpy as np
+    import torch
+
+    import gymnasium_robotics_amd as grx
+    import sim_cases as S
+    from gymnasium_robotics_amd import _native
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--worlds", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--nstep", type=int, default=5)
+    a = ap.parse_args()
+    print(f"command: python tools/sim_probe.py --worlds {a.worlds} --steps {a.steps} --warmup {a.warmup} --nstep {a.nstep}")
+    print(f"build id: {_native.build_id()}   device: {torch.cuda.get_device_name(0)}   SINGLE RUN")
+    sc = S.SCENES["arm"]
+    st = sc.states(a.worlds)
+    arm = grx.BatchedSim(sc.model, num_worlds=a.worlds, outputs=("site_xpos", "site_xvelp"))
+    for k in ("qpos", "qvel", "ctrl"):
+        getattr(arm, k).copy_(torch.from_numpy(np.ascontiguousarray(st[k], dtype=np.float32)))
+    rate = timed(arm, a.nstep, a.steps, a.warmup)
+    print(f"arm scene (nv 10, 4 plane contacts)   {a.worlds} worlds x {a.nstep} substeps: {rate:12.0f} env-steps/s   LDS/world {arm.lds_bytes} B   status {arm.status_counts()}")
+    env = grx.make_vec("AntMaze_UMaze-v5", num_envs=a.worlds)
+    env.reset(seed=0)
+    ant = grx.BatchedSim(env.model, num_worlds=a.worlds, outputs=("site_xpos", "site_xvelp") if env.model.dim("nsite") else ())
+    ant.qpos.copy_(env.qpos); ant.qvel.copy_(env.qvel)
+    ant.ctrl.copy_(torch.from_numpy(np.random.default_rng(0).uniform(-1, 1, (a.worlds, ant.nu)).astype(np.float32)))
+    rate = timed(ant, a.nstep, a.steps, a.warmup)
+    print(f"AntMaze_UMaze model (RK4, generic kernel) {a.worlds} worlds x {a.nstep} substeps: {rate:12.0f} env-steps/s   LDS/world {ant.lds_bytes} B   status {ant.status_counts()}")
+
+
+if __name__ == "__main__":
+    main()
