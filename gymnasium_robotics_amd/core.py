@@ -5,9 +5,36 @@
 arbitrary leading batch dimensions (core.py:45-114) -- with a leading ``num_envs`` axis on everything,
 following the gymnasium.vector.VectorEnv conventions [3P].
 """
+import ctypes
+import weakref
+
 import numpy as np
 
 from .spaces import Dict
+
+
+def stream_ptr(device):
+    """torch's CURRENT stream on `device`, as the native entry points take it"""
+    import torch
+
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def release_models(obj, names):
+    """drop obj's reference to each native model handle it holds under `names` (_native.release_model destroys a model with its last reference) and clear the attribute"""
+    from . import _native
+
+    for k in names:
+        if getattr(obj, k, None):
+            _native.release_model(getattr(obj, k))
+            setattr(obj, k, None)
+
+
+def status_counts(words, n):
+    """worlds per sticky GRX_STATUS_* flag (the high halves of the status words; synchronises)"""
+    st = (words >> 16).cpu().numpy()
+    return {"badnum": int((st & 1 != 0).sum()), "con_overflow": int((st & 2 != 0).sum()), "efc_overflow": int((st & 4 != 0).sum()),
+            "factor": int((st & 8 != 0).sum()), "worlds": int(n)}
 
 
 class GoalVecEnv:
@@ -16,6 +43,7 @@ class GoalVecEnv:
     tests/test_envs.py:164-178 and tests/envs/hand/test_reach.py pickle every env).  Device state is not serialised."""
 
     metadata = {"render_modes": []}
+    MODEL_HANDLES = ("_h", "_h_big", "_h_fast")      # every attribute that may hold a reference-counted native model (fast tables, the overflow lane's, Fetch's hull-less kernel's)
 
     def __new__(cls, *args, **kwargs):
         obj = super().__new__(cls)
@@ -28,10 +56,30 @@ class GoalVecEnv:
     def __setstate__(self, d):
         out = type(self)(*d["_ezpickle_args"], **d["_ezpickle_kwargs"])
         self.__dict__.update(out.__dict__)
-        out.__dict__.pop("_h", None)   # the native handles now belong to self: do not let the temporary destroy them
-        out.__dict__.pop("_h_big", None)
-        if getattr(self, "lane", None) is not None and hasattr(self, "_lane_make_bufs"):
+        for k in self.MODEL_HANDLES:   # the native handles now belong to self: do not let the temporary release them
+            out.__dict__.pop(k, None)
+        if getattr(self, "lane", None) is not None:
             self.lane._make_bufs = self._lane_make_bufs()     # the overflow lane's buffer factory held a weak reference to the temporary
+
+    def close(self):
+        release_models(self, self.MODEL_HANDLES)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return stream_ptr(self.device)
+
+    def _lane_make_bufs(self):
+        """the overflow lane's buffer factory: mask tensor (or None) -> a fresh buffer struct of the family"""
+        me = weakref.ref(self)      # (the lane must not keep the environment alive: its native models are released by __del__)
+        return lambda m: me()._make_lane_bufs(m)
+
+    def _make_lane_bufs(self, mask):
+        return self._make_bufs(mask)
 
     num_envs: int
     single_observation_space: Dict
@@ -71,9 +119,7 @@ class GoalVecEnv:
     # `status` (int32 per world): low half = GRX_STATUS_* flags of the last launch, high half = the same flags OR-accumulated by the kernels
     # since clear_status() (include/grx_capi.h).  A capacity overflow drops contacts for one substep: training code should poll this.
     def status_counts(self):
-        st = (self.status >> 16).cpu().numpy()
-        return {"badnum": int((st & 1 != 0).sum()), "con_overflow": int((st & 2 != 0).sum()), "efc_overflow": int((st & 4 != 0).sum()),
-                "factor": int((st & 8 != 0).sum()), "worlds": int(self.num_envs)}
+        return status_counts(self.status, self.num_envs)
 
     def clear_status(self):
         self.status.zero_()
@@ -89,9 +135,6 @@ class GoalVecEnv:
             st = self.status.cpu().numpy()
             info["status"], info["status_sticky"] = st & 0xFFFF, st >> 16
         return info
-
-    def close(self):
-        pass
 
     # ---- frames: the device rows live in the compiled model's (workspace-centred) world frame, the reference / the oracle / fixtures in the MJCF's (mjcf.CompiledModel.origin)
     def load_world_rows(self, rows=None, **more):
@@ -137,13 +180,7 @@ class GoalVecEnv:
         if getattr(self, "_rng_dev", None) is None or not getattr(self, "_device_draws", True):
             self.np_randoms[i] = generator
             return
-        s = generator.bit_generator.state
-        if s["bit_generator"] != "PCG64":
-            raise ValueError("the device streams are numpy PCG64 streams")
-        mask = (1 << 64) - 1
-        row = [s["state"]["state"] >> 64, s["state"]["state"] & mask, s["state"]["inc"] >> 64, s["state"]["inc"] & mask]
-        if self._rng_dev.shape[1] > 4:
-            row.append((int(s["has_uint32"]) << 32) | int(s["uinteger"]))
+        row = pcg64_row(generator.bit_generator.state, buffered=self._rng_dev.shape[1] > 4)
         self._rng_dev[i] = torch.from_numpy(np.array(row, dtype=np.uint64).view(np.int64)).to(self.device)
 
     # ------------------------------------------------------------------ checkpoint / resume (the reference's own round trip: adroit_hand/adroit_hammer.py:380-402,
@@ -289,6 +326,25 @@ def np_random(seed=None):
     return np.random.Generator(np.random.PCG64(ss)), ss.entropy
 
 
+def pcg64_row(bit_generator_state, buffered=False):
+    """a numpy PCG64's `bit_generator.state` as the words of a device stream row: [state_hi, state_lo, inc_hi, inc_lo], with buffered=True also numpy's buffered
+    32-bit half (has_uint32 << 32 | uinteger); Python ints"""
+    if bit_generator_state["bit_generator"] != "PCG64":
+        raise ValueError("the device streams are numpy PCG64 streams")
+    s, mask = bit_generator_state["state"], (1 << 64) - 1
+    row = [s["state"] >> 64, s["state"] & mask, s["inc"] >> 64, s["inc"] & mask]
+    if buffered:
+        row.append((int(bit_generator_state["has_uint32"]) << 32) | int(bit_generator_state["uinteger"]))
+    return row
+
+
+def seed_rows(seeds, buffered=False):
+    """one PCG64 per seed, seeded like gymnasium.utils.seeding.np_random [3P] (None: fresh entropy): their stream rows, uint64 [n, 4 | 5]"""
+    st = np.zeros((len(seeds), 5 if buffered else 4), np.uint64)
+    for i, sd in enumerate(seeds):
+        st[i] = pcg64_row(np_random(sd)[0].bit_generator.state, buffered)
+    return st
+
 
 # ---------------------------------------------------------------------------------------------- the overflow lane (include/grx_capi.h, grx_overflow_lane)
 # Tables of the LARGE model of every family: 256 rows / 4 080 Jacobian-pool words (row offsets are 14 bits, GRX_ROW_PACK: the kitchen's 8 160 fit as well) / 64 contacts (one lane each: twice the fast kernels' lists); ~32-42 KB of LDS per
@@ -326,6 +382,52 @@ def cost_order_update(env, alpha=None):
 
     alpha = float(os.environ.get("GRX_BALANCE_ALPHA", 0.1 if alpha is None else alpha))      # weight of the newest sample in the moving average the order is sorted by
     _native.check(env._L.grx_order_by_cost(env.cost.data_ptr(), env.cost_ema.data_ptr(), alpha, env.num_envs, env.order.data_ptr(), env._stream()))
+
+
+def split_alloc(env, parts, stride_words, state_words, bufs, rows_field="split_rows", stride_field="split_stride"):
+    """Split step (include/grx_capi.h, split_parts of the families' buffer structs): `parts` workgroups per world, the world handed on through a carrier row of `stride_words`
+    floats (rounded up to 16 words) and `state_words` hand-over words.  Allocates env._split_rows / env._split_state, points the given STEP buffer structs at them, and
+    tells the standing lane (when the environment has one by now) that the fast launch has `parts` times the workgroups: its polling workgroups wait for EVERY one of them
+    (grx_overflow_lane.progress_total)."""
+    import torch
+
+    stride = -(-int(stride_words) // 16) * 16
+    env._split_rows = torch.zeros(env.num_envs, stride, dtype=torch.float32, device=env.device)
+    env._split_state = torch.zeros(env.num_envs, state_words, dtype=torch.int32, device=env.device)
+    for b in bufs:
+        setattr(b, rows_field, env._split_rows.data_ptr())
+        setattr(b, stride_field, stride)
+        b.split_state, b.split_parts = env._split_state.data_ptr(), parts
+    if getattr(env, "lane", None) is not None:
+        env.lane._fast_grid *= parts
+
+
+def launch_step(env, bufs, fast_call, large_call, *, timed_kernel, timed_group, use_lane, launch_lane=None):
+    """The launch group of one step on torch's current stream.  fast_call(b) / large_call(b) enqueue ONE library call on the buffer struct b: the family's step kernel on its fast
+    tables and on the overflow lane's.  use_lane: through env.lane (OverflowLane.step: fast launch + the lane's launches; launch_lane: the standing lane's kernel where it is not
+    large_call), else the plain fast launch.  timed_kernel: a (start, end) event pair around every fast launch goes to env.kernel_events; timed_group: one around the whole group
+    (the step's device time) to env.step_events.  The masked struct carries env.mask."""
+    import torch
+
+    fast = fast_call
+    if timed_kernel:
+        def fast(b):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fast_call(b)
+            e1.record()
+            env.kernel_events.append((e0, e1))
+
+    if not use_lane:
+        fast(bufs)
+        return
+    if timed_group:
+        l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        l0.record()
+    env.lane.step(env.mask if bufs is env._bufs_masked else None, fast, large_call, fast_bufs=bufs, launch_lane=launch_lane)
+    if timed_group:
+        l1.record()
+        env.step_events.append((l0, l1))
 
 
 def create_rerun_model(L, model, device_index, enabled=True, capacity=None):

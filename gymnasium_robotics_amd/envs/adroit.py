@@ -10,14 +10,13 @@ body_quat / site_pos) are per-world state here (`shift`, `target`: adroit_spec.s
 """
 import ctypes
 import os
-import weakref
 from typing import Optional
 
 import numpy as np
 import torch
 
 from .. import _native
-from ..core import cost_order_alloc, cost_order_update, create_rerun_model, GoalVecEnv, OverflowLane, PinnedStager, np_random
+from ..core import cost_order_alloc, cost_order_update, create_rerun_model, GoalVecEnv, launch_step, OverflowLane, PinnedStager, np_random, seed_rows, split_alloc
 from ..mjcf import CompiledModel
 from ..spaces import Box, batch_space
 from .adroit_spec import IDENTITY_SHIFT, MAX_EPISODE_STEPS, SPECS, action_scaling, group_shift, load_adroit_model, make_adroit_task, parse_adroit_id, sample_reset_batch
@@ -80,12 +79,7 @@ class AdroitVecEnv(GoalVecEnv):
         # Bit-identical to the plain launch (tests/test_gpu_adroit.py::test_split_step_is_the_plain_step).  GRX_ADROIT_SPLIT=P (1: off).
         self._split = max(1, min(int(self.task.n_substeps), 8, int(os.environ.get("GRX_ADROIT_SPLIT", ADROIT_SPLIT_PARTS if n > 2048 else 1)))) if n >= 64 else 1
         if self._split > 1:
-            stride = -(-(self.nq + 2 * self.nv) // 16) * 16
-            self._split_rows, self._split_state = z(n, stride), z(n, 4, dtype=torch.int32)
-            for b in (self._bufs, self._bufs_masked):
-                b.split_rows, b.split_state, b.split_stride, b.split_parts = self._split_rows.data_ptr(), self._split_state.data_ptr(), stride, self._split
-            if self.lane is not None:
-                self.lane._fast_grid *= self._split      # (polling workgroups of the standing lane wait for EVERY workgroup of the fast launch: grx_overflow_lane.progress_total)
+            split_alloc(self, self._split, self.nq + 2 * self.nv, 4, (self._bufs, self._bufs_masked))
         self.single_action_space = Box(-1.0, 1.0, (self.nu,), np.float32)                      # adroit_hammer.py:231-233
         self.single_observation_space = Box(-np.inf, np.inf, (self.obs_dim,), np.float64)      # :205-207
         self.action_space = batch_space(self.single_action_space, n)
@@ -131,12 +125,7 @@ class AdroitVecEnv(GoalVecEnv):
 
     def _seed_worlds(self, seeds):
         """one numpy PCG64 per world, seeded like gymnasium.utils.seeding.np_random [3P]; only the raw 128-bit (state, inc) pairs are kept, on the device"""
-        st = np.zeros((self.num_envs, 4), np.uint64)
-        mask = (1 << 64) - 1
-        for i, sd in enumerate(seeds):
-            s = np_random(sd)[0].bit_generator.state["state"]
-            st[i] = [s["state"] >> 64, s["state"] & mask, s["inc"] >> 64, s["inc"] & mask]
-        self._rng_dev = torch.from_numpy(st.view(np.int64)).to(self.device)
+        self._rng_dev = torch.from_numpy(seed_rows(seeds).view(np.int64)).to(self.device)
 
     # model.body_pos / body_quat of every world as the reference's get_env_state reports it (float64 [N, 3 or 4]); reading it from a device-draw task synchronises
     @property
@@ -161,10 +150,6 @@ class AdroitVecEnv(GoalVecEnv):
         """hammer: model.body_pos[nail_board, 2] of every world"""
         return self.model_edit[:, 2]
 
-    def _lane_make_bufs(self):
-        me = weakref.ref(self)      # (the lane must not keep the environment alive: its native model slots are released by __del__)
-        return lambda m: me()._make_bufs(m)
-
     def _make_bufs(self, mask):
         b = _native.AdroitBuffersStruct()
         for name in ("qpos", "qvel", "qacc_ws", "shift", "action", "obs", "reward", "success", "status"):
@@ -174,32 +159,10 @@ class AdroitVecEnv(GoalVecEnv):
         b.mask = None if mask is None else mask.data_ptr()
         return b
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _launch(self, bufs, forward_only):
-        def fast(b):
-            timed = self.kernel_events is not None and not forward_only
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            _native.check(self._L.grx_adroit_step(self._h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, int(forward_only), self._stream()))
-            if timed:
-                e1.record()
-                self.kernel_events.append((e0, e1))
-
-        if self.lane is not None and not forward_only:
-            large = lambda b: _native.check(self._L.grx_adroit_step(self._h_big, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, 0, self._stream()))
-            timed_all = self.kernel_events is not None and not forward_only      # the fast launch AND the lane's launches (side stream, joined before the entry launch): the step's device time
-            if timed_all:
-                l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                l0.record()
-            self.lane.step(self.mask if bufs is self._bufs_masked else None, fast, large, fast_bufs=bufs)
-            if timed_all:
-                l1.record()
-                self.step_events.append((l0, l1))
-        else:
-            fast(bufs)
+        on = lambda h, fwd: (lambda b: _native.check(self._L.grx_adroit_step(h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, fwd, self._stream())))
+        timed = self.kernel_events is not None and not forward_only      # (the group: the fast launch AND the lane's launches -- side stream, joined before the entry launch: the step's device time)
+        launch_step(self, bufs, on(self._h, int(forward_only)), on(self._h_big, 0), timed_kernel=timed, timed_group=timed, use_lane=self.lane is not None and not forward_only)
         if self.balance and not forward_only:
             cost_order_update(self, self.balance_alpha)
 
@@ -400,20 +363,6 @@ class AdroitVecEnv(GoalVecEnv):
             self.qvel.copy_(torch.from_numpy(np.asarray(state_dict["qvel"], dtype=np.float32)).to(self.device))
             self.qacc_ws.zero_()
             self._launch(self._bufs, True)   # set_state -> mj_forward
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _native.release_model(self._h)
-            self._h = None
-        if getattr(self, "_h_big", None):
-            _native.release_model(self._h_big)
-            self._h_big = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 AdroitHammerVecEnv = AdroitVecEnv   # round-1/2 name of the class

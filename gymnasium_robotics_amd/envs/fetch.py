@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..core import create_rerun_model, GoalVecEnv, OverflowLane, np_random
+from ..core import cost_order_alloc, create_rerun_model, GoalVecEnv, launch_step, OverflowLane, seed_rows, split_alloc
 from ..mjcf import CompiledModel, compile_mjcf, load_model
 from ..spaces import Box, Dict, batch_space
 from .fetch_spec import DISTANCE_THRESHOLD, FETCH_TASKS, MAX_EPISODE_STEPS, N_SUBSTEPS, make_fetch_task, parse_env_id
@@ -151,30 +151,12 @@ class FetchVecEnv(GoalVecEnv):
         self.step_events = None    # ... and [] to collect the pairs around the whole launch group of a step (fast launch + the serialised re-run of the worlds that overflowed its tables)
 
     def _launch_step(self, bufs):
-        def fast(b):
-            ev = self.kernel_events
-            if ev is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            _native.check(self._L.grx_fetch_step(self._h_fast or self._h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, self._stream()))
-            if ev is not None:
-                e1.record()
-                ev.append((e0, e1))
-
-        if self.lane is None:
-            fast(bufs)
-        else:
-            large = lambda b: _native.check(self._L.grx_fetch_step(self._h_big, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, self._stream()))
-            # with the fast kernel: the standing lane (hull worlds, worlds near a capacity of the fast tables) runs the model's own kernel on FETCH_CAPACITY
-            middle = (lambda b: _native.check(self._L.grx_fetch_step(self._h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, self._stream()))) if self._h_fast else None
-            timed = self.kernel_events is not None and self.step_events is not None      # the fast launch AND the re-run of the worlds that overflowed its tables (behind it, same stream)
-            if timed:
-                l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                l0.record()
-            self.lane.step(self.mask if bufs is self._bufs_masked else None, fast, large, fast_bufs=bufs, launch_lane=middle)
-            if timed:
-                l1.record()
-                self.step_events.append((l0, l1))
+        on = lambda h: (lambda b: _native.check(self._L.grx_fetch_step(h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, self._stream())))
+        timed = self.kernel_events is not None
+        # with the fast kernel: the standing lane (hull worlds, worlds near a capacity of the fast tables) runs the model's own kernel on FETCH_CAPACITY
+        # (timed_group: the fast launch AND the re-run of the worlds that overflowed its tables, behind it on the same stream)
+        launch_step(self, bufs, on(self._h_fast or self._h), on(self._h_big), timed_kernel=timed, timed_group=timed and self.step_events is not None,
+                    use_lane=self.lane is not None, launch_lane=on(self._h) if self._h_fast else None)
         if self.balance:
             if self._defer_order:      # fused tail: the launch that commits this step's reset rows sorts the next order as well (step())
                 self._order_pending = True
@@ -194,7 +176,8 @@ class FetchVecEnv(GoalVecEnv):
         # and the next launch starts the expensive worlds first.  A world's cost is strongly correlated from one step to the next (it is
         # in contact or it is not), and with ~2 worlds per resident wave slot the launch otherwise ends with a few slots finishing two
         # expensive worlds while the rest of the chip idles.  Worlds stay inside their XCD's slice (L2 locality of neighbouring rows).
-        self.balance = bool(self.balance) and n % 8 == 0 and 1024 <= n <= 65536 * 8   # grx_order_by_cost sorts one XCD slice (n / 8 worlds, <= 65536) per workgroup in LDS
+        self.cost = self.cost_ema = self.order = None
+        self.balance = bool(self.balance) and cost_order_alloc(self, n, d)      # (the step structs take order / cost from _make_bufs below)
         self._reset_stage = z(n, 6)   # device side of the reset staging buffer (see _reset_worlds)
         # Fused tail (include/grx_capi.h grx_fetch_post_step): in same-step mode ONE launch behind the step launch sorts the next dispatch order, commits the overlapped reset and
         # writes the terminal rows of info["final_obs"] compactly -- instead of the order kernel, the commit kernel and a gather.  GRX_FETCH_FUSED_TAIL=0: those launches (A/B, tests).
@@ -205,23 +188,16 @@ class FetchVecEnv(GoalVecEnv):
         self.step_reset_list = None
         self.packed = z(n, self.obs_dim + 8)   # [obs | achieved | desired | reward | success] rows written by the step kernel (cross-rank gather, parallel.py)
         self.final_packed = z(n, self.obs_dim + 8)   # same-step autoreset: row w = the TERMINAL packed row of world w's last finished episode (info["final_obs"], HerReplay.append(final_rows=...))
-        self.cost = torch.zeros(n, dtype=torch.int32, device=d) if self.balance else None
-        self.cost_ema = torch.zeros(n, dtype=torch.float32, device=d) if self.balance else None
         self.balance_alpha = float(os.environ.get("GRX_BALANCE_ALPHA", 0.1))   # weight of the newest sample in the moving average the order is sorted by (A/B on FetchPickAndPlace: 1.0 -> 2.69 ms, 0.15 -> 2.64 ms per step)
-        self.order = None
         # wave slots of one XCD (32 CUs): worlds per CU = what the LDS footprint allows (1 280-byte granules of 160 KB), at most the 8 waves a 2-waves-per-SIMD kernel gets;
         # grx_order_by_cost_slots uses it in the two-worlds-per-slot regime (4096 worlds on 2048 slots), GRX_TAIL_ORDER=0 restores the plain descending order
         self._slots_per_xcd = 32 * min(12 if self._h_fast else 8, (160 * 1024) // (-(-self.lds_bytes // 1280) * 1280)) if (self.balance and os.environ.get("GRX_TAIL_ORDER", "1") != "0") else 0
-        if self.balance:
-            per = n // 8
-            self._slice_base = (torch.arange(8, device=d, dtype=torch.int32) * per).unsqueeze(1)          # [8,1]
-            self.order = (self._slice_base + torch.arange(per, device=d, dtype=torch.int32).unsqueeze(0)).t().contiguous().view(-1)   # workgroup b -> slice b & 7, position b >> 3
         # the worlds' caches of separating directions (hull-vs-convex pairs), carried across launches: without it every env.step() starts with one portal
         # search for the arm's permanently near pair (torso / shoulder link, 1.9 cm apart); a stale row is harmless (directions are re-verified)
         self.hullcache = z(n, 90) if os.environ.get("GRX_NO_HULLCACHE") is None else None      # GRX_HULLCACHE_WORDS (csrc/grx_engine.h)
         # No dropped contacts (core.OverflowLane / include/grx_capi.h grx_overflow_lane): a world that exceeds a table capacity of the specialised kernel writes
         # nothing and is stepped on the SAME model with larger tables (generic kernel) -- concurrently with the fast launch once it is in the lane.
-        common = (self.qpos, self.qvel, self.qacc_ws, self.mocap, self.aux, self.goal, self.action, self.obs, self.achieved, self.reward, self.success, self.status)
+        common = tuple(getattr(self, k) for k in self._COMMON)
         # mid-step hand-off rows (include/grx_capi.h grx_fetch_buffers.handoff): [substep + 1 | status | ctrl | mocap | qpos | qvel | warm start], 16-word aligned; all zero between steps
         self.handoff, self._handoff_stride = None, 0
         if getattr(self, "_h_fast", None):
@@ -231,8 +207,8 @@ class FetchVecEnv(GoalVecEnv):
         self._bufs_masked = self._make_bufs(*common, self.mask, self.order, self.cost, self.packed, self.hullcache, self.handoff)
         self._bufs.handoff_stride = self._bufs_masked.handoff_stride = self._handoff_stride
         # site frames only in the pass the outputs read (include/grx_capi.h grx_fetch_buffers.sites_every_substep); GRX_FETCH_SITES_EVERY_SUBSTEP=1: in every pass (A/B, tests)
-        sites_every = int(os.environ.get("GRX_FETCH_SITES_EVERY_SUBSTEP", "0") != "0")
-        self._bufs.sites_every_substep = self._bufs_masked.sites_every_substep = sites_every
+        self._sites_every = int(os.environ.get("GRX_FETCH_SITES_EVERY_SUBSTEP", "0") != "0")
+        self._bufs.sites_every_substep = self._bufs_masked.sites_every_substep = self._sites_every
         # SPLIT STEP (include/grx_capi.h grx_fetch_buffers.split_parts): the step launch has P workgroups per world, each running 1 / P of the substeps (the state travels through the
         # world's hand-off row): the launch's tail -- the duration of the LAST workgroup started, a whole world-step otherwise -- shrinks to 1 / P of it.  Bit-identical to the unsplit
         # launch (tests/test_gpu_fetch.py::test_split_step_is_the_plain_step).  GRX_FETCH_SPLIT=P (1: off); not combined with the hull-less fast kernel.
@@ -241,26 +217,17 @@ class FetchVecEnv(GoalVecEnv):
         # parts, 8 192: 1.540 -> 1.667 / 1.683 / 1.698 / 1.696 M, 16 384: 1.724 -> 1.796 / 1.795 / 1.789 / 1.778 M.  (With agent-scope fences in the hand-off -- the first version,
         # profiles/ab_r06_fetch_split.txt -- every part wrote the XCD's L2 back: 2 parts 1.382 M @4 096, more parts lost.)
         self._split = max(1, int(os.environ.get("GRX_FETCH_SPLIT", str((FETCH_SPLIT_PARTS if n <= FETCH_SPLIT_WIDE else 2) if n > 2048 else 1)))) if self.handoff is None and n >= 64 else 1
-        if self._split > 1:
-            stride = -(-(2 + self.model.dim("nu") + 7 * self.nmocap + self.nq + 2 * self.nv) // 16) * 16
-            self._split_rows, self._split_state = z(n, stride), z(n, 2, dtype=torch.int32)
-            for b in (self._bufs, self._bufs_masked):
-                b.handoff, b.handoff_stride, b.split_state, b.split_parts = self._split_rows.data_ptr(), stride, self._split_state.data_ptr(), self._split
+        if self._split > 1:      # (the hand-off row is the carrier; the entry-mode lane below has no polling workgroups to tell about the larger grid)
+            split_alloc(self, self._split, 2 + self.model.dim("nu") + 7 * self.nmocap + self.nq + 2 * self.nv, 2, (self._bufs, self._bufs_masked),
+                        rows_field="handoff", stride_field="handoff_stride")
         self.lane = None
         if self._h_big is not None:
-            packed, hullcache, handoff, stride, mk = self.packed, self.hullcache, self.handoff, self._handoff_stride, FetchVecEnv._make_bufs      # (no reference to self: the lane must not keep the environment alive)
-
-            def lane_bufs(m):
-                b = mk(*common, m, None, None, packed, hullcache, handoff)
-                b.handoff_stride, b.sites_every_substep = stride, sites_every
-                return b
-
-            if handoff is not None:
+            if self.handoff is not None:
                 # hull activity persists for a few steps and 8 % of a stationary batch shows it: a STANDING lane with polling workgroups for the ~1 % of the worlds that enter per step
-                self.lane = OverflowLane(n, d, self._fast_model, lane_bufs, mode="lane", handoff=True, poll_grid=int(os.environ.get("GRX_FETCH_POLL", max(64, n // 32))),
+                self.lane = OverflowLane(n, d, self._fast_model, self._lane_make_bufs(), mode="lane", handoff=True, poll_grid=int(os.environ.get("GRX_FETCH_POLL", max(64, n // 32))),
                                          ttl=int(os.environ.get("GRX_FETCH_TTL", 4)), margin=0.9)
             else:
-                self.lane = OverflowLane(n, d, self.model, lane_bufs, mode="entry")     # overflows are rare events here (0.0007 % of the world-steps)
+                self.lane = OverflowLane(n, d, self.model, self._lane_make_bufs(), mode="entry")     # overflows are rare events here (0.0007 % of the world-steps)
         # Overlapped same-step reset (include/grx_capi.h, grx_fetch_commit_rows): Fetch episodes end by the time limit only, so the worlds a step will reset are known before
         # it is launched and their reset state depends on nothing the step computes.  The reset kernel runs for them on a side stream, beside the step kernel, into this second
         # set of world rows; ONE small kernel behind the step commits them (parks the terminal rows, copies the staged ones).  The in-line reset (88 us of a 3.3 ms step at
@@ -285,8 +252,13 @@ class FetchVecEnv(GoalVecEnv):
             setattr(b, name, None if t is None else t.data_ptr())
         return b
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    _COMMON = ("qpos", "qvel", "qacc_ws", "mocap", "aux", "goal", "action", "obs", "achieved", "reward", "success", "status")      # the leading fields of every buffer struct of an environment
+
+    def _make_lane_bufs(self, mask):
+        """the lane's launches: no cost order (they run a handful of worlds), no split"""
+        b = self._make_bufs(*(getattr(self, k) for k in self._COMMON), mask, None, None, self.packed, self.hullcache, self.handoff)
+        b.handoff_stride, b.sites_every_substep = self._handoff_stride, self._sites_every
+        return b
 
     # ------------------------------------------------------------------ construction (fetch_env.py:404-428)
     def _env_setup(self):
@@ -323,12 +295,7 @@ class FetchVecEnv(GoalVecEnv):
     def _seed_worlds(self, seeds):
         """One numpy PCG64 per world, seeded like gymnasium.utils.seeding.np_random [3P]; only the raw 128-bit (state, inc) pairs are kept, ON THE DEVICE: the
         streams are advanced by grx_fetch_sample_resets_device (bit-exact with numpy's Generator.uniform), the host never draws."""
-        st = np.zeros((self.num_envs, 4), np.uint64)
-        mask = (1 << 64) - 1
-        for i, sd in enumerate(seeds):
-            s = np_random(sd)[0].bit_generator.state["state"]
-            st[i] = [s["state"] >> 64, s["state"] & mask, s["inc"] >> 64, s["inc"] & mask]
-        self._rng_dev = torch.from_numpy(st.view(np.int64)).to(self.device)
+        self._rng_dev = torch.from_numpy(seed_rows(seeds).view(np.int64)).to(self.device)
 
     @property
     def _rng_state(self):
@@ -546,20 +513,3 @@ class FetchVecEnv(GoalVecEnv):
         return np.zeros(np.asarray(achieved_goal).shape[:-1], bool)  # robot_env.py:110-112
 
     # checkpoint / resume: core.GoalVecEnv.get_state / set_state (state rows, the device-resident PCG64 streams, TimeLimit counters, hull caches, dispatch order, lane)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _native.release_model(self._h)
-            self._h = None
-        if getattr(self, "_h_big", None):
-            _native.release_model(self._h_big)
-            self._h_big = None
-        if getattr(self, "_h_fast", None):
-            _native.release_model(self._h_fast)
-            self._h_fast = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

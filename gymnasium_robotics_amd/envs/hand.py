@@ -7,7 +7,6 @@ observations (observation 63 = 24 joint positions | 24 joint velocities | 5 fing
 steps, never terminated.  One call of `step` = one launch of `grx_hand_step_kernel` (set_action + 20 substeps + obs + reward).
 """
 import ctypes
-import weakref
 import os
 from typing import Optional
 
@@ -15,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..core import create_rerun_model, GoalVecEnv, OverflowLane, PinnedStager, np_random
+from ..core import cost_order_alloc, cost_order_update, create_rerun_model, GoalVecEnv, launch_step, OverflowLane, PinnedStager, np_random, split_alloc
 from ..mjcf import CompiledModel, compile_mjcf, load_model
 from ..spaces import Box, Dict, batch_space
 from .hand_spec import (DISTANCE_THRESHOLD, MAX_EPISODE_STEPS, N_ACTIONS, initial_qpos_vector, make_hand_task, parse_hand_reach_id,
@@ -92,15 +91,9 @@ class HandReachVecEnv(GoalVecEnv):
         # cost-ordered dispatch (see FetchVecEnv._alloc / include/grx_capi.h): the worlds that took longest in the last launch start first.
         # Off by default for the hand: measured neutral to -1.5 % (16 384 worlds are 8 per wave slot, the tail is short; at 4 096 the cost of a
         # world under random finger motion is not persistent enough to pay for the argsort)
-        self.balance = bool(balance) and n % 8 == 0 and 1024 <= n <= 65536 * 8
-        self.cost = torch.zeros(n, dtype=torch.int32, device=d) if self.balance else None
-        self.cost_ema = torch.zeros(n, dtype=torch.float32, device=d) if self.balance else None
+        self.cost = self.cost_ema = self.order = None
         self.balance_alpha = 0.1   # weight of the newest sample in the moving average the order is sorted by (A/B on FetchPickAndPlace: 1.0 -> 2.69 ms, 0.15 -> 2.64 ms per step)
-        self.order = None
-        if self.balance:
-            per = n // 8
-            self._slice_base = (torch.arange(8, device=d, dtype=torch.int32) * per).unsqueeze(1)
-            self.order = (self._slice_base + torch.arange(per, device=d, dtype=torch.int32).unsqueeze(0)).t().contiguous().view(-1)
+        self.balance = bool(balance) and cost_order_alloc(self, n, d)      # (_make_bufs points the step structs at order / cost)
         self._bufs, self._bufs_masked = self._make_bufs(None), self._make_bufs(self.mask)
         # no dropped contacts: the worlds that exceed a table capacity of the fast kernel are stepped on larger tables (core.OverflowLane)
         # (with the entrants picked up by polling workgroups a smaller standing lane is cheaper: margin 0.9 / ttl 4 against 0.8 / 8, +1 % on hand + touch, profiles/ab_r03_lane_size_with_polling.txt)
@@ -109,12 +102,7 @@ class HandReachVecEnv(GoalVecEnv):
         # GRX_HAND_SPLIT=P (1: off).  Bit-identical to the plain launch (tests/test_gpu_hand.py::test_split_step_is_the_plain_step).
         self._split = max(1, min(int(self.task.n_substeps), 8, int(os.environ.get("GRX_HAND_SPLIT", HAND_SPLIT_PARTS.get(type(self).__name__, 1) if n > 2048 else 1)))) if n >= 64 else 1
         if self._split > 1:
-            stride = -(-(self.nq + 2 * self.nv) // 16) * 16
-            self._split_rows, self._split_state = z(n, stride), z(n, 4, dtype=torch.int32)
-            for b in (self._bufs, self._bufs_masked):
-                b.split_rows, b.split_state, b.split_stride, b.split_parts = self._split_rows.data_ptr(), self._split_state.data_ptr(), stride, self._split
-            if self.lane is not None:
-                self.lane._fast_grid *= self._split      # (polling workgroups of the standing lane wait for EVERY workgroup of the fast launch)
+            split_alloc(self, self._split, self.nq + 2 * self.nv, 4, (self._bufs, self._bufs_masked))
         self.single_action_space = Box(-1.0, 1.0, (self.nu,), np.float32)
         self.single_observation_space = Dict(dict(
             observation=Box(-np.inf, np.inf, (self.obs_dim,), np.float64), achieved_goal=Box(-np.inf, np.inf, (GOAL_DIM,), np.float64),
@@ -150,9 +138,8 @@ class HandReachVecEnv(GoalVecEnv):
     def _obs_dim(self):
         return self.nq + self.nv + self.GOAL_DIM
 
-    def _lane_make_bufs(self):
-        me = weakref.ref(self)      # (the lane must not keep the environment alive: its native model slots are released by __del__)
-        return lambda m: me()._make_bufs(m, large=True)
+    def _make_lane_bufs(self, mask):
+        return self._make_bufs(mask, large=True)
 
     def _make_bufs(self, mask, large=False):
         """large: buffers of a launch of the large-table kernel of the overflow lane (no cost ordering: it runs a handful of worlds)"""
@@ -164,44 +151,21 @@ class HandReachVecEnv(GoalVecEnv):
         b.cost = None if (self.cost is None or large) else self.cost.data_ptr()
         return b
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _launch(self, bufs, forward_only, settle=False):
         """settle: a reset-time settle launch of the step kernel (manipulate.py:205-224) -- not a timed env.step(), no cost re-ordering."""
         own = bufs is self._bufs or bufs is self._bufs_masked      # the side arenas of the overlapped settle chains carry their own structs (no lane: a handful of freshly reset worlds)
-        large = lambda b: _native.check(self._L.grx_hand_step(self._h_big, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, 0, self._stream()))
+        on = lambda h, fwd: (lambda b: _native.check(self._L.grx_hand_step(h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, fwd, self._stream())))
+        fast, large = on(self._h, 0 if settle else int(forward_only)), on(self._h_big, 0)
         if settle:
-            fast = lambda b: _native.check(self._L.grx_hand_step(self._h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, 0, self._stream()))
             if self.lane is not None and own:
                 self.lane.rerun_only(self.mask if bufs is self._bufs_masked else None, bufs, fast, large)     # every masked world is stepped by the fast kernel, whatever lane it is in; an overflow is re-run at once
             else:
                 fast(bufs)
             return
-
-        def fast(b):
-            timed = self.kernel_events is not None and not forward_only
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            _native.check(self._L.grx_hand_step(self._h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, int(forward_only), self._stream()))
-            if timed:
-                e1.record()
-                self.kernel_events.append((e0, e1))
-
-        if self.lane is not None and own and not forward_only:
-            timed_all = self.kernel_events is not None and not forward_only      # the fast launch AND the lane's launches (side stream, joined before the entry launch): the step's device time
-            if timed_all:
-                l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                l0.record()
-            self.lane.step(self.mask if bufs is self._bufs_masked else None, fast, large, fast_bufs=bufs)
-            if timed_all:
-                l1.record()
-                self.step_events.append((l0, l1))
-        else:
-            fast(bufs)
+        timed = self.kernel_events is not None and not forward_only      # (the group: the fast launch AND the lane's launches -- side stream, joined before the entry launch: the step's device time)
+        launch_step(self, bufs, fast, large, timed_kernel=timed, timed_group=timed, use_lane=self.lane is not None and own and not forward_only)
         if self.balance and not forward_only:
-            _native.check(self._L.grx_order_by_cost(self.cost.data_ptr(), self.cost_ema.data_ptr(), self.balance_alpha, self.num_envs, self.order.data_ptr(), self._stream()))
+            cost_order_update(self, self.balance_alpha)
 
     # ------------------------------------------------------------------ _env_setup (reach.py:408-416) on the device
     def _env_setup(self):
@@ -380,20 +344,6 @@ class HandReachVecEnv(GoalVecEnv):
             chains.append(dict(worlds=c["worlds"].copy(), ti=self._dev_index(c["worlds"]), lo=c["lo"], k=c["k"], due_at=c["due_at"], ready=ev, event=ev, ok=None if c["ok"] is None else c["ok"].copy(),
                                rng_states=c["rng_states"], obj_host=buf))
         self._chains = chains
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _native.release_model(self._h)
-            self._h = None
-        if getattr(self, "_h_big", None):
-            _native.release_model(self._h_big)
-            self._h_big = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # Engine capacities of the hand + object models.  With split dof spans a finger-object row takes 12-20 pool words (6 rows per condim-4

@@ -16,14 +16,13 @@ leading world axis.  reward = number of still-open tasks completed in this step;
 (terminate_on_tasks_completed).
 """
 import ctypes
-import weakref
 from typing import Optional
 
 import numpy as np
 import torch
 
 from .. import _native
-from ..core import KITCHEN_RERUN_CAPACITY, cost_order_alloc, cost_order_update, create_rerun_model, GoalVecEnv, OverflowLane, np_random
+from ..core import KITCHEN_RERUN_CAPACITY, cost_order_alloc, cost_order_update, create_rerun_model, GoalVecEnv, launch_step, OverflowLane, seed_rows, split_alloc
 from ..mjcf import CompiledModel
 from ..spaces import Box, Dict, batch_space
 from .kitchen_spec import (INIT_QPOS, MAX_EPISODE_STEPS, OBS_DIM, OBS_ELEMENT_GOALS, OBS_ELEMENT_INDICES, TASKS, load_kitchen_model, make_kitchen_task, task_mask)
@@ -88,12 +87,7 @@ class KitchenVecEnv(GoalVecEnv):
         # GRX_KITCHEN_SPLIT=P (1: off).  Bit-identical to the plain launch (tests/test_gpu_kitchen.py::test_split_step_is_the_plain_step).
         self._split = max(1, min(8, int(os.environ.get("GRX_KITCHEN_SPLIT", KITCHEN_SPLIT_PARTS if n > 2048 else 1)))) if n >= 64 else 1
         if self._split > 1:
-            stride = -(-(self.nq + 2 * self.nv) // 16) * 16
-            self._split_rows, self._split_state = z(n, stride), z(n, 4, dtype=torch.int32)
-            for b in (self._bufs, self._bufs_masked):
-                b.split_rows, b.split_state, b.split_stride, b.split_parts = self._split_rows.data_ptr(), self._split_state.data_ptr(), stride, self._split
-            if self.lane is not None:
-                self.lane._fast_grid *= self._split      # (polling workgroups of the standing lane wait for EVERY workgroup of the fast launch)
+            split_alloc(self, self._split, self.nq + 2 * self.nv, 4, (self._bufs, self._bufs_masked))
         self.single_action_space = Box(-1.0, 1.0, (self.nu,), np.float64)                     # franka_env.py:88
         goal_space = Dict({t: Box(-np.inf, np.inf, OBS_ELEMENT_GOALS[t].shape, np.float64) for t in self.tasks})
         self.single_observation_space = Dict(dict(desired_goal=goal_space, achieved_goal=Dict(dict(goal_space)),
@@ -132,10 +126,6 @@ class KitchenVecEnv(GoalVecEnv):
         self.step_events = []      # (start, end) HIP events around the whole launch group of a step: fast kernel + the overflow lane's launches
         self.kernel_events = None
 
-    def _lane_make_bufs(self):
-        me = weakref.ref(self)      # (the lane must not keep the environment alive: its native model slots are released by __del__)
-        return lambda m: me()._make_bufs(m)
-
     def _make_bufs(self, mask):
         b = _native.KitchenBuffersStruct()
         for name in ("qpos", "qvel", "qacc_ws", "last_qpos", "action", "obs", "completed", "status"):
@@ -146,16 +136,9 @@ class KitchenVecEnv(GoalVecEnv):
             b.skin, b.skin_stride, b.skin_radius = self._skin.data_ptr(), self._skin.shape[1], self.skin_radius
         return b
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ------------------------------------------------------------------ per-world numpy PCG64 streams, advanced in C
     def _seed_worlds(self, seeds):
-        st, mask = np.zeros((self.num_envs, 4), np.uint64), (1 << 64) - 1
-        for i, sd in enumerate(seeds):
-            s = np_random(sd)[0].bit_generator.state["state"]
-            st[i] = [s["state"] >> 64, s["state"] & mask, s["inc"] >> 64, s["inc"] & mask]
-        self._rng_state = st
+        st = self._rng_state = seed_rows(seeds)
         self._noise_uploaded = None
         if self._device_path:
             self.d_rng.copy_(torch.from_numpy(st.view(np.int64)))      # the streams live on the device from here on (grx_uniform_rows_device)
@@ -192,28 +175,9 @@ class KitchenVecEnv(GoalVecEnv):
             self._noise_host[torch.from_numpy(idx64)] = torch.from_numpy(rows)
 
     def _launch(self, bufs, forward_only):
-        def fast(b):
-            timed = self.kernel_events is not None and not forward_only
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            _native.check(self._L.grx_kitchen_step(self._h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, int(forward_only), self._stream()))
-            if timed:
-                e1.record()
-                self.kernel_events.append((e0, e1))
-
-        if self.lane is not None and not forward_only:
-            large = lambda b: _native.check(self._L.grx_kitchen_step(self._h_big, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, 0, self._stream()))
-            timed_all = self.kernel_events is not None and not forward_only      # the fast launch AND the lane's launches (side stream, joined before the entry launch): the step's device time
-            if timed_all:
-                l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                l0.record()
-            self.lane.step(self.mask if bufs is self._bufs_masked else None, fast, large, fast_bufs=bufs)
-            if timed_all:
-                l1.record()
-                self.step_events.append((l0, l1))
-        else:
-            fast(bufs)
+        on = lambda h, fwd: (lambda b: _native.check(self._L.grx_kitchen_step(h, ctypes.byref(self.task), ctypes.byref(b), self.num_envs, fwd, self._stream())))
+        timed = self.kernel_events is not None and not forward_only      # (the group: the fast launch AND the lane's launches -- side stream, joined before the entry launch: the step's device time)
+        launch_step(self, bufs, on(self._h, int(forward_only)), on(self._h_big, 0), timed_kernel=timed, timed_group=timed, use_lane=self.lane is not None and not forward_only)
         if self.balance and not forward_only:
             cost_order_update(self)
 
@@ -426,20 +390,6 @@ class KitchenVecEnv(GoalVecEnv):
 
     def compute_truncated(self, achieved_goal, desired_goal, info=None):
         return np.zeros(np.asarray(next(iter(achieved_goal.values()))).shape[:-1], bool)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _native.release_model(self._h)
-            self._h = None
-        if getattr(self, "_h_big", None):
-            _native.release_model(self._h_big)
-            self._h_big = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _popcount(x):

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from ..core import GoalVecEnv, np_random
+from ..core import GoalVecEnv, np_random, seed_rows
 from ..mjcf import CompiledModel, compile_mjcf, load_model
 from ..spaces import Box, Dict, batch_space
 from .maze_spec import (redraw_goal, ANT_FRAME_SKIP, ANT_MAZE_HEIGHT, ANT_MAZE_SIZE_SCALING, GOAL_RADIUS, MAPS, POINT_MAZE_HEIGHT, POINT_MAZE_SIZE_SCALING, Maze,
@@ -145,17 +145,9 @@ class PointMazeVecEnv(GoalVecEnv):
         b.mask = None if mask is None else mask.data_ptr()
         return b
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _seed_worlds(self, seeds):
         """one numpy PCG64 per world, seeded like gymnasium.utils.seeding.np_random [3P]; the raw (state, inc) pairs and the empty 32-bit buffer go to the device"""
-        st = np.zeros((self.num_envs, 5), np.uint64)
-        mask = (1 << 64) - 1
-        for i, sd in enumerate(seeds):
-            s = np_random(sd)[0].bit_generator.state
-            st[i] = [s["state"]["state"] >> 64, s["state"]["state"] & mask, s["state"]["inc"] >> 64, s["state"]["inc"] & mask, (int(s["has_uint32"]) << 32) | int(s["uinteger"])]
-        self._rng_dev = torch.from_numpy(st.view(np.int64)).to(self.device)
+        self._rng_dev = torch.from_numpy(seed_rows(seeds, buffered=True).view(np.int64)).to(self.device)
 
     def _sample_on_device(self, idx, options):
         """index list through pinned memory, the draws by one kernel into the staging rows grx_maze_reset_rows reads; nothing waits"""
@@ -325,17 +317,6 @@ class PointMazeVecEnv(GoalVecEnv):
 
     def compute_truncated(self, achieved_goal, desired_goal, info=None):
         return np.zeros(np.asarray(achieved_goal).shape[:-1], bool)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _native.release_model(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class AntMazeVecEnv(PointMazeVecEnv):

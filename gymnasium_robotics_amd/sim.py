@@ -177,13 +177,13 @@ class BatchedSim:
         import torch
 
         from . import _native
+        from .core import stream_ptr
 
         self._ensure()
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            stream = lambda: ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream())))
+            go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream_ptr(self.device))))
             self._bufs.mask = None if m is None else m.data_ptr()
             if self.lane is None:
                 go(self._h)(self._bufs)
@@ -231,9 +231,9 @@ class BatchedSim:
         return self._ensure()["status_words"].view(torch.int16).view(-1, 2)[:, 1]
 
     def status_counts(self):
-        st = (self._ensure()["status_words"] >> 16).cpu().numpy()
-        return {"badnum": int((st & 1 != 0).sum()), "con_overflow": int((st & 2 != 0).sum()), "efc_overflow": int((st & 4 != 0).sum()),
-                "factor": int((st & 8 != 0).sum()), "worlds": int(self.num_worlds)}
+        from .core import status_counts
+
+        return status_counts(self._ensure()["status_words"], self.num_worlds)
 
     def clear_status(self):
         self._ensure()["status_words"].zero_()
@@ -260,16 +260,13 @@ class BatchedSim:
             t[k].copy_(torch.from_numpy(np.ascontiguousarray(d[k], dtype=np.int32 if k == "status_words" else np.float32)).to(self.device))
 
     def close(self):
-        from . import _native
+        from .core import release_models
 
         if self._t is not None:
             import torch
 
             torch.cuda.synchronize(self.device)
-        for k in ("_h", "_h_big"):
-            if self.__dict__.get(k):
-                _native.release_model(self.__dict__[k])
-                self.__dict__[k] = None
+        release_models(self, ("_h", "_h_big"))
         self.lane = None
 
     def __del__(self):

@@ -415,3 +415,58 @@ def test_split_steps_at_batch_sizes_that_are_no_multiple_of_eight(monkeypatch, e
             e.step(a)
         for name in ("qpos", "qvel", "qacc_ws", "obs", "reward", "status", "packed"):
             assert torch.equal(getattr(envs[0], name), getattr(envs[1], name)), (t, name)
+
+
+@pytest.mark.parametrize("env_id,handles", [("FetchPickAndPlace-v4", ("_h", "_h_big", "_h_fast")), ("HandReach-v3", ("_h", "_h_big"))])
+def test_pickle_takes_over_every_model_handle(monkeypatch, env_id, handles):
+    """An unpickled environment owns one reference to EVERY native model it launches on (GoalVecEnv.MODEL_HANDLES), the hull-less fast Fetch model of GRX_FETCH_HANDOFF=1
+    included: the temporary instance __setstate__ builds must not release any of them when it is collected.  Construction only: no kernel is launched here."""
+    import gc
+
+    import gymnasium_robotics_amd as grx
+    from gymnasium_robotics_amd import _native
+
+    monkeypatch.setenv("GRX_FETCH_HANDOFF", "1")
+    gc.collect()
+    before = len(_native._MODELS)
+    env = grx.make_vec(env_id, num_envs=64, device="cuda:0")      # (64 worlds: the smallest Fetch batch that gets the fast model)
+    assert all(getattr(env, k) for k in handles)
+    refs = lambda: [_native._MODELS[_native._MODEL_KEYS[getattr(env, k).value]][1] for k in handles]
+    start = refs()
+    twin = pickle.loads(pickle.dumps(env))
+    gc.collect()
+    assert refs() == [c + 1 for c in start]
+    assert all(getattr(twin, k).value == getattr(env, k).value for k in handles)
+    twin.close()
+    assert refs() == start
+    env.close()
+    assert len(_native._MODELS) == before
+
+
+@pytest.mark.parametrize("env_id", ["HandReach-v3", "FetchReach-v4"])
+def test_cost_order_of_hand_and_fetch_is_scheduling_only(monkeypatch, env_id):
+    """The sibling of the kitchen / Adroit test above for the two families that allocate through core.cost_order_alloc since the launch scaffold is shared: with `balance` on,
+    the order stays a permutation inside each of the 8 XCD slices, every launch records the worlds' durations, and every returned array and the status words are bit-identical
+    to the launch in index order.  HandReach updates through core.cost_order_update: with GRX_BALANCE_ALPHA=1.0 the moving average IS the newest sample."""
+    import gymnasium_robotics_amd as grx
+
+    n, per = 1024, 128
+    monkeypatch.setenv("GRX_BALANCE_ALPHA", "1.0")
+    a = grx.make_vec(env_id, num_envs=n, device="cuda:0", balance=True)
+    b = grx.make_vec(env_id, num_envs=n, device="cuda:0", balance=False)
+    assert a.balance and a.order is not None and not b.balance and b.order is None
+    _assert_equal(a.reset(seed=3)[0], b.reset(seed=3)[0])
+    rng = np.random.default_rng(3)
+    for t in range(3):
+        act = rng.uniform(-1, 1, (n, a.single_action_space.shape[0])).astype(np.float32)
+        sa, sb = a.step(act), b.step(act)
+        for x, y in zip(sa, sb):
+            _assert_equal(x, y)
+        assert np.array_equal(a.status.cpu().numpy(), b.status.cpu().numpy()), t
+        cost, order = a.cost.cpu().numpy(), a.order.cpu().numpy().reshape(per, 8)
+        assert cost.min() > 0, t
+        for s in range(8):
+            assert sorted(order[:, s].tolist()) == list(range(s * per, (s + 1) * per)), (t, s)
+        if t == 0 and env_id.startswith("Hand"):
+            assert np.array_equal(a.cost_ema.cpu().numpy(), cost.astype(np.float32))
+    a.close(); b.close()
