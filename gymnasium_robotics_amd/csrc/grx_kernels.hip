@@ -5,16 +5,17 @@
 // and write HBM exactly once.  Worlds are independent: no inter-workgroup communication.
 //
 // Build: this ONE source is compiled either as a single translation unit (no GRX_TU_* macro: the profiling variant) or, for the product
-// library, seven times in parallel with -DGRX_TU_FETCH / -DGRX_TU_HAND / -DGRX_TU_POINT / -DGRX_TU_ADROIT / -DGRX_TU_KITCHEN / -DGRX_TU_SIM / -DGRX_TU_API (one family of kernel
+// library, eight times in parallel with -DGRX_TU_FETCH / -DGRX_TU_HAND / -DGRX_TU_POINT / -DGRX_TU_ADROIT / -DGRX_TU_KITCHEN / -DGRX_TU_SIM / -DGRX_TU_SIMDYN / -DGRX_TU_API (one family of kernel
 // instantiations each; __graft_entry__.build links the objects).  Every unit has its own copy of the constant-memory model descriptors
 // (g_grx_models is static): grx_model_create uploads a descriptor to each of them through grx_tu_*_prepare.
-#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_API)
+#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API)
 #define GRX_TU_FETCH 1
 #define GRX_TU_HAND 1
 #define GRX_TU_POINT 1
 #define GRX_TU_ADROIT 1
 #define GRX_TU_KITCHEN 1
 #define GRX_TU_SIM 1
+#define GRX_TU_SIMDYN 1
 #define GRX_TU_API 1
 #endif
 // The guessed support vertices of persistent hull contacts (grx_engine.h, grx_mesh_support) need a per-world HBM row, which only the Fetch buffers carry (hullcache): the
@@ -25,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -51,6 +53,8 @@ static_assert(sizeof(grx_adroit_buffers) == sizeof(GrxAdroitBuffers), "grx_adroi
 static_assert(sizeof(grx_kitchen_task) == sizeof(GrxKitchenTask), "grx_kitchen_task must mirror GrxKitchenTask");
 static_assert(sizeof(grx_kitchen_buffers) == sizeof(GrxKitchenBuffers), "grx_kitchen_buffers must mirror GrxKitchenBuffers");
 static_assert(sizeof(grx_sim_buffers) == sizeof(GrxSimBuffers), "grx_sim_buffers must mirror GrxSimBuffers");
+static_assert(sizeof(grx_sim_dynamics) == sizeof(GrxSimDynamics) && offsetof(grx_sim_dynamics, njac) == offsetof(GrxSimDynamics, njac) && offsetof(grx_sim_dynamics, jac_site) == offsetof(GrxSimDynamics, jac_site) && GRX_SIM_MAXJAC == sizeof(((grx_sim_dynamics*)0)->jac_site) / sizeof(int),
+              "grx_sim_dynamics must mirror GrxSimDynamics");
 
 // ------------------------------------------------------------------------------------------
 // kernels
@@ -790,8 +794,11 @@ grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_
 // The task-free stepper (include/grx_capi.h grx_sim_step, csrc/grx_sim_task.h): mj_step(nstep) or mj_forward of a caller's own model, one wavefront per world, and the MjData
 // fields of the last pass.  Overflow lane in entry mode only: a world that exceeds a table of the fast launch claims a re-run and writes NOTHING; the lane kernel below runs
 // it again from its untouched state rows on the handle with the large tables.  Forward launches claim too: their outputs are the point of the call.
-template <class S>
-__device__ __forceinline__ void grx_sim_step_world(int mslot, const GrxSimBuffers& b, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_) {
+// DYN: the instance that serves the second output block (GrxSimDynamics), in kernels of its own (grx_sim_step_dyn_kernel, grx_sim_lane_dyn_kernel; translation unit GRX_TU_SIMDYN).  A launch that requests
+// none of its outputs runs the kernels without the block (d = nullptr, DYN = false): the stepper as it was before the block existed, argument list included -- the second
+// inlined copy of the forward pass costs the DYN instance 250 B of scratch per lane and took 5 % off a launch that shared a kernel with it (profiles/sim_probe_dynamics.txt).
+template <class S, bool DYN>
+__device__ __forceinline__ void grx_sim_step_world(int mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_) {
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
   const GrxModel& m = g_grx_models[mslot];
@@ -807,12 +814,13 @@ __device__ __forceinline__ void grx_sim_step_world(int mslot, const GrxSimBuffer
   for (int i = lane_; i < 3 * m.nmocap; i += 64) c.mocap_pos[i] = b.mocap_pos[(size_t)w * 3 * m.nmocap + i];
   for (int i = lane_; i < 4 * m.nmocap; i += 64) c.mocap_quat[i] = b.mocap_quat[(size_t)w * 4 * m.nmocap + i];
   __syncthreads();
-  GrxSim<S>::grx_sim_world(&m, &c, nstep, forward_only, lane_);
+  GrxSim<S>::template grx_sim_world<DYN>(&m, &c, nstep, forward_only, d, (size_t)w, lane_);
   __syncthreads();
   if (grx_lane_overflowed(c)) return;   // the re-run on the large tables is booked: state, outputs and status keep their values
   if (forward_only) { for (int i = lane_; i < m.nv; i += 64) b.qacc_ws[(size_t)w * m.nv + i] = c.qacc_ws[i]; }   // mj_forward leaves qpos / qvel as given (the position stage normalises quaternions in its own copy only)
   else grx_state_store(c, b.qpos, (size_t)w * m.nq, b.qvel, (size_t)w * m.nv, b.qacc_ws, (size_t)w * m.nv, m.nq, m.nv, lane_);
   GrxSim<S>::grx_sim_outputs(&m, &c, &b, (size_t)w, lane_);
+  if constexpr (DYN) GrxSim<S>::grx_sim_dynamics_out(&m, &c, d, (size_t)w, lane_);
   if (lane_ == 0) b.status[w] = grx_status_word(b.status[w], c.cnt[2]);
   GRX_PROF_END(c, lane_);
 }
@@ -820,14 +828,26 @@ template <class S>
 __global__ void __launch_bounds__(64, 2)
 grx_sim_step_kernel(int mslot, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
   extern __shared__ float lds[];
-  grx_sim_step_world<S>(mslot, b, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
+  grx_sim_step_world<S, false>(mslot, b, nullptr, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
 }
-// the large-table kernel of the entry list: a small fixed grid, one workgroup per entry (grx_lane_walk; no polling workgroups, no tickets: nothing stands between two launches)
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_dyn_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
+}
+// the large-table kernels of the entry list: a small fixed grid, one workgroup per entry (grx_lane_walk; no polling workgroups, no tickets: nothing stands between two launches)
 template <class S>
 __global__ void __launch_bounds__(64, 2)
 grx_sim_lane_kernel(int mslot, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
   extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S>(mslot, b, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, false>(mslot, b, nullptr, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_dyn_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -856,6 +876,7 @@ int grx_tu_hand_prepare(const GrxModel* g, int bytes, int slot, int* shape);
 int grx_tu_adroit_prepare(const GrxModel* g, int bytes, int slot, int* shape);
 int grx_tu_kitchen_prepare(const GrxModel* g, int bytes, int slot, int* shape);
 int grx_tu_sim_prepare(const GrxModel* g, int bytes, int slot);   // generic kernels only: no shape
+int grx_tu_simdyn_prepare(const GrxModel* g, int bytes, int slot);   // the same stepper with the second output block (GrxSimDynamics): a unit of its own, compiled beside the others
 // kind 0: env.step, 1: forward (nstep), 2: compacted reset
 int grx_tu_fetch_launch(int kind, int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxFetchTask* t, const GrxFetchBuffers* b, const GrxFetchResetArgs* r, int n, int words, int nstep);
 int grx_tu_point_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxPointTask* t, const GrxPointBuffers* b, int n, int words);
@@ -863,6 +884,7 @@ int grx_tu_hand_launch(int shape, unsigned grid, size_t lds_bytes, void* stream,
 int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxAdroitTask* t, const GrxAdroitBuffers* b, int n, int words, int forward_only);
 int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words, int forward_only);
 int grx_tu_sim_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
+int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
 }
 // Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
 // overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
@@ -1044,6 +1066,18 @@ extern "C" int grx_tu_sim_prepare(const GrxModel* g, int bytes, int slot) {
 extern "C" int grx_tu_sim_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only) {
   if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, n, words, nstep, forward_only);
   else hipLaunchKernelGGL(grx_sim_step_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
+#if GRX_TU_SIMDYN
+// ... and the launches that request one of the dynamics outputs, on kernels of their own (see grx_sim_step_world)
+extern "C" int grx_tu_simdyn_prepare(const GrxModel* g, int bytes, int slot) {
+  GRX_LDS(grx_sim_step_dyn_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_dyn_kernel<GrxShapeAny>);
+  return (int)grx_upload_descriptor(g, slot);
+}
+extern "C" int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_dyn_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_dyn_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, n, words, nstep, forward_only);
   return (int)hipGetLastError();
 }
 #endif
@@ -1245,6 +1279,7 @@ static int grx_model_create_impl(const int32_t* H, const int32_t* I, const doubl
   if ((e = grx_tu_adroit_prepare(&g, bytes, m->slot, &m->shape)) != 0) return fail(std::string("grx_model_create (adroit kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_kitchen_prepare(&g, bytes, m->slot, &m->shape)) != 0) return fail(std::string("grx_model_create (kitchen kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_sim_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels): ") + hipGetErrorString((hipError_t)e));
+  if ((e = grx_tu_simdyn_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the dynamics block): ") + hipGetErrorString((hipError_t)e));
   HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), &m->dev, sizeof(GrxModel), sizeof(GrxModel) * (size_t)m->slot, hipMemcpyHostToDevice));
   return 0;
 }
@@ -1396,23 +1431,51 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
 }
 
 // The argument checks that do not need the model come first and read nothing of it (tests/test_cpu_sim.py reaches them without a device).
-extern "C" int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream) {
+// grx_sim_step is this call without the second block; the messages keep its name.
+extern "C" int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream) {
   if (!m) return fail("grx_sim_step: null model");
   if (!buf) return fail("grx_sim_step: null buffers");
   if (!buf->qpos || !buf->qvel || !buf->qacc_ws) return fail("grx_sim_step: null state buffer (qpos, qvel, qacc_ws)");
   if (!buf->status) return fail("grx_sim_step: null status buffer");
   if (n_worlds < 1) return fail("grx_sim_step: n_worlds < 1");
   if (!forward_only && nstep < 1) return fail("grx_sim_step: nstep < 1 (a launch that is not forward_only runs at least one substep)");
+  GrxSimDynamics d; memset(&d, 0, sizeof(d));
+  if (dyn) {
+    memcpy(&d, dyn, sizeof(d));
+    if (d.njac < 0 || d.njac > GRX_SIM_MAXJAC) return fail("grx_sim_step_dyn: njac outside [0, GRX_SIM_MAXJAC]");
+    if (d.njac > 0 && !d.site_jacp && !d.site_jacr) return fail("grx_sim_step_dyn: njac > 0 with site_jacp and site_jacr both null");
+    if (d.njac == 0 && (d.site_jacp || d.site_jacr)) return fail("grx_sim_step_dyn: a Jacobian buffer with njac == 0 (no site selected)");
+  }
   const GrxModel& g = m->dev;
+  for (int k = 0; k < d.njac; k++)
+    if (d.jac_site[k] < 0 || d.jac_site[k] >= g.nsite) return fail("grx_sim_step_dyn: jac_site[" + std::to_string(k) + "] = " + std::to_string(d.jac_site[k]) + " is outside [0, nsite)");
   if (g.nu > 0 && !buf->ctrl) return fail("grx_sim_step: null ctrl buffer (the model has actuators)");
   if (g.nmocap > 0 && (!buf->mocap_pos || !buf->mocap_quat)) return fail("grx_sim_step: null mocap_pos / mocap_quat buffer (the model has mocap bodies)");
   if (g.origin[0] != 0.0 || g.origin[1] != 0.0 || g.origin[2] != 0.0)
     return fail("grx_sim_step: the model was compiled with an origin; the outputs are raw engine coordinates, so compile it in the MJCF's own frame (origin = None)");
   if (g.nshift > 0) return fail("grx_sim_step: the model has a per-world shift group (compile_mjcf(shift_body=...)), which only the Adroit task layer feeds");
   GrxSimBuffers b; memcpy(&b, buf, sizeof(b));
-  const int e = grx_tu_sim_launch(grx_step_grid(b.lane, 0, 0, n_worlds), (size_t)m->words * 4 + m->lds_pad, stream, m->slot, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  // a launch that requests none of the ten runs the kernels without the block
+  const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
+  const unsigned grid = grx_step_grid(b.lane, 0, 0, n_worlds); const size_t lds_bytes = (size_t)m->words * 4 + m->lds_pad;
+  const int e = dynamic ? grx_tu_simdyn_launch(grid, lds_bytes, stream, m->slot, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+                        : grx_tu_sim_launch(grid, lds_bytes, stream, m->slot, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
   if (e) return fail(std::string("grx_sim_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
+}
+extern "C" int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream) {
+  return grx_sim_step_dyn(m, buf, nullptr, n_worlds, nstep, forward_only, stream);
+}
+// sizeof(grx_sim_dynamics) and the byte offset of every member, in declaration order: what _native.SimDynamicsStruct must mirror (host only)
+extern "C" int grx_sim_dynamics_layout(long long* out, int cap) {
+  const grx_sim_dynamics* z = nullptr;
+#define OFF(f) (long long)((const char*)&z->f - (const char*)z)
+  const long long v[] = {(long long)sizeof(grx_sim_dynamics), OFF(qM), OFF(qfrc_smooth), OFF(qacc_smooth), OFF(qfrc_constraint), OFF(qacc), OFF(qfrc_bias), OFF(qfrc_passive), OFF(qfrc_actuator),
+                         OFF(site_jacp), OFF(site_jacr), OFF(njac), OFF(jac_site)};
+#undef OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  if (out) for (int i = 0; i < n && i < cap; i++) out[i] = v[i];
+  return n;
 }
 // sizeof(grx_sim_buffers) and the byte offset of every member, in declaration order (the lane as one member): what _native.SimBuffersStruct must mirror (host only)
 extern "C" int grx_sim_layout(long long* out, int cap) {

@@ -15,10 +15,17 @@ Outputs are what ``MjData`` holds at that moment: after ``step`` the derived fie
 one-substep-stale kinematics the reference's environments read after ``mj_step``), ``qpos`` / ``qvel`` are the integrated state; after ``forward`` they belong to the state as
 given.  ``site_xvelp`` / ``site_xvelr`` are the site Jacobian of that pass times the current ``qvel`` (``get_site_xvelp`` / ``get_site_xvelr``).
 
+The dynamics of the same pass are outputs too: ``qM`` (dense ``mj_fullM``), ``qfrc_bias`` / ``qfrc_passive`` / ``qfrc_actuator`` / ``qfrc_smooth`` / ``qfrc_constraint``,
+``qacc_smooth`` / ``qacc``, and ``site_jacp`` / ``site_jacr``: ``mj_jacSite`` of the sites named in ``jac_sites`` (at most 16; ``sim.jac_row(name)`` is a site's row), shape
+[N, len(jac_sites), 3, nv].  Requesting one of them routes the launch through grx_sim_step_dyn; a simulation that requests none calls grx_sim_step as before.
+
+    sim = grx.BatchedSim("my_robot.xml", 4096, outputs=("qfrc_bias", "site_jacp"), jac_sites=("tip",))
+    J = sim.site_jacp[:, sim.jac_row("tip")]                       # [N, 3, nv]
+
 ``xpos`` / ``xquat`` index the COMPILED model's bodies: the compiler merges static children into their parents, ``sim.model.names["body"]`` maps the surviving names to rows.
 Sites keep their identity whatever body they end up on: they are the stable handle for "where is this point of my robot".
 
-Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, Jacobians, keyframes, per-world model edits.
+Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world model edits.
 """
 import ctypes
 
@@ -27,16 +34,20 @@ import numpy as np
 from .mjcf import CompiledModel, compile_mjcf
 
 STATE = ("qpos", "qvel", "qacc_warmstart", "ctrl", "mocap_pos", "mocap_quat")
-OUTPUTS = ("xpos", "xquat", "site_xpos", "site_xmat", "site_xvelp", "site_xvelr", "sensordata", "ncon", "nefc")
+DYNAMICS = ("qM", "qfrc_smooth", "qacc_smooth", "qfrc_constraint", "qacc", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "site_jacp", "site_jacr")      # grx_sim_dynamics, in its order
+JACOBIANS = ("site_jacp", "site_jacr")
+OUTPUTS = ("xpos", "xquat", "site_xpos", "site_xmat", "site_xvelp", "site_xvelr", "sensordata", "ncon", "nefc") + DYNAMICS
+MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
 
 
 class BatchedSim:
-    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None):
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None):
         """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
         default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
         again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
         CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
-        keep_sites, mutate, ...).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        keep_sites, mutate, ...).  jac_sites: the names of the sites whose Jacobians site_jacp / site_jacr hold, in the order of their rows (None: every site of the model, which must
+        then have at most 16).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
         if int(num_worlds) < 1:
             raise ValueError("num_worlds must be at least 1")
         if overflow not in ("rerun", "flag"):
@@ -65,6 +76,27 @@ class BatchedSim:
         self.nq, self.nv, self.nu, self.nbody, self.nsite, self.nmocap = (m.dim(k) for k in ("nq", "nv", "nu", "nbody", "nsite", "nmocap"))
         self.ntouch = len(np.asarray(m.tables.get("touch_body", [])).reshape(-1))
         self.timestep = m.opt("timestep")
+        self.dynamics = tuple(o for o in self.outputs if o in DYNAMICS)
+        wants_jac = any(o in JACOBIANS for o in self.outputs)
+        if isinstance(jac_sites, str):
+            jac_sites = (jac_sites,)
+        if jac_sites is not None and not wants_jac:
+            raise ValueError("jac_sites selects the rows of site_jacp / site_jacr, and neither is among the outputs")
+        if jac_sites is None:      # every site, row = site id (a site without a name has a row all the same)
+            if wants_jac and self.nsite > MAXJAC:
+                raise ValueError(f"the model has {self.nsite} sites: name at most {MAXJAC} of them in jac_sites")
+            by_id = {i: name for name, i in m.names.get("site", {}).items()}
+            self._jac_ids = tuple(range(self.nsite)) if wants_jac else ()
+            self.jac_sites = tuple(by_id.get(i) for i in self._jac_ids)
+        else:
+            self.jac_sites = tuple(jac_sites)
+            if len(set(self.jac_sites)) != len(self.jac_sites):
+                raise ValueError(f"jac_sites names a site twice: {self.jac_sites}")
+            if len(self.jac_sites) > MAXJAC:
+                raise ValueError(f"jac_sites names {len(self.jac_sites)} sites; a launch carries at most {MAXJAC}")
+            self._jac_ids = tuple(self.site_id(name) for name in self.jac_sites)
+        if wants_jac and not self._jac_ids:
+            raise ValueError("site_jacp / site_jacr need at least one site (the model has none, or jac_sites is empty)")
         self._t = None      # the device tensors, made on first use
         self._h = self._h_big = self.lane = None
 
@@ -81,6 +113,13 @@ class BatchedSim:
 
     def site_id(self, name):
         return self._lookup("site", name)
+
+    def jac_row(self, name):
+        """row of the site `name` in site_jacp / site_jacr (its position in jac_sites)"""
+        self.site_id(name)
+        if name not in self.jac_sites:
+            raise KeyError(f"site {name!r} is not among jac_sites {self.jac_sites}")
+        return self.jac_sites.index(name)
 
     def actuator_id(self, name):
         return self._lookup("actuator", name)
@@ -100,7 +139,8 @@ class BatchedSim:
         n = self.num_worlds
         return dict(qpos=(n, self.nq), qvel=(n, self.nv), qacc_warmstart=(n, self.nv), ctrl=(n, self.nu), mocap_pos=(n, self.nmocap, 3), mocap_quat=(n, self.nmocap, 4),
                     xpos=(n, self.nbody, 3), xquat=(n, self.nbody, 4), site_xpos=(n, self.nsite, 3), site_xmat=(n, self.nsite, 9), site_xvelp=(n, self.nsite, 3),
-                    site_xvelr=(n, self.nsite, 3), sensordata=(n, self.ntouch), ncon=(n,), nefc=(n,))
+                    site_xvelr=(n, self.nsite, 3), sensordata=(n, self.ntouch), ncon=(n,), nefc=(n,), qM=(n, self.nv, self.nv), site_jacp=(n, len(self._jac_ids), 3, self.nv),
+                    site_jacr=(n, len(self._jac_ids), 3, self.nv), **{k: (n, self.nv) for k in DYNAMICS if k not in ("qM",) + JACOBIANS})
 
     def _ensure(self):
         if self._t is not None:
@@ -129,6 +169,12 @@ class BatchedSim:
         self._mocap_quat0 = torch.from_numpy(np.asarray(tb.get("mocap_quat0", np.zeros(0)), dtype=np.float32).reshape(self.nmocap, 4)).to(self.device)
         self._t = t
         self._bufs = self._make_bufs(None)
+        self._dyn = None
+        if self.dynamics:      # one block for the step launch and for the re-run behind it
+            self._dyn = _native.SimDynamicsStruct(**{k: t[k].data_ptr() for k in self.dynamics})
+            if any(k in JACOBIANS for k in self.dynamics):
+                self._dyn.njac = len(self._jac_ids)
+                self._dyn.jac_site[:len(self._jac_ids)] = self._jac_ids
         if self.overflow == "rerun":
             self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
             if self._h_big is not None:
@@ -158,7 +204,8 @@ class BatchedSim:
         b.qpos, b.qvel, b.qacc_ws = t["qpos"].data_ptr(), t["qvel"].data_ptr(), t["qacc_warmstart"].data_ptr()
         b.ctrl, b.mocap_pos, b.mocap_quat = ptr(t["ctrl"]), ptr(t["mocap_pos"]), ptr(t["mocap_quat"])
         for k in self.outputs:
-            setattr(b, k, ptr(t[k]))
+            if k not in DYNAMICS:
+                setattr(b, k, ptr(t[k]))
         b.status = t["status_words"].data_ptr()
         b.mask = None if mask is None else mask.data_ptr()
         return b
@@ -183,7 +230,11 @@ class BatchedSim:
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream_ptr(self.device))))
+            if self._dyn is None:
+                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream_ptr(self.device))))
+            else:
+                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_dyn(h, ctypes.byref(b), ctypes.byref(self._dyn), self.num_worlds, int(nstep), int(forward_only),
+                                                                                  stream_ptr(self.device))))
             self._bufs.mask = None if m is None else m.data_ptr()
             if self.lane is None:
                 go(self._h)(self._bufs)

@@ -391,6 +391,29 @@ typedef struct grx_sim_buffers {
 int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_buffers), out[1 ...] = the byte offset of each member in declaration order (the lane as one member); returns the number of values (19) */
 int grx_sim_layout(long long* out, int cap);
+/* The DYNAMICS of the same pass, a second and optional output block of the task-free stepper: what a controller reads from MjData next to the fields above -- gravity
+ * compensation (qfrc_bias), operational-space control and differential IK (site_jacp / site_jacr, qM), inverse-dynamics feed-forward, contact-force observations
+ * (qfrc_constraint).  Every pointer may be NULL (not written); mirrors struct GrxSimDynamics (csrc/grx_sim_task.h).  Same moment as the other outputs: after nstep >= 1 the
+ * fields of the LAST forward pass, before its integration (RK4 models: the fourth stage's pass); after forward_only those of the state as given.
+ *   qM                                  mj_fullM(data.qM): dense, row-major, both triangles              [N,nv,nv]
+ *   qfrc_smooth, qacc_smooth, qfrc_constraint, qacc, qfrc_bias, qfrc_passive, qfrc_actuator   data.*     [N,nv]
+ *   site_jacp, site_jacr                mj_jacSite(model, data, jacp, jacr, jac_site[k]), k < njac        [N,njac,3,nv]
+ * Every element of a requested buffer is written, a Jacobian column of a dof that does not move the site as 0.0f: the buffers need no initialisation.  njac and jac_site
+ * select the sites of BOTH Jacobian buffers.  grx_sim_step_dyn with dyn == NULL is grx_sim_step; the re-run call of the overflow lane takes the same block as the first call.
+ * Returns -1 (grx_last_error) for everything grx_sim_step refuses and for njac outside [0, GRX_SIM_MAXJAC], njac > 0 with both Jacobian pointers NULL, a Jacobian pointer
+ * with njac == 0, a site id outside [0, nsite). */
+#define GRX_SIM_MAXJAC 16
+typedef struct grx_sim_dynamics {
+  float* qM;
+  float *qfrc_smooth, *qacc_smooth, *qfrc_constraint, *qacc;
+  float *qfrc_bias, *qfrc_passive, *qfrc_actuator;
+  float *site_jacp, *site_jacr;
+  int njac;                                /* number of selected sites, 0 .. GRX_SIM_MAXJAC */
+  int jac_site[GRX_SIM_MAXJAC];            /* their site ids, in the order of the rows */
+} grx_sim_dynamics;
+int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream);
+/* host only: out[0] = sizeof(grx_sim_dynamics), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (13) */
+int grx_sim_dynamics_layout(long long* out, int cap);
 /* `count` consecutive np_random.uniform(-1, 1) draws per listed world, float32 rows (states / idx as in grx_fetch_sample_resets; idx NULL = worlds 0..n-1).  HOST pointers. */
 int grx_sample_uniform_rows(uint64_t* states, const int64_t* idx, int n, int count, float* out);
 /* The same draws ON THE DEVICE: states [N,4] uint64 and out [N,count] float32 are DEVICE pointers, mask [N] uint8 or NULL selects the worlds whose streams advance

@@ -2,7 +2,10 @@
 `--nstep` substeps, beside the AntMaze model stepped through the same door (same kernel, AntMaze's own table capacities and frame_skip).  One run, no repetition: a figure to
 size expectations by, not a benchmark (bench.py measures the flagship workload).
 
-    python tools/sim_probe.py --worlds 4096 --steps 200 --warmup 20 > profiles/sim_probe.txt"""
+    python tools/sim_probe.py --worlds 4096 --steps 200 --warmup 20 > profiles/sim_probe.txt
+
+--outputs (comma-separated names of sim.OUTPUTS, or `all`) replaces the arm scene's default pair, --jac-sites names the sites of its Jacobian outputs:
+profiles/sim_probe_dynamics.txt."""
 import argparse
 import os
 import sys
@@ -39,12 +42,18 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--nstep", type=int, default=5)
+    ap.add_argument("--outputs", default="site_xpos,site_xvelp")
+    ap.add_argument("--jac-sites", default="")
     a = ap.parse_args()
-    print(f"command: python tools/sim_probe.py --worlds {a.worlds} --steps {a.steps} --warmup {a.warmup} --nstep {a.nstep}")
+    from gymnasium_robotics_amd.sim import OUTPUTS
+
+    outputs = OUTPUTS if a.outputs == "all" else tuple(o for o in a.outputs.split(",") if o)
+    jac = tuple(s for s in a.jac_sites.split(",") if s) or None
+    print(f"command: python tools/sim_probe.py --worlds {a.worlds} --steps {a.steps} --warmup {a.warmup} --nstep {a.nstep} --outputs {a.outputs}" + (f" --jac-sites {a.jac_sites}" if jac else ""))
     print(f"build id: {_native.build_id()}   device: {torch.cuda.get_device_name(0)}   SINGLE RUN")
     sc = S.SCENES["arm"]
     st = sc.states(a.worlds)
-    arm = grx.BatchedSim(sc.model, num_worlds=a.worlds, outputs=("site_xpos", "site_xvelp"))
+    arm = grx.BatchedSim(sc.model, num_worlds=a.worlds, outputs=outputs, **(dict(jac_sites=jac) if jac else {}))
     for k in ("qpos", "qvel", "ctrl"):
         getattr(arm, k).copy_(torch.from_numpy(np.ascontiguousarray(st[k], dtype=np.float32)))
     rate = timed(arm, a.nstep, a.steps, a.warmup)
