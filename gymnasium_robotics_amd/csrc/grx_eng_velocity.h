@@ -4,6 +4,25 @@
 // ------------------------------------------------------------------------------------------
 // velocity stage: cvel, cdof_dot, RNE bias (K2/K5), passive (K6), actuation (K7)
 // ------------------------------------------------------------------------------------------
+// generalised force of actuator i on the dof of its joint: gear * clamp(gain * clamp(ctrl) + bias), the arithmetic of grx_velocity's actuator loop; *next = the next actuator
+// on the same dof, or -1.  Only the pass over shared dofs calls it.
+GRX_MEM float grx_actuator_force(const GrxModel* m, const GrxCtx* c, int i, int* next) {
+  const int* AI = m->reci_act + GRX_RAI * i; const float* AF = m->recf_act + GRX_RAF * i;
+  const int qadr = AI[0], dadr = AI[1], ctrllimited = AI[2], gaintype = AI[3], biastype = AI[4], forcelimited = AI[5];
+  const float gear = AF[0], cr0 = AF[1], cr1 = AF[2], g0 = AF[3], g1 = AF[4], g2 = AF[5], b0 = AF[6], b1 = AF[7], b2 = AF[8], fr0 = AF[9], fr1 = AF[10];
+  float len = gear * c->qpos[qadr], vel = gear * c->qvel[dadr];
+  float u = c->ctrl[i];
+  if (ctrllimited) u = fminf(cr1, fmaxf(cr0, u));
+  float gain = g0;
+  if (gaintype == 1) gain += g1 * len + g2 * vel;
+  float bias = 0;
+  if (biastype == 1) bias = b0 + b1 * len + b2 * vel;
+  float f = gain * u + bias;
+  if (forcelimited) f = fminf(fr1, fmaxf(fr0, f));
+  *next = AI[7];
+  return gear * f;
+}
+
 GRX_MEM void grx_velocity(const GrxModel* m, GrxCtx* c, int lane_) {
   GRX_OPAQUE_STAGE(lane_);   // record addresses and lane masks of this stage are recomputed here, not carried (spilled) across the substep loop
   GRX_FRESH_MODEL(m, c);
@@ -89,11 +108,28 @@ GRX_MEM void grx_velocity(const GrxModel* m, GrxCtx* c, int lane_) {
       if (biastype == 1) bias = b0 + b1 * len + b2 * vel;
       float f = gain * u + bias;
       if (forcelimited) f = fminf(fr1, fmaxf(fr0, f));
-      c->qfrc_actuator[dadr] = gear * f;  // models in scope have at most one actuator per dof
+      c->qfrc_actuator[dadr] = gear * f;  // the whole force of a dof with one actuator; a dof with several is written again below
     }
   }
   WAVE_SYNC();
   GRX_SUBTICK(c, 7);
+  // Dofs with more than one actuator (a <position> plus a <velocity> on one joint is the usual PD pair): qfrc_actuator[d] is the SUM over the dof's actuators in actuator
+  // order, the oracle's order.  The store above leaves one of the summands there, which one is not specified; here the lane of the dof's FIRST actuator walks the chain of
+  // its actuators (record slots 6 and 7, grx_host_model.h), sums and writes once -- one writer per dof, no atomics.  The branch is wave-uniform, and the fixed shapes do not
+  // carry it at all (GrxShape::kActShare): in their kernels the test costs a scalar load and a wait per substep, 0.4 % of a Fetch step when it was measured.
+  if (S::kActShare && m->nactshare) {
+    FOR_LANES {
+      for (int i = lane; i < GRX_NUC; i += 64) {
+        const int* AI = m->reci_act + GRX_RAI * i;
+        if (AI[6]) {
+          int next;
+          float f = grx_actuator_force(m, c, i, &next);
+          while (next >= 0) f += grx_actuator_force(m, c, next, &next);
+          c->qfrc_actuator[AI[1]] = f;
+        }
+      }
+    }
+  }
   FOR_LANES {
     // subtree force sums
     for (int it = lane; it < 6 * GRX_NBC; it += 64) {

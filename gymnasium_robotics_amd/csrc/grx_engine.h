@@ -147,6 +147,7 @@ struct GrxModel {
   int nq, nv, nu, nbody, njnt, ngeom, nsite, nmocap, neq, npair, ndevpair, nmpair, maxdepth, eulerdamp, anydamp, nfric, nweld, integrator, njump, wpool, ntendon, maxefc, jpool, ntouch, maxcon, twospan, nconvex, nfreeobj, ngridgeom, ngridwall, gridnx, gridny, handtree, nmeshpair, nshift, noslip_iterations, iterations, njeq, ngate;
   float timestep, gravity[3], meaninertia, impratio, mpr_tolerance, gridx0, gridy0, gridinv, noslip_tolerance;
   int mpr_iterations;
+  int nactshare;   // dofs with more than one actuator (derived at model creation): their forces are summed in a pass of their own (grx_velocity)
   // MJCF coordinates of this model's world origin (include/grx_model.h GRX_ORIGIN_*; zeros for a model compiled in the MJCF's own frame).  The engine never reads it: it works in
   // the model's frame.  The task code adds it back, in fp64, to every world position it writes out (grx_world_out below).
   double origin[3];
@@ -183,7 +184,7 @@ enum { GRX_RBI = 16, GRX_RBF = 16,    // body (kinematics): I mocapid, jntadr, j
        GRX_RCI = 4,                   // body (Jacobian columns): I dof_chainmask lo, hi, rootid, -
        GRX_RWI = 12, GRX_RWF = 28,    // active weld: I eq, body1, body2, weld_row, chainmask lo / hi / root of body1, of body2, -, -;  F eq_data[11], -, eq_relpose[14], -, -
        GRX_REF = 12,                  // equality (row parameters): F row-parameter block with invweight[0] at GRX_PRM_DA and invweight[1] at GRX_PRM_DA2, -
-       GRX_RAI = 8, GRX_RAF = 12,     // actuator: I qposadr / dofadr of its joint, ctrllimited, gaintype, biastype, forcelimited, -, -;  F gear, ctrlrange[2], gainprm[3], biasprm[3], forcerange[2], -
+       GRX_RAI = 8, GRX_RAF = 12,     // actuator: I qposadr / dofadr of its joint, ctrllimited, gaintype, biastype, forcelimited, first actuator of a dof that has several, next actuator of the same dof or -1;  F gear, ctrlrange[2], gainprm[3], biasprm[3], forcerange[2], -
        GRX_RDI = 8, GRX_RDF = 16,     // dof: I qposadr / type / dofadr of its joint, cvelstart, body of that dof, last dof of that body, bodyid, -;  F damping, stiffness, springref, armature, row-parameter block [4, 14) of its friction-loss row, -, -
        GRX_RMI = 4,                   // mass-matrix entry: I i, j, body of dof i, -;  F (one word) armature of dof i
        GRX_RHI = 12, GRX_RHF = 8,     // hull pair (every candidate pair has one; a geom that is no hull has address, count 0 and cell base -1): I geom1, geom2, type1, type2, first hull vertex / vertex count of geom1, of geom2,
@@ -667,6 +668,9 @@ struct GrxShape {
   // rows may carry a second dof span (models compiled with split pair spans); fixed shapes without it skip that bookkeeping
   static constexpr bool kTwoSpan = (NV_ == 0) || (TWOSPAN_ != 0);
   static constexpr bool kFixed = NV_ > 0;   // nu / nmocap may legitimately be 0 in a fixed shape
+  // carries the pass that sums the forces of several actuators on one dof (grx_velocity): the generic kernels only.  No model a fixed shape was written for has such a
+  // dof, and grx_shape_matches hands a model that has one (GrxModel::nactshare) to the generic kernel.
+  static constexpr bool kActShare = (NV_ == 0);
   // incremental Hessian corrections between Newton iterations (grx_hessian_update): compiled into the kernels of models with a free
   // object in contact (several iterations per substep are common there); articulated-only models and the RK4 ant converge in one
   static constexpr bool kIncrHess = (NV_ == 0) || (NQ_ != NV_ && INTEG_ == 0) || NV_ > 33;   // ... and AdroitHandRelocate (nv 36: a full assembly = the 32 x 32 tile + four more rows / columns; A/B 17.4 -> 15.9 ms per step; door / pen / hammer measured slower or equal with it)

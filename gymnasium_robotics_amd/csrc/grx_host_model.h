@@ -178,6 +178,12 @@ inline void grx_pack_model(const int32_t* H, const int32_t* I, const double* F, 
   m.nfric = 0; m.nweld = 0; m.wpool = 0;
   for (int k = 0; k < v.n_weld_row; k++) m.wpool += 6 * ((v.weld_row[k] >> 20) & 0xFF);
   m.njeq = v.n_jeq_eq;
+  m.nactshare = 0;   // dofs with more than one actuator: counted at the first actuator of each
+  for (int a = 0; a < m.nu; a++) {
+    const int da = v.jnt_dofadr[v.act_trnid[a]]; int before = 0, after = 0;
+    for (int b = 0; b < m.nu; b++) if (b != a && v.jnt_dofadr[v.act_trnid[b]] == da) { if (b < a) before++; else after++; }
+    if (!before && after) m.nactshare++;
+  }
   for (int k = 0; k < v.n_jeq_row; k++) m.wpool += (v.jeq_row[k] >> 20) & 0xFF;
   for (int k = 0; k < v.n_dof_frictionloss; k++) if (v.dof_frictionloss[k] > 0) m.nfric++;
   for (int k = 0; k < v.n_eq_type; k++) if (v.eq_active[k] && v.eq_type[k] == GRX_EQ_WELD) m.nweld++;
@@ -325,7 +331,13 @@ inline void grx_build_records(GrxPackedModel* out, bool allocate) {
   for (int a = 0; a < nu; a++) {
     int32_t* I = ri + out->rec.i_act + GRX_RAI * a; float* F = rf + out->rec.f_act + GRX_RAF * a;
     const int j = h.act_trnid[a];
-    I[0] = h.jnt_qposadr[j]; I[1] = h.jnt_dofadr[j]; I[2] = h.act_ctrllimited[a]; I[3] = h.act_gaintype[a]; I[4] = h.act_biastype[a]; I[5] = h.act_forcelimited[a]; I[6] = I[7] = 0;
+    I[0] = h.jnt_qposadr[j]; I[1] = h.jnt_dofadr[j]; I[2] = h.act_ctrllimited[a]; I[3] = h.act_gaintype[a]; I[4] = h.act_biastype[a]; I[5] = h.act_forcelimited[a];
+    // the actuators of one dof form a chain in actuator order: I[7] = the next actuator on the same dof or -1, I[6] = 1 on the first actuator of a dof that has more than
+    // one (grx_velocity sums along the chain; GrxModel::nactshare counts these dofs)
+    I[6] = 1; I[7] = -1;
+    for (int b = 0; b < a; b++) if (h.jnt_dofadr[h.act_trnid[b]] == I[1]) I[6] = 0;
+    for (int b = nu - 1; b > a; b--) if (h.jnt_dofadr[h.act_trnid[b]] == I[1]) I[7] = b;
+    if (I[7] < 0) I[6] = 0;
     F[0] = h.act_gear[a]; F[1] = h.act_ctrlrange[2 * a]; F[2] = h.act_ctrlrange[2 * a + 1];
     for (int k = 0; k < 3; k++) { F[3 + k] = h.act_gainprm[3 * a + k]; F[6 + k] = h.act_biasprm[3 * a + k]; }
     F[9] = h.act_forcerange[2 * a]; F[10] = h.act_forcerange[2 * a + 1];

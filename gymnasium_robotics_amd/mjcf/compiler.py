@@ -515,9 +515,15 @@ class MjcfCompiler:
             if "mpr_iterations" in a:
                 self.opt["mpr_iterations"] = int(a["mpr_iterations"])
             if "integrator" in a:
-                self.opt["integrator"] = {"euler": 0, "rk4": 1, "implicit": 2, "implicitfast": 3}[a["integrator"].lower()]
+                # the engine and the oracle integrate with semi-implicit Euler and RK4; the implicit integrators used to be parsed and then stepped as Euler
+                if a["integrator"].lower() in ("implicit", "implicitfast"):
+                    raise NotImplementedError(f'integrator="{a["integrator"]}": the engine and the oracle have Euler and RK4 only')
+                self.opt["integrator"] = {"euler": 0, "rk4": 1}[a["integrator"].lower()]
             if "cone" in a:
-                self.opt["cone"] = {"pyramidal": 0, "elliptic": 1}[a["cone"].lower()]
+                # contact rows are pyramidal on both sides; an elliptic model used to run with a pyramidal cone
+                if a["cone"].lower() == "elliptic":
+                    raise NotImplementedError('cone="elliptic": the engine and the oracle have the pyramidal friction cone only')
+                self.opt["cone"] = {"pyramidal": 0}[a["cone"].lower()]
             for fl in o.findall("flag"):
                 if fl.attrib.get("eulerdamp", "enable") == "disable":
                     self.opt["eulerdamp"] = 0
@@ -1462,6 +1468,8 @@ class _Lowering:
                     a["gaintype"] = "fixed"
                 if "joint" not in a:
                     raise NotImplementedError("only joint transmissions are supported")
+                if a.get("dyntype", "none").lower() != "none":
+                    raise NotImplementedError(f'actuator dyntype="{a["dyntype"]}": actuators are stateless here (there is no act vector)')
                 jid = names["joint"][a["joint"]]
                 ctrlrange = _floats(a.get("ctrlrange"), 2, [0, 0])
                 forcerange = _floats(a.get("forcerange"), 2, [0, 0])

@@ -6,6 +6,8 @@ A. pair groups ... geom A on a free joint against geom B (a plane, a static geom
 B. tree groups ... contact-free random trees of hinge / slide joints, half of them on a free root, with limits, friction loss, springs, actuators; Euler and RK4
                    (no ball joints: neither the engine nor the oracle has one, and the compiler refuses them)
 C. solve groups .. hinge / slide trees of an exact nv (every route of grx_sym_solve_full), and robots followed by a free body (the block-diagonal routes)
+D. row groups .... welds, joint equalities, fixed-tendon limits, affine and clamped actuators, two actuators on one joint, impratio and noslip: one model each, and
+                   two of nv = 20 that hold all five row kinds in one world (Euler and RK4)
 
 condim and margin / gap are properties of the MODEL in MJCF, so a pair group is compiled in up to eight VARIANTS (condim 1 / 3 / 4 / 6, with and without
 margin="0.004" gap="0.001"); each variant carries the group's cases that use it and is one launch of one world per case.
@@ -368,9 +370,10 @@ def build_pair_group(spec, gidx):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # B. tree groups and C. solve-size groups
-def _tree_xml(rng, joints, parents, integrator, free_first=False, fric=0.3, lim=0.4, actuators=True, extra_world="", extra_body=None, tail=""):
+def _tree_xml(rng, joints, parents, integrator, free_first=False, fric=0.3, lim=0.4, actuators=True, extra_world="", extra_body=None, tail="", names=False):
     """joints: the joint type of each body; parents: index of the parent body (-1: the world).  Every joint gets a random axis and offset, armature, damping, sometimes a
-    spring, friction loss on a share `fric` of the joints and limits on a share `lim`; every body a rotated box of random size (contype = conaffinity = 0)."""
+    spring, friction loss on a share `fric` of the joints and limits on a share `lim`; every body a rotated box of random size (contype = conaffinity = 0).  names: body k is
+    called b{k} (a weld refers to its bodies by name)."""
     kids = {k: [] for k in range(-1, len(joints))}
     for k, p in enumerate(parents):
         kids[p].append(k)
@@ -397,7 +400,7 @@ def _tree_xml(rng, joints, parents, integrator, free_first=False, fric=0.3, lim=
         g = '<geom type="box" size="{:.4f} {:.4f} {:.4f}" pos="{:.4f} {:.4f} {:.4f}" quat="{:.5f} {:.5f} {:.5f} {:.5f}" mass="{:.4f}" contype="0" conaffinity="0"/>'.format(
             *rng.uniform(0.02, 0.08, 3), *rng.uniform(-0.05, 0.05, 3), *_unit(rng, 4), rng.uniform(0.1, 0.8))
         more = extra_body(k) if extra_body else ""
-        return '<body pos="{:.4f} {:.4f} {:.4f}">'.format(*pos) + j + g + more + "".join(body(c) for c in kids[k]) + "</body>"
+        return '<body{} pos="{:.4f} {:.4f} {:.4f}">'.format(f' name="b{k}"' if names else "", *pos) + j + g + more + "".join(body(c) for c in kids[k]) + "</body>"
 
     bodies = "".join(body(k) for k in kids[-1])
     return (f'<mujoco><compiler angle="radian"/><option timestep="{0.004 if integrator == "RK4" else 0.002}" integrator="{integrator}" gravity="1.5 -2 -9"/>'
@@ -515,7 +518,295 @@ def _link_geom(model):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
-ALL = [("pair", s) for s in pair_groups()] + [("tree", s) for s in tree_groups()] + [("solve", s) for s in solve_groups()]
+# D. row groups: the rows and actuator forms the trees above never carry -- welds, joint equalities, fixed-tendon limits, affine actuators and their clamps, two
+# actuators on one joint, impratio and noslip.  One compiled model per group (two for rows-options), ROWS_N cases each, no colliding geom unless the group says so.
+ROWS_N = 7      # 6 .. 8 cases, never a multiple of 8 worlds
+ROWS_GROUPS = ("rows-weld", "rows-jeq", "rows-tendon", "rows-actuator", "rows-mixed-euler", "rows-mixed-rk4", "rows-options")
+_JEQ_POLY = (0.01, 0.8, -0.3, 0.2, -0.1)      # all five coefficients non-zero
+_JEQ = ('<joint joint1="j{a}" joint2="j{b}" polycoef="' + " ".join(map(str, _JEQ_POLY)) + '" solimp="0.85 0.97 0.002 0.4 3"/>'       # five-value solimp, power 3
+        '<joint joint1="j{c}" joint2="j{d}" polycoef="0 -1.2 0 0 0" solref="0.001 1"/>'      # solref[0] below two timesteps: the clamp
+        '<joint joint1="j{e}" joint2="j{d}" active="false"/>')
+# three fixed tendons with ranges of a few centimetres: one over two branches, one with margin and a negative solreflimit, one that lists a joint twice.  The joint
+# named first is the one the states solve the tendon's length with (it belongs to no other tendon)
+_TENDONS = ('<fixed limited="true" range="-0.03 0.04"><joint joint="j{a}" coef="1"/><joint joint="j{b}" coef="-0.7"/></fixed>'
+            '<fixed limited="true" range="-0.025 0.035" margin="0.004" solreflimit="-1500 -50"><joint joint="j{c}" coef="1.2"/><joint joint="j{d}" coef="0.5"/></fixed>'
+            '<fixed limited="true" range="-0.04 0.03"><joint joint="j{e}" coef="1"/><joint joint="j{f}" coef="0.6"/><joint joint="j{f}" coef="0.4"/></fixed>')
+_TENDON_RANGE = ((-0.03, 0.04, 0.0), (-0.025, 0.035, 0.004), (-0.04, 0.03, 0.0))      # lower end, upper end, margin
+# <general> with affine gain and bias, both clamps and a gear; <velocity>; <motor> with a ctrlrange; <position> plus <velocity> on ONE joint (the PD pair)
+_ACTUATORS = ('<general joint="j{a}" gaintype="affine" gainprm="8 -3 0.5" biastype="affine" biasprm="0.4 -6 -0.8" ctrllimited="true" ctrlrange="-0.6 0.8" forcelimited="true" '
+              'forcerange="-3 2.5" gear="2"/><velocity joint="j{b}" kv="1.5"/><motor joint="j{c}" ctrllimited="true" ctrlrange="-0.4 0.5" gear="3"/>'
+              '<position joint="j{d}" kp="25"/><velocity joint="j{d}" kv="2"/>')
+_CTRL_MODE = ((0, 1, 2, 0, 1, 2, 2), (2, 0, 1, 1, 0, 2, 2))      # per case: ctrl of the <general> / of the <motor> below (0), above (1) or inside (2) its ctrlrange
+_WELD_QSTAR = np.array([0.4, 0.03, -0.5])      # the chain configuration whose tip pose the world weld holds
+
+
+def rows_groups():
+    return [(n,) for n in ROWS_GROUPS]
+
+
+def _fmt(v):
+    return " ".join(repr(float(x)) for x in v)
+
+
+def _with(xml, k, attrs):
+    """the text of _tree_xml with more attributes on joint j{k}"""
+    key = f'name="j{k}" '
+    assert xml.count(key) == 1
+    return xml.replace(key, key + attrs + " ")
+
+
+def _sections(xml, equality="", tendon="", actuator=""):
+    assert xml.count("<actuator></actuator>") == 1
+    return xml.replace("<actuator></actuator>", f"<equality>{equality}</equality><tendon>{tendon}</tendon><actuator>{actuator}</actuator>")
+
+
+def _qadr(model, k):
+    return int(np.asarray(model.tables["jnt_qposadr"]).reshape(-1)[model.names["joint"][f"j{k}"]])
+
+
+def _dadr(model, k):
+    return int(np.asarray(model.tables["jnt_dofadr"]).reshape(-1)[model.names["joint"][f"j{k}"]])
+
+
+def _world_weld(xml, q, body):
+    """a weld of a named body to the world, negative solref, with the explicit relpose that holds the body where it is at qpos = q (on the oracle): the world's pose in
+    the body's frame"""
+    model = compile_xml(xml)
+    sim = _oracle(model)
+    sim.qpos[:], sim.qvel[:] = f32(q), 0.0
+    sim.forward()
+    b = int(model.names["body"][body])
+    x, r = sim.xpos[3 * b:3 * b + 3].copy(), sim.xquat[4 * b:4 * b + 4] * np.array([1.0, -1, -1, -1])
+    return f'<weld body1="{body}" solref="-2000 -60" relpose="{_fmt(np.r_[quat_rot(r, -x), r])}"/>'
+
+
+def _off(rng, n=None):
+    """a few millimetres (milliradians) off, either way: a start 0.3 N(0, 1) away from a welded pose asks of the rows what build_solve_group's docstring says of limits"""
+    return rng.uniform(3e-4, 3e-3, n) * np.where(rng.random(n) < 0.5, -1.0, 1.0)
+
+
+def _poly(c, x):
+    return c[0] + x * (c[1] + x * (c[2] + x * (c[3] + x * c[4])))
+
+
+def _band(rng, lo, hi, margin, mode):
+    """a coordinate inside [lo, hi] and clear of the margin (mode 0), or 0.3 .. 3 mm (mrad) beyond the lower (1) or the upper end (2): _states' near_limits, by turns"""
+    over = rng.uniform(3e-4, 3e-3)
+    return rng.uniform(lo + margin + 2e-3, hi - margin - 2e-3) if mode == 0 else lo - over if mode == 1 else hi + over
+
+
+def _solve_tendons(rng, model, q, i, joints):
+    """moves the first joint of each tendon of _TENDONS so that tendon t of case i is inside, below or above its range by turns: mode (i + t) % 3"""
+    t_ = model.tables
+    adr, num, qa, coef = (np.asarray(t_[k]).reshape(-1) for k in ("tendon_adr", "tendon_num", "wrap_qadr", "wrap_coef"))
+    for t, (lo, hi, mg) in enumerate(_TENDON_RANGE):
+        w = slice(adr[t], adr[t] + num[t])
+        own = _qadr(model, joints[t])
+        assert qa[w][0] == own and (qa[w] == own).sum() == 1
+        rest = sum(c * q[a] for c, a in zip(coef[w][1:], qa[w][1:]))
+        q[own] = (_band(rng, lo, hi, mg, (i + t) % 3) - rest) / coef[w][0]
+
+
+def tendon_sides(var, i):
+    """(lower active, upper active) of every tendon of the variant's model at case i, from the tables and the fp32 start alone, and the residuals of the active sides in
+    the oracle's row order"""
+    t_ = var.model.tables
+    adr, num, qa = (np.asarray(t_[k]).reshape(-1) for k in ("tendon_adr", "tendon_num", "wrap_qadr"))
+    coef, rg, mg = np.asarray(t_["wrap_coef"], dtype=np.float64).reshape(-1), np.asarray(t_["tendon_range"], dtype=np.float64).reshape(-1, 2), np.asarray(t_["tendon_margin"], dtype=np.float64).reshape(-1)
+    sides, pos = [], []
+    for t in range(len(adr)):
+        ln = sum(coef[w] * var.q0[i, qa[w]] for w in range(adr[t], adr[t] + num[t]))
+        d = (ln - rg[t, 0], rg[t, 1] - ln)
+        sides.append((d[0] < mg[t], d[1] < mg[t]))
+        pos += [x for x in d if x < mg[t]]
+    return sides, np.array(pos)
+
+
+def actuator_forces(var, i):
+    """per actuator of case i, in numpy from the model tables: (ctrl, ctrlrange or None, unclamped force, forcerange or None, dof, generalised force gear * clamped force)"""
+    t_ = var.model.tables
+    g = lambda k, w=1: np.asarray(t_[k], dtype=np.float64).reshape(-1, w) if w > 1 else np.asarray(t_[k]).reshape(-1)
+    trn, cl, fl, gt, bt, gear = g("act_trnid"), g("act_ctrllimited"), g("act_forcelimited"), g("act_gaintype"), g("act_biastype"), g("act_gear")
+    cr, fr, gp, bp = g("act_ctrlrange", 2), g("act_forcerange", 2), g("act_gainprm", 3), g("act_biasprm", 3)
+    ja, jd = g("jnt_qposadr"), g("jnt_dofadr")
+    out = []
+    for a in range(var.nu):
+        ln, vel, u = gear[a] * var.q0[i, ja[trn[a]]], gear[a] * var.v0[i, jd[trn[a]]], var.ctrl[i, a]
+        uc = min(cr[a, 1], max(cr[a, 0], u)) if cl[a] else u
+        f = (gp[a, 0] + (gp[a, 1] * ln + gp[a, 2] * vel if gt[a] == 1 else 0.0)) * uc + (bp[a, 0] + bp[a, 1] * ln + bp[a, 2] * vel if bt[a] == 1 else 0.0)
+        fc = min(fr[a, 1], max(fr[a, 0], f)) if fl[a] else f
+        out.append((u, tuple(cr[a]) if cl[a] else None, f, tuple(fr[a]) if fl[a] else None, int(jd[trn[a]]), gear[a] * fc))
+    return out
+
+
+def _actuator_ctrl(rng, q, v, i, pd_q, pd_d):
+    """ctrl of _ACTUATORS for case i: beyond either end of both ctrlranges by turns (_CTRL_MODE); on the shared joint a position error of 0.05 .. 0.5 and a velocity error
+    of 0.1 .. 1, so that both of its actuators push with more than 0.05 (kp 25, kv 2)"""
+    side = lambda lo, hi, mode: lo - rng.uniform(0.05, 0.4) if mode == 0 else hi + rng.uniform(0.05, 0.4) if mode == 1 else rng.uniform(lo, hi)
+    sign = lambda: -1.0 if rng.random() < 0.5 else 1.0
+    return np.array([side(-0.6, 0.8, _CTRL_MODE[0][i]), 0.5 * rng.standard_normal(), side(-0.4, 0.5, _CTRL_MODE[1][i]),
+                     q[pd_q] + sign() * rng.uniform(0.05, 0.5), v[pd_d] + sign() * rng.uniform(0.1, 1.0)])
+
+
+def _rows_weld(rng):
+    """two free bodies welded to each other (torquescale, anchor) ahead of a hinge / slide / hinge chain whose tip is welded to the world (negative solref, explicit
+    relpose).  The free pair moves as one by a random rigid motion per case; every welded pose is then left by a few millimetres and milliradians."""
+    free = "".join(f'<body name="{n}" pos="{p}" quat="{_fmt(_unit(rng, 4))}"><freejoint/><geom type="box" size="{s}" mass="{m}" contype="0" conaffinity="0"/></body>'
+                   for n, p, s, m in (("fa", "0.2 -0.1 0.3", "0.05 0.04 0.03", 0.4), ("fb", "0.32 -0.05 0.38", "0.04 0.06 0.03", 0.6)))
+    base = _tree_xml(rng, ["hinge", "slide", "hinge"], [-1, 0, 1], "Euler", fric=0, lim=0, actuators=False, extra_world=free, names=True)
+    q0 = np.asarray(compile_xml(base).tables["qpos0"], dtype=np.float64).reshape(-1)
+    xml = _sections(base, equality='<weld body1="fa" body2="fb" solref="0.05 1" torquescale="0.7" anchor="0.02 -0.01 0.03"/>' + _world_weld(base, np.r_[q0[:14], _WELD_QSTAR], "b2"))
+    q = np.zeros((ROWS_N, 17))
+    for i in range(ROWS_N):
+        r, t = _unit(rng, 4), 0.1 * rng.standard_normal(3)
+        for s in (0, 7):
+            q[i, s:s + 3] = quat_rot(r, q0[s:s + 3]) + t + _off(rng, 3)
+            q[i, s + 3:s + 7] = quat_mul(quat_mul(r, q0[s + 3:s + 7]), axis_angle(_unit(rng, 3), _off(rng)))
+        q[i, 14:] = _WELD_QSTAR + _off(rng, 3)
+    return [Variant(xml, range(ROWS_N), q, 0.1 * rng.standard_normal((ROWS_N, 15)))]
+
+
+def _rows_jeq(rng):
+    """a branching tree; j2 (first branch) follows a quartic of j4 (second branch), j1 follows j3 through the solref clamp, the third equality is switched off"""
+    xml = _sections(_tree_xml(rng, ["hinge", "hinge", "slide", "hinge", "hinge", "slide"], [-1, 0, 1, 0, 3, 0], "Euler", fric=0, lim=0, actuators=False),
+                    equality=_JEQ.format(a=2, b=4, c=1, d=3, e=5))
+    model = compile_xml(xml)
+    q = 0.3 * rng.standard_normal((ROWS_N, 6))
+    for i in range(ROWS_N):
+        q[i, _qadr(model, 2)] = _poly(_JEQ_POLY, q[i, _qadr(model, 4)]) + _off(rng)
+        q[i, _qadr(model, 1)] = -1.2 * q[i, _qadr(model, 3)] + _off(rng)
+    return [Variant(xml, range(ROWS_N), q, 0.5 * rng.standard_normal((ROWS_N, 6)))]
+
+
+def _rows_tendon(rng):
+    xml = _sections(_tree_xml(rng, ["hinge", "slide", "hinge", "hinge", "slide", "hinge", "slide"], [-1, 0, 1, 0, 3, 0, 5], "Euler", fric=0, lim=0, actuators=False),
+                    tendon=_TENDONS.format(a=2, b=4, c=1, d=5, e=6, f=3))
+    model = compile_xml(xml)
+    q = 0.3 * rng.standard_normal((ROWS_N, 7))
+    for i in range(ROWS_N):
+        _solve_tendons(rng, model, q[i], i, (2, 1, 6))
+    return [Variant(xml, range(ROWS_N), q, 0.5 * rng.standard_normal((ROWS_N, 7)))]
+
+
+def _rows_actuator(rng):
+    xml = _sections(_tree_xml(rng, ["hinge", "slide", "hinge", "hinge", "hinge"], [-1, 0, 1, 0, 3], "Euler", fric=0, lim=0, actuators=False), actuator=_ACTUATORS.format(a=0, b=1, c=2, d=3))
+    model = compile_xml(xml)
+    q, v = 0.3 * rng.standard_normal((ROWS_N, 5)), 1.0 * rng.standard_normal((ROWS_N, 5))
+    ctrl = np.array([_actuator_ctrl(rng, q[i], v[i], i, _qadr(model, 3), _dadr(model, 3)) for i in range(ROWS_N)])
+    return [Variant(xml, range(ROWS_N), q, v, ctrl)]
+
+
+_MIXED_PARENTS = [-1, 0, 1, -1, 3, 4, 3, 6, -1, 8, 8, 10, 9, 11]
+_MIXED_JOINTS = ["hinge", "slide", "hinge", "hinge", "hinge", "slide", "hinge", "hinge", "hinge", "slide", "hinge", "hinge", "hinge", "slide"]
+_MIXED = {}
+_MIXED_LIMITS = {12: (-0.3, 0.4, 0.003), 13: (-0.06, 0.08, 0.002)}      # joint: lower end, upper end, margin
+
+
+def rows_mixed(name, site=False):
+    """(xml, qpos, qvel, ctrl) of rows-mixed-euler / rows-mixed-rk4: fourteen hinge / slide joints in three trees and a trailing free sphere, nv = 20 -- the register-resident
+    solve and the MFMA Hessian with multi-entry rows that are no contact rows.  One world holds equality, friction-loss, joint-limit, tendon-limit and contact rows:
+      tree 1  j0 j1 j2, the tip b2 welded to the world at _WELD_QSTAR (negative solref, explicit relpose)
+      tree 2  j3 with the branches j4 j5 and j6 j7, whose tips b5 and b7 are welded to each other where qpos0 has them (torquescale, anchor): 6 rows over dofs 3 .. 7
+      tree 3  j8 with j9 - j12 and j10 - j11 - j13; j9 follows a quartic of j11, j10 follows j3 through the solref clamp, a third equality is switched off
+      tendons over j8 j1 (two trees), j11 j5 (margin, negative solreflimit) and j3 j6 j6; friction loss on j1, j9, j12, j13; limits with a margin on j12, j13
+      the actuators of _ACTUATORS on j12, j13, j8 and the position / velocity pair on j3
+      a free sphere, declared last, 0.5 mm inside a plane, condim 3
+    site: a named site on b2, the tip of the first chain (tests/sim_dyn_cases.py)."""
+    if (name, site) in _MIXED:
+        return _MIXED[name, site]
+    rng = np.random.default_rng([0xD44, _name_seed(name)])
+    plane = '<geom type="plane" size="3 3 0.1" contype="0" conaffinity="1" condim="3"/>'
+    tail = f'<body pos="2 -2 {_R_FREE}"><freejoint/><geom type="sphere" size="{_R_FREE}" mass="0.3" contype="1" conaffinity="0" condim="3"/></body>'
+    tip = (lambda k: '<site name="tip" pos="0.03 0.01 0.05"/>' if k == 2 else "") if site else None
+    base = _tree_xml(rng, _MIXED_JOINTS, _MIXED_PARENTS, "RK4" if name.endswith("rk4") else "Euler", fric=0, lim=0, actuators=False, extra_world=plane, extra_body=tip, tail=tail, names=True)
+    for k, (lo, hi, mg) in _MIXED_LIMITS.items():
+        base = _with(base, k, f'limited="true" range="{lo} {hi}" margin="{mg}"')
+    for k, fl in ((1, 0.15), (9, 0.25), (12, 0.2), (13, 0.3)):
+        base = _with(base, k, f'frictionloss="{fl}"')
+    model = compile_xml(base)
+    nq, nv = model.dim("nq"), model.dim("nv")
+    qa, da = (lambda k: _qadr(model, k)), (lambda k: _dadr(model, k))
+    qstar = np.zeros(nq)
+    qstar[-4] = 1.0
+    qstar[[qa(0), qa(1), qa(2)]] = _WELD_QSTAR
+    xml = _sections(base, equality='<weld body1="b5" body2="b7" torquescale="0.7" anchor="0.02 -0.01 0.03"/>' + _world_weld(base, qstar, "b2") + _JEQ.format(a=9, b=11, c=10, d=3, e=8),
+                    tendon=_TENDONS.format(a=8, b=1, c=11, d=5, e=3, f=6), actuator=_ACTUATORS.format(a=12, b=13, c=8, d=3))
+    model = compile_xml(xml)
+    q, v, ctrl = np.zeros((ROWS_N, nq)), 0.3 * rng.standard_normal((ROWS_N, nv)), np.zeros((ROWS_N, 5))
+    for i in range(ROWS_N):
+        for k in range(3):
+            q[i, qa(k)] = _WELD_QSTAR[k] + _off(rng)
+        for k in (4, 5, 6, 7):
+            q[i, qa(k)] = _off(rng)
+        for k in (3, 8, 11):
+            q[i, qa(k)] = 0.3 * rng.standard_normal()
+        _solve_tendons(rng, model, q[i], i, (8, 11, 3))
+        q[i, qa(9)] = _poly(_JEQ_POLY, q[i, qa(11)]) + _off(rng)
+        q[i, qa(10)] = -1.2 * q[i, qa(3)] + _off(rng)
+        for n, (k, (lo, hi, mg)) in enumerate(_MIXED_LIMITS.items()):
+            q[i, qa(k)] = _band(rng, lo, hi, mg, (i + n) % 3)
+        q[i, -7:] = np.r_[2.0 + 0.1 * rng.standard_normal(), -2.0 + 0.1 * rng.standard_normal(), _R_FREE - 5e-4, _unit(rng, 4)]
+        v[i, -6:] = 0.1 * rng.standard_normal(6)
+        ctrl[i] = _actuator_ctrl(rng, q[i], v[i], i, qa(3), da(3))
+    _MIXED[name, site] = (xml, q, v, ctrl)      # read only
+    return _MIXED[name, site]
+
+
+def _rows_mixed(name):
+    xml, q, v, ctrl = rows_mixed(name)
+    var = Variant(xml, range(ROWS_N), q, v, ctrl)
+    assert 16 <= var.nv <= 24 and trailing_free_object(var.model), (name, "the compiled model does not report the trailing free object")
+    var.want_contact = True
+    return [var]
+
+
+def _rows_options(rng):
+    """a box on a plane, condim 4, gravity off the axis so that it slides: impratio="4" (cases 0 .. 3) and impratio="0.5" noslip_iterations="3" (cases 4 .. 6).  Poses as
+    in the plane pair groups: the lowest corner 0 .. 2 mm deep, the box turned about the normal and tilted by 0.5 .. 3 mrad"""
+    xml = lambda opt: (f'<mujoco><option timestep="0.002" gravity="1.5 -2 -9" {opt}/><worldbody><geom type="plane" size="2 2 0.1" condim="4" friction="0.8 0.02 0.002"/>'
+                       '<body pos="0 0 1"><freejoint/><geom type="box" size="0.05 0.04 0.03" mass="0.4" condim="4" friction="0.8 0.02 0.002"/></body></worldbody></mujoco>')
+    corners = np.array([[sx * 0.05, sy * 0.04, sz * 0.03] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)])
+    q, v = np.zeros((ROWS_N, 7)), 0.3 * rng.standard_normal((ROWS_N, 6))
+    for i in range(ROWS_N):
+        th = rng.uniform(0, 2 * np.pi)
+        r = quat_mul(axis_angle([np.cos(th), np.sin(th), 0.0], rng.uniform(5e-4, 3e-3)), axis_angle([0, 0, 1], rng.uniform(-np.pi, np.pi)))
+        low = min(quat_rot(r, c)[2] for c in corners)
+        q[i] = np.r_[0.3 * rng.standard_normal(2), -low - rng.uniform(0.0, 2e-3), r]
+    out = []
+    for opt, idx in (('impratio="4"', range(0, 4)), ('impratio="0.5" noslip_iterations="3"', range(4, ROWS_N))):
+        var = Variant(xml(opt), idx, q[list(idx)], v[list(idx)])
+        var.want_contact = True
+        out.append(var)
+    return out
+
+
+def build_rows_group(spec, gidx):
+    name, = spec
+    if name.startswith("rows-mixed"):
+        return Group(name, "rows", "rows", _rows_mixed(name))
+    rng = np.random.default_rng([0xD44, _name_seed(name)])
+    variants = {"rows-weld": _rows_weld, "rows-jeq": _rows_jeq, "rows-tendon": _rows_tendon, "rows-actuator": _rows_actuator, "rows-options": _rows_options}[name](rng)
+    assert all(var.nq >= 2 for var in variants)
+    return Group(name, "rows", "rows", variants)
+
+
+def oracle_rows(var):
+    """per case, from one forward pass of the oracle at the start state: ncon, nefc, the row counts ne (equality), nf (friction loss), nl (limits, joint and tendon), ntl
+    (tendon limits among them), the noslip sweeps taken, and the residuals efc_pos"""
+    sim, out = _oracle(var.model), []
+    for i in range(len(var.idx)):
+        sim.reset_data()
+        sim.qpos[:], sim.qvel[:], sim.qacc_warmstart[:] = var.q0[i], var.v0[i], 0.0
+        if sim.nu:
+            sim.ctrl[:] = var.ctrl[i][:sim.nu]
+        sim.forward()
+        row = {k: int(sim._L.orc_int(sim._h, k.encode())) for k in ("ncon", "nefc", "ne", "nf", "nl", "ntl")}
+        out.append(dict(row, noslip_iter=int(sim.noslip_iter), pos=sim.efc("pos")))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+ALL = [("pair", s) for s in pair_groups()] + [("tree", s) for s in tree_groups()] + [("solve", s) for s in solve_groups()] + [("rows", s) for s in rows_groups()]
 NAMES = [s[0] for _, s in ALL]
 _BUILT = {}
 
@@ -525,5 +816,5 @@ def group(name):
     if name not in _BUILT:
         gidx = NAMES.index(name)
         kind, spec = ALL[gidx]
-        _BUILT[name] = {"pair": build_pair_group, "tree": build_tree_group, "solve": build_solve_group}[kind](spec, gidx)
+        _BUILT[name] = {"pair": build_pair_group, "tree": build_tree_group, "solve": build_solve_group, "rows": build_rows_group}[kind](spec, gidx)
     return _BUILT[name]

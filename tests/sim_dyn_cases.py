@@ -5,6 +5,9 @@ anchor .. the arm scene with two more sites: `base` on the world body (its Jacob
           merges into link2 (a site of a merged static child).  Three of the four sites are selected, in an order that differs from their site ids.  Same starts as arm.
 pile16 .. the pile of sim_cases with sixteen spheres, every one pressed into the plane, on the default tables: sixteen sites, as many as one launch carries, all selected in
           a scrambled order.  pile17 has one site too many for jac_sites=None.
+rows .... the model and the first worlds of the engine matrix's rows-mixed-euler group (engine_matrix_cases.rows_mixed) with a site on the tip of its welded chain: welds, joint
+          equalities, friction loss, joint and tendon limits and a contact in every world (nefc > 0: the in-LDS qacc_smooth solve), and qfrc_actuator with both clamps and
+          with two actuators on one joint, whose forces add.  Compared like the others, within the bounds the other scenes set.
 
 Error measure.  qM, site_jacp and site_jacr are compared absolutely (entries are O(1)).  The eight force / acceleration vectors are compared per world as
 max |got - want| / max(1, max |want|): the arm's qacc reaches 1.5e3, where an absolute 1e-4 would ask more than fp32 holds."""
@@ -42,13 +45,41 @@ def _pilek_states(model, n, seed):
     return dict(qpos=q, qvel=v, ctrl=np.zeros((n, nu)), mocap_pos=np.zeros((n, nm, 3)), mocap_quat=np.zeros((n, nm, 4)))
 
 
-S._STATES.update(anchor=S._arm_states, pile16=_pilek_states, pile17=_pilek_states)
+def _rows_states(model, n, seed):
+    """the first n cases of rows-mixed-euler"""
+    nm = model.dim("nmocap")
+    _, q, v, ctrl = C.rows_mixed("rows-mixed-euler", site=True)
+    assert n <= len(q) and q.shape[1] == model.dim("nq")
+    return dict(qpos=q[:n], qvel=v[:n], ctrl=ctrl[:n], mocap_pos=np.zeros((n, nm, 3)), mocap_quat=np.zeros((n, nm, 4)))
+
+
+S._STATES.update(anchor=S._arm_states, pile16=_pilek_states, pile17=_pilek_states, rows=_rows_states)
 SCENES = dict(S.SCENES, anchor=S.Scene("anchor", ANCHOR_XML, 15, compile_kwargs=dict(touch_filter=lambda name: True, keep_sites=("ee", "pad", "base", "elbow"))))
+
+
+class _RowsScene(S.Scene):
+    """the rows scene: its MJCF comes from engine_matrix_cases.rows_mixed, which asks the oracle for the welded pose, so it is written on first use and not at import"""
+    def __init__(self):
+        super().__init__("rows", None, 18)
+
+    @property
+    def xml(self):
+        if self._xml is None:
+            self._xml = C.rows_mixed("rows-mixed-euler", site=True)[0]
+        return self._xml
+
+    @xml.setter
+    def xml(self, text):
+        self._xml = text
+
+
+SCENES.update(rows=_RowsScene())
 SCENES.update(pile16=S.Scene("pile16", _pile_xml(16), 16), pile17=S.Scene("pile17", _pile_xml(17), 17))      # 16 sites: the most one launch carries; 17: one too many
 # the selected sites of each scene, in the order of the rows of site_jacp / site_jacr
-JAC_SITES = {"arm": ("ee", "pad"), "mocap": ("grip", "pegtip"), "rk4": ("imu", "tip"), "anchor": ("elbow", "base", "ee"), "pile": ("c3", "c0"),
+JAC_SITES = {"arm": ("ee", "pad"), "mocap": ("grip", "pegtip"), "rk4": ("imu", "tip"), "anchor": ("elbow", "base", "ee"), "pile": ("c3", "c0"), "rows": ("tip",),
              "pile16": tuple(f"c{(5 * k) % 16}" for k in range(16))}
-CASES = [(s, k) for s in ("arm", "mocap", "rk4", "anchor") for k in (0, 1, 4)]
+BOUND_SCENES = ("arm", "mocap", "rk4", "anchor")      # the scenes whose measured errors set the vector bounds (tests/test_gpu_sim_dynamics.py); rows is held to them
+CASES = [(s, k) for s in BOUND_SCENES for k in (0, 1, 4)] + [("rows", 0), ("rows", 1)]
 
 
 def jac_ids(scene):

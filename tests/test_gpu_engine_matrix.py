@@ -1,7 +1,8 @@
 """The generated scenes of tests/engine_matrix_cases.py on the GPU (pytest -m gpu): the generic kernel (GrxEngine<GrxShapeAny>, grx_point_step with agent = 1) takes one
 step from each case's state, one world per case, and has to land where the live fp64 oracle lands -- the narrow-phase routines away from symmetric rest poses, free
 joints under fast spin, and every size class of grx_sym_solve_full inside a real step (register-resident 14 .. 36, the two-block routes behind a trailing free body, the LDS route
-next to them).  Acceptance rule and caps: engine_matrix_cases.accept -- the same as on the emulator (tests/test_cpu_engine_matrix.py)."""
+next to them), and the row groups: welds, joint equalities, tendon limits and summed actuators, whose multi-entry spans feed the MFMA Hessian's operand fetch and whose
+blocks the wave scans place between the limit and the contact rows).  Acceptance rule and caps: engine_matrix_cases.accept -- the same as on the emulator (tests/test_cpu_engine_matrix.py)."""
 import ctypes
 import json
 import os
