@@ -243,6 +243,11 @@ struct GrxCtx {
                             // the pass grx_fetch_outputs reads).  sites_every: that caller leaves sites at 1 in every pass (GrxFetchBuffers::sites_every_substep)
   float* meshcache;  // models with hull-vs-convex pairs: 4 x (pair + 1, separating direction, the two support vertices) + the slot to evict next, kept across the substeps of a step (grx_mesh_pairs)
   int mslot;   // slot of this world's model in g_grx_models (GPU build)
+#if defined(GRX_PARAM_MODEL)
+  const GrxModel* pmodel;   // the kernels with per-world model parameters (csrc/grx_sim_params.h): this world's own descriptor in HBM, which GRX_FRESH_MODEL resolves to instead of the slot
+  // NOTE: with this member GrxCtx (like GrxSimModelArg and the signature of grx_sim_step_world in grx_kernels.hip) differs between the units linked into one library.  That holds
+  // only because GrxCtx is DEVICE-ONLY and every unit is a code object of its own: no host code, and nothing in the lane emulator, may pass a GrxCtx between units.
+#endif
   int bail;    // != 0: a step kernel that hands capacity overflows to a re-run at a larger capacity stops simulating at the first overflowing substep (nothing of this run is kept)
   int soft_maxefc, soft_jpool, soft_maxcon;   // > 0 (the large-table kernel of the overflow lane): the capacities of the FAST kernel; exceeding one of them raises GRX_ST_SOFT
   int *lane_entry_count, *lane_entry_list; int lane_entry_cap, lane_world; int* lane_ready; int lane_ready_cap;   // fast kernel with an overflow lane: where a world that overflows claims its re-run (grx_lane_claim)
@@ -277,7 +282,17 @@ struct GrxCtx {
 #define GRX_OPAQUE_STAGE(l) do { if constexpr (S::kOpaque) GRX_OPAQUE_LANE(l); } while (0)
 #define GRX_MAX_MODELS 32
 static __constant__ GrxModel g_grx_models[GRX_MAX_MODELS];   // one copy per translation unit (see csrc/grx_kernels.hip on the build)
+#if defined(GRX_PARAM_MODEL)
+// A translation unit compiled with GRX_PARAM_MODEL holds only the step kernels whose worlds each have a descriptor of their own in HBM (GrxCtx::pmodel).  A wave owns one world, so
+// the address is wave-uniform: both halves go through readfirstlane and the table pointers of a stage are still fetched with scalar loads at its top, now from HBM.
+// The pointer is formed in the constant address space, where g_grx_models lives too: no launch that reads a descriptor writes one (a commit is a launch of its own), and a
+// stage may then re-load a table pointer where it needs it instead of keeping it live across the stores in between -- as a plain global pointer the step kernel had
+// 936 B of scratch per lane instead of 288 B (the slot kernel: 320 B).
+#define GRX_FRESH_MODEL(m, c) do { const unsigned long long a_ = (unsigned long long)(c)->pmodel; unsigned lo_ = __builtin_amdgcn_readfirstlane((unsigned)a_), hi_ = __builtin_amdgcn_readfirstlane((unsigned)(a_ >> 32)); \
+    asm volatile("" : "+s"(lo_), "+s"(hi_)); (m) = (const GrxModel*)(const __attribute__((address_space(4))) GrxModel*)(((unsigned long long)hi_ << 32) | lo_); } while (0)
+#else
 #define GRX_FRESH_MODEL(m, c) do { int s_ = __builtin_amdgcn_readfirstlane((c)->mslot); asm volatile("" : "+s"(s_)); (m) = g_grx_models + s_; } while (0)
+#endif
 #endif
 
 // LDS layout.  Arrays that only live in the position/velocity stages of a substep (P1: local poses, spatial inertias,

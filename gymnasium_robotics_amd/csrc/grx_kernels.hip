@@ -8,7 +8,11 @@
 // library, eight times in parallel with -DGRX_TU_FETCH / -DGRX_TU_HAND / -DGRX_TU_POINT / -DGRX_TU_ADROIT / -DGRX_TU_KITCHEN / -DGRX_TU_SIM / -DGRX_TU_SIMDYN / -DGRX_TU_API (one family of kernel
 // instantiations each; __graft_entry__.build links the objects).  Every unit has its own copy of the constant-memory model descriptors
 // (g_grx_models is static): grx_model_create uploads a descriptor to each of them through grx_tu_*_prepare.
-#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API)
+// Two more units, -DGRX_TU_SIMPRM / -DGRX_TU_SIMDYNPRM, hold the task-free stepper's kernels for worlds with per-world model parameters (csrc/grx_sim_params.h) and the commit
+// kernels: they are compiled with GRX_PARAM_MODEL, under which every stage takes its model from the world's own descriptor in HBM (GRX_FRESH_MODEL, csrc/grx_engine.h), so
+// nothing else can share a unit with them and the single-unit build has stubs in their place (GRX_TU_ALL).
+#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM)
+#define GRX_TU_ALL 1
 #define GRX_TU_FETCH 1
 #define GRX_TU_HAND 1
 #define GRX_TU_POINT 1
@@ -22,6 +26,9 @@
 // code is compiled into the Fetch kernels only -- in the hand / kitchen kernels it would be dead weight in a register-starved routine (measured: -1 ... -2.5 %).
 #if GRX_TU_FETCH && !defined(GRX_NO_HULL_HINTS)
 #define GRX_HULL_HINTS 1
+#endif
+#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM
+#define GRX_PARAM_MODEL 1
 #endif
 #include <hip/hip_runtime.h>
 
@@ -38,6 +45,7 @@
 #include "grx_adroit_task.h"
 #include "grx_kitchen_task.h"
 #include "grx_sim_task.h"
+#include "grx_sim_params.h"
 #include "grx_host_model.h"
 #include "grx_copy.h"
 #include "grx_step_frame.h"
@@ -798,13 +806,30 @@ grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_
 // DYN: the instance that serves the second output block (GrxSimDynamics), in kernels of its own (grx_sim_step_dyn_kernel, grx_sim_lane_dyn_kernel; translation unit GRX_TU_SIMDYN).  A launch that requests
 // none of its outputs runs the kernels without the block (d = nullptr, DYN = false): the stepper as it was before the block existed, argument list included -- the second
 // inlined copy of the forward pass costs the DYN instance 250 B of scratch per lane and took 5 % off a launch that shared a kernel with it (profiles/sim_probe_dynamics.txt).
+// PER-WORLD MODEL PARAMETERS (csrc/grx_sim_params.h): in a unit compiled with GRX_PARAM_MODEL the first argument is the array of per-world descriptors in HBM instead of the
+// slot, and m -- like every GRX_FRESH_MODEL of the stages -- is world w's descriptor.  w is wave-uniform; both halves of the address go through readfirstlane so that it sits
+// in SGPRs and the descriptor's members are scalar loads.  The units without the macro compile the lines they always compiled.
+#if defined(GRX_PARAM_MODEL)
+typedef const GrxModel* GrxSimModelArg;
+#else
+typedef int GrxSimModelArg;
+#endif
 template <class S, bool DYN>
-__device__ __forceinline__ void grx_sim_step_world(int mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_) {
+__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_) {
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
-  const GrxModel& m = g_grx_models[mslot];
   GrxCtx c;
+#if defined(GRX_PARAM_MODEL)
+  const GrxModel* mp;
+  c.pmodel = mslot + w;
+  c.mslot = 0;
+  GRX_FRESH_MODEL(mp, &c);
+  c.pmodel = mp;
+  const GrxModel& m = *mp;
+#else
+  const GrxModel& m = g_grx_models[mslot];
   c.mslot = mslot;
+#endif
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
   GRX_PROF_BEGIN(c, lane_);
   grx_lane_setup(b.lane, c, w, true);
@@ -850,6 +875,38 @@ grx_sim_lane_dyn_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, int n_worl
   extern __shared__ float lds[];
   grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
 }
+#if defined(GRX_PARAM_MODEL)
+// the same four kernels for worlds with per-world model parameters: desc[w] is world w's descriptor (grx_sim_params_create)
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_prm_kernel(const GrxModel* desc, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, false>(desc, b, nullptr, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_prm_kernel(const GrxModel* desc, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, false>(desc, b, nullptr, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_dyn_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, true>(desc, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_dyn_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(desc, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
+}
+#if GRX_TU_SIMPRM
+// the commit (csrc/grx_sim_params.h): two launches behind each other on the caller's stream, one wave per world
+__global__ void __launch_bounds__(64) grx_param_commit_rows_kernel(GrxParamCommit a) { grx_param_commit_rows(a, (int)blockIdx.x, (int)threadIdx.x); }
+__global__ void __launch_bounds__(64) grx_param_commit_records_kernel(GrxParamCommit a) { grx_param_commit_records(a, (int)blockIdx.x, (int)threadIdx.x); }
+#endif
+#endif
 
 // ------------------------------------------------------------------------------------------
 // per-family translation units: shape selection, LDS limits, descriptor upload, launches
@@ -886,6 +943,12 @@ int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* strea
 int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words, int forward_only);
 int grx_tu_sim_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
 int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
+// the units with per-world model parameters: no descriptor slot (desc: the per-world descriptors in HBM); the first of the two also holds the commit kernels
+int grx_tu_simprm_prepare(int bytes);
+int grx_tu_simdynprm_prepare(int bytes);
+int grx_tu_simprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
+int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
+int grx_tu_simprm_commit(const GrxParamCommit* a, void* stream);
 }
 // Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
 // overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
@@ -1081,6 +1144,41 @@ extern "C" int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* strea
   else hipLaunchKernelGGL(grx_sim_step_dyn_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, n, words, nstep, forward_only);
   return (int)hipGetLastError();
 }
+#endif
+#if GRX_TU_SIMPRM
+extern "C" int grx_tu_simprm_prepare(int bytes) {
+  GRX_LDS(grx_sim_step_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_prm_kernel<GrxShapeAny>);
+  return 0;
+}
+extern "C" int grx_tu_simprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+extern "C" int grx_tu_simprm_commit(const GrxParamCommit* a, void* stream) {
+  hipLaunchKernelGGL(grx_param_commit_rows_kernel, dim3((unsigned)a->n_worlds), dim3(64), 0, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(grx_param_commit_records_kernel, dim3((unsigned)a->n_worlds), dim3(64), 0, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+#endif
+#if GRX_TU_SIMDYNPRM
+extern "C" int grx_tu_simdynprm_prepare(int bytes) {
+  GRX_LDS(grx_sim_step_dyn_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_dyn_prm_kernel<GrxShapeAny>);
+  return 0;
+}
+extern "C" int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_dyn_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_dyn_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
+#if defined(GRX_TU_ALL)
+// the single-unit build cannot hold the GRX_PARAM_MODEL kernels: a parameter object cannot be created there (grx_sim_params_create fails on the first of these)
+extern "C" int grx_tu_simprm_prepare(int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simdynprm_prepare(int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, int, int, int, int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simdynprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, int, int, int, int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simprm_commit(const GrxParamCommit*, void*) { return (int)hipErrorNotSupported; }
 #endif
 #undef GRX_LDS
 
@@ -1433,7 +1531,8 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
 
 // The argument checks that do not need the model come first and read nothing of it (tests/test_cpu_sim.py reaches them without a device).
 // grx_sim_step is this call without the second block; the messages keep its name.
-extern "C" int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream) {
+// desc: null, or the per-world descriptors of a parameter object made for m (grx_sim_step_params): the launch then goes to the kernels of the parameter units
+static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc) {
   if (!m) return fail("grx_sim_step: null model");
   if (!buf) return fail("grx_sim_step: null buffers");
   if (!buf->qpos || !buf->qvel || !buf->qacc_ws) return fail("grx_sim_step: null state buffer (qpos, qvel, qacc_ws)");
@@ -1459,11 +1558,18 @@ extern "C" int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, 
   // a launch that requests none of the ten runs the kernels without the block
   const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
   const unsigned grid = grx_step_grid(b.lane, 0, 0, n_worlds); const size_t lds_bytes = (size_t)m->words * 4 + m->lds_pad;
-  const int e = dynamic ? grx_tu_simdyn_launch(grid, lds_bytes, stream, m->slot, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
-                        : grx_tu_sim_launch(grid, lds_bytes, stream, m->slot, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  int e;
+  if (desc) e = dynamic ? grx_tu_simdynprm_launch(grid, lds_bytes, stream, desc, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+                        : grx_tu_simprm_launch(grid, lds_bytes, stream, desc, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  else e = dynamic ? grx_tu_simdyn_launch(grid, lds_bytes, stream, m->slot, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+                   : grx_tu_sim_launch(grid, lds_bytes, stream, m->slot, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
   if (e) return fail(std::string("grx_sim_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
+extern "C" int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream) {
+  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, nullptr);
+}
+#include "grx_sim_params_api.h"
 extern "C" int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream) {
   return grx_sim_step_dyn(m, buf, nullptr, n_worlds, nstep, forward_only, stream);
 }

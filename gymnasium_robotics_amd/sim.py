@@ -25,7 +25,22 @@ The dynamics of the same pass are outputs too: ``qM`` (dense ``mj_fullM``), ``qf
 ``xpos`` / ``xquat`` index the COMPILED model's bodies: the compiler merges static children into their parents, ``sim.model.names["body"]`` maps the surviving names to rows.
 Sites keep their identity whatever body they end up on: they are the stable handle for "where is this point of my robot".
 
-Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world model edits.
+PER-WORLD MODEL PARAMETERS (domain randomization): ``model_params`` names the model tables whose values differ from world to world, any of ``sim.PARAMS``.  Each is a device
+tensor ``sim.params.<name>`` of shape [N, ...], initialised to the model's own fp32 values; write it with any torch op, then ``sim.commit_params()`` makes the values take effect
+for the launches that follow.  The meaning is that of writing the same ``MjModel`` fields in place, world by world, WITHOUT ``mj_setConst``: what the compiler derived from them
+(``dof_invweight0``, ``geom_invweight0``, ``eq_invweight``, ``tendon_invweight0``, ``meaninertia``, the structural counts) keeps the nominal model's value -- exactly what the fp64 oracle
+does when the same table is written through ``OracleSim.model_table``, which is the operational definition.  The structure stays the nominal model's: a world whose row breaks a rule
+(a non-finite value, ``dof_frictionloss`` switched on or off, a negative mass, ... include/grx_capi.h) keeps the parameters of its last good commit and ``sim.params_invalid[w]`` says
+which rule; a commit never raises and never synchronises.  Friction is a property of the candidate PAIR in the compiled model: ``sim.pair_ids("geom")`` gives the rows.
+
+    sim = grx.BatchedSim("my_robot.xml", 4096, model_params=("body_mass", "dof_damping", "pair_friction", "gravity"))
+    sim.params.body_mass *= torch.empty_like(sim.params.body_mass).uniform_(0.5, 2.0)
+    sim.params.pair_friction[:, sim.pair_ids("foot"), 0] = torch.empty(4096, 1, device="cuda").uniform_(0.5, 1.5)
+    sim.params.gravity[:, 2] = -9.81 * torch.empty(4096, device="cuda").uniform_(0.9, 1.1)
+    sim.commit_params()
+    assert not sim.params_invalid.any()
+
+Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses.
 """
 import ctypes
 
@@ -37,17 +52,27 @@ STATE = ("qpos", "qvel", "qacc_warmstart", "ctrl", "mocap_pos", "mocap_quat")
 DYNAMICS = ("qM", "qfrc_smooth", "qacc_smooth", "qfrc_constraint", "qacc", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "site_jacp", "site_jacr")      # grx_sim_dynamics, in its order
 JACOBIANS = ("site_jacp", "site_jacr")
 OUTPUTS = ("xpos", "xquat", "site_xpos", "site_xmat", "site_xvelp", "site_xvelr", "sensordata", "ncon", "nefc") + DYNAMICS
+PARAMS = ("gravity", "body_mass", "body_inertia", "dof_damping", "dof_armature", "dof_frictionloss", "jnt_stiffness", "jnt_springref", "jnt_range", "act_gear", "act_gainprm",
+          "act_biasprm", "act_ctrlrange", "act_forcerange", "pair_friction", "pair_solref", "pair_solimp")      # include/grx_capi.h grx_sim_params_create
+PARAM_BAD = dict(nonfinite=1, frictionloss=2, damping=4, inertial=8, armature=16, jnt_range=32, act_range=64)      # GRX_PARAM_BAD_*: the bits of params_invalid
 MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
 
 
+class _Params:
+    """sim.params: one attribute per named table, the [N, ...] device tensor the caller writes"""
+
+    def __repr__(self):
+        return "params(" + ", ".join(f"{k}{tuple(v.shape)}" for k, v in self.__dict__.items()) + ")"
+
+
 class BatchedSim:
-    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None):
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=()):
         """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
         default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
         again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
         CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
         keep_sites, mutate, ...).  jac_sites: the names of the sites whose Jacobians site_jacp / site_jacr hold, in the order of their rows (None: every site of the model, which must
-        then have at most 16).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        then have at most 16).  model_params: the tables that are per world, any of sim.PARAMS (module docstring).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
         if int(num_worlds) < 1:
             raise ValueError("num_worlds must be at least 1")
         if overflow not in ("rerun", "flag"):
@@ -59,6 +84,15 @@ class BatchedSim:
             raise ValueError(f"unknown output(s) {unknown}; the optional outputs are {OUTPUTS}")
         if capacity is not None and not set(capacity) <= {"maxcon", "maxefc", "jpool"}:
             raise ValueError(f"capacity takes maxcon, maxefc and jpool, not {sorted(set(capacity) - {'maxcon', 'maxefc', 'jpool'})}")
+        if isinstance(model_params, str):
+            model_params = (model_params,)
+        model_params = tuple(model_params)
+        unknown = [p for p in model_params if p not in PARAMS]
+        if unknown:
+            raise ValueError(f"unknown model parameter(s) {unknown}; the per-world parameters are {PARAMS}")
+        if len(set(model_params)) != len(model_params):
+            raise ValueError(f"model_params names a parameter twice: {model_params}; the per-world parameters are {PARAMS}")
+        self.param_names = tuple(p for p in PARAMS if p in model_params)
         kw = dict(compile_kwargs or {})
         if kw.get("origin") is not None or kw.get("shift_body") is not None:
             raise ValueError("BatchedSim returns raw engine coordinates: compile the model in the MJCF's own frame (no origin) and without a shift group")
@@ -98,7 +132,7 @@ class BatchedSim:
         if wants_jac and not self._jac_ids:
             raise ValueError("site_jacp / site_jacr need at least one site (the model has none, or jac_sites is empty)")
         self._t = None      # the device tensors, made on first use
-        self._h = self._h_big = self.lane = None
+        self._h = self._h_big = self.lane = self._p = None
 
     # ------------------------------------------------------------------ names (CompiledModel.names / tables): no device needed
     def _lookup(self, kind, name):
@@ -133,6 +167,25 @@ class BatchedSim:
 
     def joint_dofadr(self, name):
         return int(np.asarray(self.model.tables["jnt_dofadr"]).reshape(-1)[self._lookup("joint", name)])
+
+    def pair_ids(self, geom_a, geom_b=None):
+        """rows of params.pair_friction / pair_solref / pair_solimp: the candidate pairs of the geom named geom_a (with geom_b: only those against that geom), ascending.
+        Friction, solref and solimp are properties of the PAIR in the compiled model (the compiler has combined the two geoms' values)."""
+        a = self._lookup("geom", geom_a)
+        g1, g2 = (np.asarray(self.model.tables[k]).reshape(-1) for k in ("pair_geom1", "pair_geom2"))
+        hit = (g1 == a) | (g2 == a)
+        if geom_b is not None:
+            b = self._lookup("geom", geom_b)
+            hit &= (g1 == b) | (g2 == b)
+        return [int(i) for i in np.nonzero(hit)[0]]
+
+    def _param_shape(self, name):
+        if name == "gravity":
+            return (self.num_worlds, 3)
+        shape = tuple(np.asarray(self.model.tables[name]).shape)
+        while len(shape) > 1 and shape[-1] == 1:      # jnt_stiffness is stored [njnt, 1]
+            shape = shape[:-1]
+        return (self.num_worlds,) + shape
 
     # ------------------------------------------------------------------ device side
     def _shapes(self):
@@ -179,6 +232,20 @@ class BatchedSim:
             self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
             if self._h_big is not None:
                 self.lane = OverflowLane(self.num_worlds, self.device, self.model, self._make_bufs, mode="entry")
+        if self.param_names:      # one parameter object serves the handle of the step launch and that of the re-run
+            from .env_capi import device_view
+
+            names = (ctypes.c_char_p * len(self.param_names))(*[p.encode() for p in self.param_names])
+            self._p = ctypes.c_void_p()
+            _native.check(self._L.grx_sim_params_create(self._h, self._h_big, self.num_worlds, names, len(self.param_names), ctypes.byref(self._p)))
+            self._params = _Params()
+            for name in self.param_names:
+                ptr, cnt = ctypes.c_void_p(), ctypes.c_int()
+                _native.check(self._L.grx_sim_params_row(self._p, name.encode(), ctypes.byref(ptr), ctypes.byref(cnt)))
+                shape = self._param_shape(name)
+                assert int(np.prod(shape[1:])) == cnt.value, (name, shape, cnt.value)
+                self._params.__dict__[name] = device_view(ptr.value, shape, np.float32, self.device)
+            t["params_invalid"] = torch.zeros(self.num_worlds, dtype=torch.int32, device=self.device)
         t["qpos"][:] = self._qpos0
         if self.nmocap:
             t["mocap_pos"][:], t["mocap_quat"][:] = self._mocap_pos0, self._mocap_quat0
@@ -192,6 +259,11 @@ class BatchedSim:
             return self.__dict__[name]
         if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()):
             return self._ensure()[name]
+        if name in ("params", "params_invalid"):
+            if not self.__dict__.get("param_names"):
+                raise AttributeError(f"no per-world parameters were named: BatchedSim(..., model_params=...), any of {PARAMS}")
+            t = self._ensure()
+            return t["params_invalid"] if name == "params_invalid" else self._params
         if name in OUTPUTS:
             raise AttributeError(f"output {name!r} was not requested: BatchedSim(..., outputs={self.__dict__.get('outputs', ())})")
         raise AttributeError(name)
@@ -230,7 +302,11 @@ class BatchedSim:
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            if self._dyn is None:
+            if self._p is not None:      # the kernels that take each world's model from its own descriptor
+                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
+                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_params(h, self._p, ctypes.byref(b), dyn, self.num_worlds, int(nstep), int(forward_only),
+                                                                                     stream_ptr(self.device))))
+            elif self._dyn is None:
                 go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream_ptr(self.device))))
             else:
                 go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_dyn(h, ctypes.byref(b), ctypes.byref(self._dyn), self.num_worlds, int(nstep), int(forward_only),
@@ -252,8 +328,26 @@ class BatchedSim:
         """mj_forward: the derived fields of the state as given; qpos / qvel are left as they are, the warm start is updated"""
         self._launch(0, 1, mask)
 
+    def commit_params(self, mask=None):
+        """make the rows of sim.params take effect for the launches that follow (mask: only the worlds with a non-zero entry).  Each selected world's entry of
+        params_invalid becomes 0, or the rules its row breaks (sim.PARAM_BAD); such a world keeps the parameters of its last good commit.  Enqueues on torch's current
+        stream; never raises for a value, never synchronises."""
+        import torch
+
+        from . import _native
+        from .core import stream_ptr
+
+        if not self.param_names:
+            raise RuntimeError("commit_params: no per-world parameters were named (BatchedSim(..., model_params=...))")
+        t = self._ensure()
+        m = self._mask(mask)
+        self._commit_mask_keep = m
+        with torch.cuda.device(self.device):
+            _native.check(self._L.grx_sim_params_commit(self._p, None if m is None else m.data_ptr(), t["params_invalid"].data_ptr(), stream_ptr(self.device)))
+
     def reset(self, mask=None):
-        """mj_resetData for the masked worlds (all by default): qpos0, zero velocities / warm start / ctrl, the model's mocap poses; then forward()"""
+        """mj_resetData for the masked worlds (all by default): qpos0, zero velocities / warm start / ctrl, the model's mocap poses; then forward().  The model parameters
+        are not state: they stay as committed."""
         import torch
 
         t = self._ensure()
@@ -296,7 +390,10 @@ class BatchedSim:
 
         t = self._ensure()
         torch.cuda.synchronize(self.device)
-        return {k: t[k].cpu().numpy().copy() for k in STATE + ("status_words",)}
+        d = {k: t[k].cpu().numpy().copy() for k in STATE + ("status_words",)}
+        if self.param_names:      # the rows as written (a row a commit refused included: set_state commits them again, with the same outcome)
+            d["params"] = {k: getattr(self._params, k).cpu().numpy().copy() for k in self.param_names}
+        return d
 
     def set_state(self, d):
         import torch
@@ -309,6 +406,18 @@ class BatchedSim:
                 raise ValueError(f"state row {k!r} has shape {tuple(np.shape(d[k]))}, this simulation holds {tuple(t[k].shape)}")
         for k in STATE + (("status_words",) if "status_words" in d else ()):
             t[k].copy_(torch.from_numpy(np.ascontiguousarray(d[k], dtype=np.int32 if k == "status_words" else np.float32)).to(self.device))
+        if "params" in d and self.param_names:      # (a state without the key leaves the parameters alone)
+            rows = d["params"]
+            if set(rows) != set(self.param_names):
+                raise ValueError(f"state holds the parameters {sorted(rows)}, this simulation {sorted(self.param_names)}")
+            for k in self.param_names:
+                dst = getattr(self._params, k)
+                if tuple(np.shape(rows[k])) != tuple(dst.shape):
+                    raise ValueError(f"parameter row {k!r} has shape {tuple(np.shape(rows[k]))}, this simulation holds {tuple(dst.shape)}")
+                dst.copy_(torch.from_numpy(np.ascontiguousarray(rows[k], dtype=np.float32)).to(self.device))
+            self.commit_params()
+        elif "params" in d:
+            raise ValueError("the state carries model parameters and this simulation names none")
 
     def close(self):
         from .core import release_models
@@ -317,6 +426,10 @@ class BatchedSim:
             import torch
 
             torch.cuda.synchronize(self.device)
+        if self.__dict__.get("_p") is not None:
+            self._params = None
+            self._L.grx_sim_params_destroy(self._p)
+            self._p = None
         release_models(self, ("_h", "_h_big"))
         self.lane = None
 

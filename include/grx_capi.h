@@ -414,6 +414,43 @@ typedef struct grx_sim_dynamics {
 int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_dynamics), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (13) */
 int grx_sim_dynamics_layout(long long* out, int cap);
+/* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
+ *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
+ *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)
+ * MEANING: that of writing the same MjModel fields in place, world by world, WITHOUT mj_setConst: everything the compiler derived from them keeps the nominal model's value
+ * (dof_invweight0, geom_invweight0, eq_invweight, tendon_invweight0, meaninertia, the structural counts).  It is what the fp64 oracle does when the same table is written
+ * through OracleSim.model_table: the oracle is the operational definition.  Tables that feed host-built structures (geom sizes, bounds, meshes, gates, the grid, poses)
+ * cannot be per world.
+ * grx_sim_params_create: model_large is the handle of the same model with the large tables of the overflow re-run, or NULL; the object serves both handles.  Each named table
+ *   gets a device row [n_worlds, count] (grx_sim_params_row), initialised to the model's own fp32 values, which the caller writes on its stream; the step launches never
+ *   read these rows.  Fails for an unknown or duplicate name (the message lists the names), n_worlds < 1, NULL arguments, a large handle whose table shapes differ.
+ * grx_sim_params_commit: makes the rows take effect for the launches enqueued behind it on `stream`.  mask [n_worlds] uint8 or NULL selects the worlds; invalid [n_worlds]
+ *   int32 or NULL receives, per selected world, 0 or the rules it breaks (GRX_PARAM_BAD_*).  A world that breaks a rule KEEPS the parameters of its last good commit.  Two
+ *   small launches; never waits, never fails for a value.  The rules: every value finite; dof_frictionloss > 0 exactly where the nominal value is (the number of friction
+ *   rows is structure); dof_damping >= 0, and 0 everywhere if the nominal model has no damped dof; body_mass / body_inertia > 0 wherever the nominal ones are;
+ *   dof_armature >= 0; jnt_range[0] < jnt_range[1] for limited joints; act_ctrlrange and act_forcerange ordered.
+ * grx_sim_step_params: grx_sim_step_dyn (dyn may be NULL) on the per-world parameters; m is either handle the object was created for, n_worlds its world count.  These
+ *   launches run kernels of their own; grx_sim_step / grx_sim_step_dyn are unchanged.
+ * Returns -1 (grx_last_error) for NULL arguments, a handle the object was not created for, an n_worlds mismatch and everything grx_sim_step_dyn refuses. */
+#define GRX_PARAM_BAD_NONFINITE 1
+#define GRX_PARAM_BAD_FRICTIONLOSS 2
+#define GRX_PARAM_BAD_DAMPING 4
+#define GRX_PARAM_BAD_INERTIAL 8
+#define GRX_PARAM_BAD_ARMATURE 16
+#define GRX_PARAM_BAD_JNT_RANGE 32
+#define GRX_PARAM_BAD_ACT_RANGE 64
+typedef struct grx_sim_params grx_sim_params;
+int grx_sim_params_create(const grx_model* model, const grx_model* model_large, int n_worlds, const char* const* names, int n_names, grx_sim_params** out);
+int grx_sim_params_destroy(grx_sim_params* p);
+int grx_sim_params_row(const grx_sim_params* p, const char* name, float** device_ptr, int* count);
+int grx_sim_params_commit(grx_sim_params* p, const unsigned char* mask, int* invalid, void* stream);
+int grx_sim_step_params(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream);
+/* host only: the parameter names, ", "-separated in the order of their ids, into out[cap]; returns the length of the list */
+int grx_sim_params_names(char* out, int cap);
+/* host only (no device is touched): the float records that depend on table `name` for one world whose row of that table is `values` (n_values fp32 words), computed
+ * (a) rec_fill: by the record-fill functions the commit kernel calls, (b) rec_build: by the model creation's own record builder on a packed model with the same edit.  Both
+ * must be byte-identical (tests/test_cpu_sim_params.py).  Returns the number of words (0: no record depends on the table), -1 on an error; written when cap_words holds them. */
+int grx_sim_params_records(const int32_t* H, const int32_t* I, const double* F, const char* name, const float* values, int n_values, float* rec_fill, float* rec_build, int cap_words);
 /* `count` consecutive np_random.uniform(-1, 1) draws per listed world, float32 rows (states / idx as in grx_fetch_sample_resets; idx NULL = worlds 0..n-1).  HOST pointers. */
 int grx_sample_uniform_rows(uint64_t* states, const int64_t* idx, int n, int count, float* out);
 /* The same draws ON THE DEVICE: states [N,4] uint64 and out [N,count] float32 are DEVICE pointers, mask [N] uint8 or NULL selects the worlds whose streams advance

@@ -5,7 +5,8 @@ size expectations by, not a benchmark (bench.py measures the flagship workload).
     python tools/sim_probe.py --worlds 4096 --steps 200 --warmup 20 > profiles/sim_probe.txt
 
 --outputs (comma-separated names of sim.OUTPUTS, or `all`) replaces the arm scene's default pair, --jac-sites names the sites of its Jacobian outputs:
-profiles/sim_probe_dynamics.txt."""
+profiles/sim_probe_dynamics.txt.  --model-params (comma-separated names of sim.PARAMS, or `all`) gives both simulations per-world model parameters, left at
+their nominal values and committed: the launches then run the kernels that read each world's own descriptor and records (profiles/sim_probe_params.txt)."""
 import argparse
 import os
 import sys
@@ -33,10 +34,6 @@ def main():
     import numpy as np
     import torch
 
-    import gymnasium_robotics_amd as grx
-    import sim_cases as S
-    from gymnasium_robotics_amd import _native
-
     ap = argparse.ArgumentParser()
     ap.add_argument("--worlds", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=200)
@@ -44,25 +41,38 @@ def main():
     ap.add_argument("--nstep", type=int, default=5)
     ap.add_argument("--outputs", default="site_xpos,site_xvelp")
     ap.add_argument("--jac-sites", default="")
+    ap.add_argument("--model-params", default="")
     a = ap.parse_args()
-    from gymnasium_robotics_amd.sim import OUTPUTS
+    import gymnasium_robotics_amd as grx
+    import sim_cases as S
+    from gymnasium_robotics_amd import _native
+
+    from gymnasium_robotics_amd.sim import OUTPUTS, PARAMS
+
+    params = PARAMS if a.model_params == "all" else tuple(p for p in a.model_params.split(",") if p)
+    kw = dict(model_params=params) if params else {}
 
     outputs = OUTPUTS if a.outputs == "all" else tuple(o for o in a.outputs.split(",") if o)
     jac = tuple(s for s in a.jac_sites.split(",") if s) or None
-    print(f"command: python tools/sim_probe.py --worlds {a.worlds} --steps {a.steps} --warmup {a.warmup} --nstep {a.nstep} --outputs {a.outputs}" + (f" --jac-sites {a.jac_sites}" if jac else ""))
+    print(f"command: python tools/sim_probe.py --worlds {a.worlds} --steps {a.steps} --warmup {a.warmup} --nstep {a.nstep} --outputs {a.outputs}" + (f" --jac-sites {a.jac_sites}" if jac else "") +
+          (f" --model-params {a.model_params}" if params else ""))
     print(f"build id: {_native.build_id()}   device: {torch.cuda.get_device_name(0)}   SINGLE RUN")
     sc = S.SCENES["arm"]
     st = sc.states(a.worlds)
-    arm = grx.BatchedSim(sc.model, num_worlds=a.worlds, outputs=outputs, **(dict(jac_sites=jac) if jac else {}))
+    arm = grx.BatchedSim(sc.model, num_worlds=a.worlds, outputs=outputs, **(dict(jac_sites=jac) if jac else {}), **kw)
     for k in ("qpos", "qvel", "ctrl"):
         getattr(arm, k).copy_(torch.from_numpy(np.ascontiguousarray(st[k], dtype=np.float32)))
+    if params:
+        arm.commit_params()
     rate = timed(arm, a.nstep, a.steps, a.warmup)
     print(f"arm scene (nv 10, 4 plane contacts)   {a.worlds} worlds x {a.nstep} substeps: {rate:12.0f} env-steps/s   LDS/world {arm.lds_bytes} B   status {arm.status_counts()}")
     env = grx.make_vec("AntMaze_UMaze-v5", num_envs=a.worlds)
     env.reset(seed=0)
-    ant = grx.BatchedSim(env.model, num_worlds=a.worlds, outputs=("site_xpos", "site_xvelp") if env.model.dim("nsite") else ())
+    ant = grx.BatchedSim(env.model, num_worlds=a.worlds, outputs=("site_xpos", "site_xvelp") if env.model.dim("nsite") else (), **kw)
     ant.qpos.copy_(env.qpos); ant.qvel.copy_(env.qvel)
     ant.ctrl.copy_(torch.from_numpy(np.random.default_rng(0).uniform(-1, 1, (a.worlds, ant.nu)).astype(np.float32)))
+    if params:
+        ant.commit_params()
     rate = timed(ant, a.nstep, a.steps, a.warmup)
     print(f"AntMaze_UMaze model (RK4, generic kernel) {a.worlds} worlds x {a.nstep} substeps: {rate:12.0f} env-steps/s   LDS/world {ant.lds_bytes} B   status {ant.status_counts()}")
 
