@@ -430,6 +430,18 @@ def launch_step(env, bufs, fast_call, large_call, *, timed_kernel, timed_group, 
         env.step_events.append((l0, l1))
 
 
+def rerun_capacity(enabled=True, capacity=None):
+    """the table capacities create_rerun_model compiles the re-run handle with, or None when it makes none"""
+    import os
+
+    if not enabled or os.environ.get("GRX_NO_OVERFLOW_RERUN") is not None:
+        return None
+    cap = dict(capacity or RERUN_CAPACITY)
+    if os.environ.get("GRX_RERUN_CAPACITY"):      # "rows,pool,contacts" (experiments: which large tables leave no world of a workload with a truncated list)
+        cap = dict(zip(("maxefc", "jpool", "maxcon"), (int(x) for x in os.environ["GRX_RERUN_CAPACITY"].split(","))))
+    return cap
+
+
 def create_rerun_model(L, model, device_index, enabled=True, capacity=None):
     """handle of `model` compiled with RERUN_CAPACITY, or None when the lane is switched off (GRX_NO_OVERFLOW_RERUN=1: round-2 behaviour, contacts dropped and flagged)"""
     import ctypes
@@ -437,11 +449,9 @@ def create_rerun_model(L, model, device_index, enabled=True, capacity=None):
 
     from . import _native
 
-    if not enabled or os.environ.get("GRX_NO_OVERFLOW_RERUN") is not None:
+    cap = rerun_capacity(enabled, capacity)
+    if cap is None:
         return None
-    cap = dict(capacity or RERUN_CAPACITY)
-    if os.environ.get("GRX_RERUN_CAPACITY"):      # "rows,pool,contacts" (experiments: which large tables leave no world of a workload with a truncated list)
-        cap = dict(zip(("maxefc", "jpool", "maxcon"), (int(x) for x in os.environ["GRX_RERUN_CAPACITY"].split(","))))
     H, I, F = model.with_capacity(**cap).pack()
     return _native.acquire_model(H, I, F, device_index)
 

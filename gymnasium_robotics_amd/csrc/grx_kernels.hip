@@ -11,7 +11,8 @@
 // Two more units, -DGRX_TU_SIMPRM / -DGRX_TU_SIMDYNPRM, hold the task-free stepper's kernels for worlds with per-world model parameters (csrc/grx_sim_params.h) and the commit
 // kernels: they are compiled with GRX_PARAM_MODEL, under which every stage takes its model from the world's own descriptor in HBM (GRX_FRESH_MODEL, csrc/grx_engine.h), so
 // nothing else can share a unit with them and the single-unit build has stubs in their place (GRX_TU_ALL).
-#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM)
+// -DGRX_TU_SIMCON and, with GRX_PARAM_MODEL, -DGRX_TU_SIMCONPRM hold the stepper's kernels for the launches that request a contact output (GrxSimContacts, csrc/grx_sim_task.h).
+#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM)
 #define GRX_TU_ALL 1
 #define GRX_TU_FETCH 1
 #define GRX_TU_HAND 1
@@ -20,6 +21,7 @@
 #define GRX_TU_KITCHEN 1
 #define GRX_TU_SIM 1
 #define GRX_TU_SIMDYN 1
+#define GRX_TU_SIMCON 1
 #define GRX_TU_API 1
 #endif
 // The guessed support vertices of persistent hull contacts (grx_engine.h, grx_mesh_support) need a per-world HBM row, which only the Fetch buffers carry (hullcache): the
@@ -27,7 +29,7 @@
 #if GRX_TU_FETCH && !defined(GRX_NO_HULL_HINTS)
 #define GRX_HULL_HINTS 1
 #endif
-#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM
+#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM
 #define GRX_PARAM_MODEL 1
 #endif
 #include <hip/hip_runtime.h>
@@ -63,6 +65,8 @@ static_assert(sizeof(grx_kitchen_buffers) == sizeof(GrxKitchenBuffers), "grx_kit
 static_assert(sizeof(grx_sim_buffers) == sizeof(GrxSimBuffers), "grx_sim_buffers must mirror GrxSimBuffers");
 static_assert(sizeof(grx_sim_dynamics) == sizeof(GrxSimDynamics) && offsetof(grx_sim_dynamics, njac) == offsetof(GrxSimDynamics, njac) && offsetof(grx_sim_dynamics, jac_site) == offsetof(GrxSimDynamics, jac_site) && GRX_SIM_MAXJAC == sizeof(((grx_sim_dynamics*)0)->jac_site) / sizeof(int),
               "grx_sim_dynamics must mirror GrxSimDynamics");
+static_assert(sizeof(grx_sim_contacts) == sizeof(GrxSimContacts) && offsetof(grx_sim_contacts, force) == offsetof(GrxSimContacts, force) && offsetof(grx_sim_contacts, ccap) == offsetof(GrxSimContacts, ccap),
+              "grx_sim_contacts must mirror GrxSimContacts");
 
 // ------------------------------------------------------------------------------------------
 // kernels
@@ -814,8 +818,10 @@ typedef const GrxModel* GrxSimModelArg;
 #else
 typedef int GrxSimModelArg;
 #endif
-template <class S, bool DYN>
-__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_) {
+// CON: the instance that serves the third output block (GrxSimContacts) too, again in kernels of its own (grx_sim_step_con_kernel, grx_sim_lane_con_kernel; translation units
+// GRX_TU_SIMCON / GRX_TU_SIMCONPRM).  They carry both optional blocks; the eight kernels without it keep their argument lists and their code.
+template <class S, bool DYN, bool CON = false>
+__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o = nullptr) {
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
   GrxCtx c;
@@ -840,12 +846,14 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
   for (int i = lane_; i < 3 * m.nmocap; i += 64) c.mocap_pos[i] = b.mocap_pos[(size_t)w * 3 * m.nmocap + i];
   for (int i = lane_; i < 4 * m.nmocap; i += 64) c.mocap_quat[i] = b.mocap_quat[(size_t)w * 4 * m.nmocap + i];
   __syncthreads();
-  GrxSim<S>::template grx_sim_world<DYN>(&m, &c, nstep, forward_only, d, (size_t)w, lane_);
+  int crow = -1, ckey = 0;   // CON: what lane k keeps of contact k across the solve of the last pass (grx_sim_contacts_p1)
+  GrxSim<S>::template grx_sim_world<DYN, CON>(&m, &c, nstep, forward_only, d, o, crow, ckey, (size_t)w, lane_);
   __syncthreads();
   if (grx_lane_overflowed(c)) return;   // the re-run on the large tables is booked: state, outputs and status keep their values
   if (forward_only) { for (int i = lane_; i < m.nv; i += 64) b.qacc_ws[(size_t)w * m.nv + i] = c.qacc_ws[i]; }   // mj_forward leaves qpos / qvel as given (the position stage normalises quaternions in its own copy only)
   else grx_state_store(c, b.qpos, (size_t)w * m.nq, b.qvel, (size_t)w * m.nv, b.qacc_ws, (size_t)w * m.nv, m.nq, m.nv, lane_);
   GrxSim<S>::grx_sim_outputs(&m, &c, &b, (size_t)w, lane_);
+  if constexpr (CON) GrxSim<S>::grx_sim_contact_force(&m, &c, o, (size_t)w, lane_, crow, ckey);
   if constexpr (DYN) GrxSim<S>::grx_sim_dynamics_out(&m, &c, d, (size_t)w, lane_);
   if (lane_ == 0) b.status[w] = grx_status_word(b.status[w], c.cnt[2]);
   GRX_PROF_END(c, lane_);
@@ -875,8 +883,21 @@ grx_sim_lane_dyn_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, int n_worl
   extern __shared__ float lds[];
   grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
 }
+// the kernels of the launches that request a contact output: both optional blocks ride along, a block of nulls writes nothing
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_con_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, true, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o);
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_con_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o); });
+}
 #if defined(GRX_PARAM_MODEL)
-// the same four kernels for worlds with per-world model parameters: desc[w] is world w's descriptor (grx_sim_params_create)
+// the same six kernels for worlds with per-world model parameters: desc[w] is world w's descriptor (grx_sim_params_create)
 template <class S>
 __global__ void __launch_bounds__(64, 2)
 grx_sim_step_prm_kernel(const GrxModel* desc, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
@@ -900,6 +921,18 @@ __global__ void __launch_bounds__(64, 2)
 grx_sim_lane_dyn_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
   extern __shared__ float lds[];
   grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(desc, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_con_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, true, true>(desc, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o);
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_con_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(desc, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o); });
 }
 #if GRX_TU_SIMPRM
 // the commit (csrc/grx_sim_params.h): two launches behind each other on the caller's stream, one wave per world
@@ -943,12 +976,16 @@ int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* strea
 int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words, int forward_only);
 int grx_tu_sim_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
 int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
+int grx_tu_simcon_prepare(const GrxModel* g, int bytes, int slot);   // ... and with the third (GrxSimContacts)
+int grx_tu_simcon_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only);
 // the units with per-world model parameters: no descriptor slot (desc: the per-world descriptors in HBM); the first of the two also holds the commit kernels
 int grx_tu_simprm_prepare(int bytes);
 int grx_tu_simdynprm_prepare(int bytes);
 int grx_tu_simprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
 int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
 int grx_tu_simprm_commit(const GrxParamCommit* a, void* stream);
+int grx_tu_simconprm_prepare(int bytes);
+int grx_tu_simconprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only);
 }
 // Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
 // overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
@@ -1145,6 +1182,18 @@ extern "C" int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* strea
   return (int)hipGetLastError();
 }
 #endif
+#if GRX_TU_SIMCON
+// ... and those that request a contact output
+extern "C" int grx_tu_simcon_prepare(const GrxModel* g, int bytes, int slot) {
+  GRX_LDS(grx_sim_step_con_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_con_kernel<GrxShapeAny>);
+  return (int)grx_upload_descriptor(g, slot);
+}
+extern "C" int grx_tu_simcon_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_con_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_con_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
 #if GRX_TU_SIMPRM
 extern "C" int grx_tu_simprm_prepare(int bytes) {
   GRX_LDS(grx_sim_step_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_prm_kernel<GrxShapeAny>);
@@ -1172,6 +1221,17 @@ extern "C" int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* st
   return (int)hipGetLastError();
 }
 #endif
+#if GRX_TU_SIMCONPRM
+extern "C" int grx_tu_simconprm_prepare(int bytes) {
+  GRX_LDS(grx_sim_step_con_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_con_prm_kernel<GrxShapeAny>);
+  return 0;
+}
+extern "C" int grx_tu_simconprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_con_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_con_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
 #if defined(GRX_TU_ALL)
 // the single-unit build cannot hold the GRX_PARAM_MODEL kernels: a parameter object cannot be created there (grx_sim_params_create fails on the first of these)
 extern "C" int grx_tu_simprm_prepare(int) { return (int)hipErrorNotSupported; }
@@ -1179,6 +1239,8 @@ extern "C" int grx_tu_simdynprm_prepare(int) { return (int)hipErrorNotSupported;
 extern "C" int grx_tu_simprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, int, int, int, int) { return (int)hipErrorNotSupported; }
 extern "C" int grx_tu_simdynprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, int, int, int, int) { return (int)hipErrorNotSupported; }
 extern "C" int grx_tu_simprm_commit(const GrxParamCommit*, void*) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simconprm_prepare(int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simconprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, int, int, int, int) { return (int)hipErrorNotSupported; }
 #endif
 #undef GRX_LDS
 
@@ -1379,6 +1441,7 @@ static int grx_model_create_impl(const int32_t* H, const int32_t* I, const doubl
   if ((e = grx_tu_kitchen_prepare(&g, bytes, m->slot, &m->shape)) != 0) return fail(std::string("grx_model_create (kitchen kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_sim_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_simdyn_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the dynamics block): ") + hipGetErrorString((hipError_t)e));
+  if ((e = grx_tu_simcon_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the contact block): ") + hipGetErrorString((hipError_t)e));
   HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), &m->dev, sizeof(GrxModel), sizeof(GrxModel) * (size_t)m->slot, hipMemcpyHostToDevice));
   return 0;
 }
@@ -1532,7 +1595,8 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
 // The argument checks that do not need the model come first and read nothing of it (tests/test_cpu_sim.py reaches them without a device).
 // grx_sim_step is this call without the second block; the messages keep its name.
 // desc: null, or the per-world descriptors of a parameter object made for m (grx_sim_step_params): the launch then goes to the kernels of the parameter units
-static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc) {
+// con: null, or the third block (grx_sim_step_con): its own checks follow those of the first two; a launch that requests one of its outputs runs the kernels of the contact units
+static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc, const grx_sim_contacts* con = nullptr, bool need_con = false) {
   if (!m) return fail("grx_sim_step: null model");
   if (!buf) return fail("grx_sim_step: null buffers");
   if (!buf->qpos || !buf->qvel || !buf->qacc_ws) return fail("grx_sim_step: null state buffer (qpos, qvel, qacc_ws)");
@@ -1546,6 +1610,11 @@ static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, con
     if (d.njac > 0 && !d.site_jacp && !d.site_jacr) return fail("grx_sim_step_dyn: njac > 0 with site_jacp and site_jacr both null");
     if (d.njac == 0 && (d.site_jacp || d.site_jacr)) return fail("grx_sim_step_dyn: a Jacobian buffer with njac == 0 (no site selected)");
   }
+  if (need_con && !con) return fail("grx_sim_step_con: null contact block (grx_sim_step_dyn is the call without one)");
+  GrxSimContacts o; memset(&o, 0, sizeof(o));
+  if (con) memcpy(&o, con, sizeof(o));
+  const bool contacts = o.geom || o.dim || o.efc_address || o.dist || o.pos || o.frame || o.force;
+  if (contacts && o.ccap < 1) return fail("grx_sim_step_con: ccap < 1 with a contact buffer set (ccap is the number of slots per world)");
   const GrxModel& g = m->dev;
   for (int k = 0; k < d.njac; k++)
     if (d.jac_site[k] < 0 || d.jac_site[k] >= g.nsite) return fail("grx_sim_step_dyn: jac_site[" + std::to_string(k) + "] = " + std::to_string(d.jac_site[k]) + " is outside [0, nsite)");
@@ -1559,7 +1628,9 @@ static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, con
   const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
   const unsigned grid = grx_step_grid(b.lane, 0, 0, n_worlds); const size_t lds_bytes = (size_t)m->words * 4 + m->lds_pad;
   int e;
-  if (desc) e = dynamic ? grx_tu_simdynprm_launch(grid, lds_bytes, stream, desc, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+  if (contacts) e = desc ? grx_tu_simconprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+                         : grx_tu_simcon_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  else if (desc) e = dynamic ? grx_tu_simdynprm_launch(grid, lds_bytes, stream, desc, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
                         : grx_tu_simprm_launch(grid, lds_bytes, stream, desc, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
   else e = dynamic ? grx_tu_simdyn_launch(grid, lds_bytes, stream, m->slot, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
                    : grx_tu_sim_launch(grid, lds_bytes, stream, m->slot, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
@@ -1572,6 +1643,28 @@ extern "C" int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, 
 #include "grx_sim_params_api.h"
 extern "C" int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream) {
   return grx_sim_step_dyn(m, buf, nullptr, n_worlds, nstep, forward_only, stream);
+}
+// The stepper with the third block: p null = the model's own parameters (grx_sim_step_dyn), else the checks and the kernels of grx_sim_step_params.  A block of nulls
+// forwards to those entry points' launches.
+extern "C" int grx_sim_step_con(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, int n_worlds, int nstep, int forward_only, void* stream) {
+  const GrxModel* desc = nullptr;
+  if (p) {
+    if (!m) return fail("grx_sim_step_params: null model");
+    if (m != p->model && m != p->large) return fail("grx_sim_step_params: the parameter object was not created for this model handle");
+    if (n_worlds != p->n) return fail("grx_sim_step_params: n_worlds = " + std::to_string(n_worlds) + ", the parameter object holds " + std::to_string(p->n) + " worlds");
+    desc = m == p->model ? p->d_desc : p->d_desc_large;
+  }
+  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, true);
+}
+// sizeof(grx_sim_contacts) and the byte offset of every member, in declaration order: what _native.SimContactsStruct must mirror (host only)
+extern "C" int grx_sim_contacts_layout(long long* out, int cap) {
+  const grx_sim_contacts* z = nullptr;
+#define OFF(f) (long long)((const char*)&z->f - (const char*)z)
+  const long long v[] = {(long long)sizeof(grx_sim_contacts), OFF(geom), OFF(dim), OFF(efc_address), OFF(dist), OFF(pos), OFF(frame), OFF(force), OFF(ccap)};
+#undef OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  if (out) for (int i = 0; i < n && i < cap; i++) out[i] = v[i];
+  return n;
 }
 // sizeof(grx_sim_dynamics) and the byte offset of every member, in declaration order: what _native.SimDynamicsStruct must mirror (host only)
 extern "C" int grx_sim_dynamics_layout(long long* out, int cap) {

@@ -34,13 +34,92 @@ struct GrxSimDynamics {
   int njac, jac_site[GRX_SIM_MAXJAC];                              // the selection rides in the block: no device list, no dependent load
 };
 
+// The third, optional output block (include/grx_capi.h grx_sim_contacts): MjData's contact list of the LAST forward pass and mj_contactForce of every entry.  Passed by value
+// beside the other two; every pointer may be null.  ccap slots per world, in the ENGINE's list order (sorted by candidate pair, not MuJoCo's order): a world writes its first
+// min(ncon, table maxcon, ccap) slots and fills the rest (geom -1, dim 0, efc_address -1, floats 0.0f), so every element of a requested buffer is owed by the launch.
+struct GrxSimContacts {
+  int *geom, *dim, *efc_address;          // [N,ccap,2] [N,ccap] [N,ccap]: pair_geom1 / pair_geom2 of the contact's pair, its condim, its first constraint row (-1: none)
+  float *dist, *pos, *frame, *force;      // [N,ccap] [N,ccap,3] [N,ccap,9] [N,ccap,6]: frame = normal and the two tangents of grx_make_frame, force in that frame
+  int ccap;
+};
+
 template <class S>
 struct GrxSim {
   typedef GrxEngine<S> E;
+  // The contact list leaves in two parts, because the solve stage reuses the P1 overlay the list lives in (grx_ctx_carve) and efc_force exists only after the solve.
+  // Part 1, between grx_make_constraint and the solve of the last pass: geom, dim, efc_address, dist, pos and frame.  A world's rows of a member are contiguous; element e goes
+  // to lane e mod 64 (grx_sim_dynamics_out does the same for the Jacobians).  Lane k keeps what part 2 needs of contact k in two registers across the solve: crow = the first
+  // row or -1, ckey = pair << 4 | rows (GRX_MAXCON = 64: one lane per contact).  A contact whose rows do not all lie inside nefc has none: address -1, zero force.
+  GRX_MEM void grx_sim_contacts_p1(const GrxModel* m, const GrxCtx* c, const GrxSimContacts* o, size_t w, int lane_, int& crow, int& ckey) {
+    GRX_FRESH_MODEL(m, c);
+    const int ncon = c->cnt[0] < c->maxcon ? c->cnt[0] : c->maxcon, nefc = c->cnt[1], cap = o->ccap, nw = ncon < cap ? ncon : cap;
+    FOR_LANES {
+      crow = -1; ckey = 0;
+      if (lane < ncon) {
+        const int r0 = c->con_efc[lane], nr = c->con_nr[lane];
+        const int has = r0 >= 0 && nr > 0 && r0 + nr <= nefc;
+        crow = has ? r0 : -1; ckey = (c->con_pair[lane] << 4) | (has ? nr : 0);
+      }
+      if (o->efc_address)
+        for (int e = lane; e < cap; e += 64) {
+          int a = -1;
+          if (e < nw) { const int r0 = c->con_efc[e], nr = c->con_nr[e]; a = (r0 >= 0 && nr > 0 && r0 + nr <= nefc) ? r0 : -1; }
+          o->efc_address[w * cap + e] = a;
+        }
+      if (o->dim) for (int e = lane; e < cap; e += 64) o->dim[w * cap + e] = e < nw ? m->reci_pair[GRX_RPI * c->con_pair[e]] : 0;
+      if (o->geom)
+        for (int e = lane; e < 2 * cap; e += 64) {
+          const int k = e >> 1;
+          int g = -1;
+          if (k < nw) { const int p = c->con_pair[k]; g = (e & 1) ? m->pair_geom2[p] : m->pair_geom1[p]; }
+          o->geom[w * 2 * cap + e] = g;
+        }
+      if (o->dist) for (int e = lane; e < cap; e += 64) o->dist[w * cap + e] = e < nw ? c->con_dist[e] : 0.0f;
+      if (o->pos) for (int e = lane; e < 3 * cap; e += 64) o->pos[w * 3 * cap + e] = e < 3 * nw ? c->con_pos[e] : 0.0f;
+      if (o->frame)
+        for (int e = lane; e < 9 * cap; e += 64) {
+          const int k = e / 9, j = e - 9 * k;
+          float v = 0.0f;
+          if (k < nw) {   // the frame the contact's rows were built in: the same routine on the same normal (grx_make_constraint)
+            float fr[9] = {c->con_frame[3 * k], c->con_frame[3 * k + 1], c->con_frame[3 * k + 2], 0, 0, 0, 0, 0, 0};
+            E::grx_make_frame(fr);
+            v = fr[0];
+#pragma unroll
+            for (int q = 1; q < 9; q++) v = (j == q) ? fr[q] : v;   // a select chain: a lane-indexed read would move the frame to scratch
+          }
+          o->frame[w * 9 * cap + e] = v;
+        }
+    }
+  }
+  // Part 2, after the pass: mj_contactForce for the pyramidal cone from the contact's rows of efc_force (P2 overlay, untouched since the solve), in flat order as above.  Lane
+  // e mod 64 fetches the rows and the pair of contact e / 6 from the lane that kept them (every lane of the wave takes part in the exchange: the trip count is wave-uniform).
+  // mu is the pair's friction row of THIS world's model (GRX_FRESH_MODEL: the world's own descriptor in the parameter units).
+  GRX_MEM void grx_sim_contact_force(const GrxModel* m, GrxCtx* c, const GrxSimContacts* o, size_t w, int lane_, int crow, int ckey) {
+    if (!o->force) return;
+    GRX_FRESH_MODEL(m, c);
+    const int ncon = c->cnt[0] < c->maxcon ? c->cnt[0] : c->maxcon, cap = o->ccap, nw = ncon < cap ? ncon : cap, total = 6 * cap, nefc = c->cnt[1];
+    // grx_solve_integrate skips the evaluation at the converged acceleration where nothing reads the row forces afterwards (no touch sensor, no noslip pass): efc_force is
+    // then one Newton step old.  Here something does read them: evaluate once more, from c->qacc and the persistent row tables (Ma, efc_jar and efc_quad, which the
+    // evaluation also writes, are dead once the pass is over).  Where the engine did evaluate -- or noslip has re-solved the friction forces -- efc_force is left as it is.
+    if (nefc > 0 && (S::kFixed ? S::NT : m->ntouch) == 0 && !(S::kNoslip && m->noslip_iterations > 0)) E::grx_newton_eval(m, c, c->qacc, nefc, 0, lane_);
+    for (int base = 0; base < total; base += 64) {
+      const int e = base + lane_, k = e / 6, j = e - 6 * k;
+      const int r0 = __shfl(crow, k & 63), key = __shfl(ckey, k & 63);
+      const int nr = key & 15, p = key >> 4, dim = (nr == 1) ? 1 : (nr >> 1) + 1;
+      float v = 0.0f;
+      if (e < total && k < nw && r0 >= 0) {
+        if (j == 0) { for (int q = 0; q < nr; q++) v += c->efc_force[r0 + q]; }
+        else if (j < dim) v = m->recf_pair[GRX_RPF * p + 3 + (j - 1)] * (c->efc_force[r0 + 2 * (j - 1)] - c->efc_force[r0 + 2 * (j - 1) + 1]);
+      }
+      if (e < total) o->force[w * total + e] = v;
+    }
+  }
   // grx_forward_euler's stage sequence with one addition: qfrc_bias / qfrc_passive / qfrc_actuator live in the P1 overlay, which the solve stage reuses (grx_ctx_carve), so
   // they leave for HBM between the velocity and the solve stage.  Only the LAST pass of a launch that asks for one of the three comes here; every other pass is
   // grx_forward_euler itself.  A world that claims a re-run on the large tables after this pass has written its three rows already: the re-run overwrites them.
-  GRX_MEM void grx_sim_forward_p1(const GrxModel* m, GrxCtx* c, int do_euler, const GrxSimDynamics* d, size_t w, int lane_) {
+  // CON: the instance of the launches that request a contact output (o, crow, ckey: grx_sim_contacts_p1); they come here in their last pass whatever d holds.
+  template <bool CON>
+  GRX_MEM void grx_sim_forward_p1(const GrxModel* m, GrxCtx* c, int do_euler, const GrxSimDynamics* d, const GrxSimContacts* o, int& crow, int& ckey, size_t w, int lane_) {
     GRX_TICK(c, GRX_P_OTHER);
     E::grx_kinematics(m, c, lane_);
     GRX_TICK(c, GRX_P_KIN);
@@ -52,6 +131,7 @@ struct GrxSim {
     E::grx_make_constraint(m, c, lane_);
     if (grx_handoff_due(c)) return;
     GRX_TICK(c, GRX_P_CONSTR);
+    if constexpr (CON) grx_sim_contacts_p1(m, c, o, w, lane_, crow, ckey);
     E::grx_velocity(m, c, lane_);
     {
       GRX_FRESH_MODEL(m, c);
@@ -69,11 +149,12 @@ struct GrxSim {
   // nstep x mj_step with ctrl held (GrxPoint::grx_point_sim_world with agent = 1 and no task: Euler models one pass per substep, RK4 models four), or one mj_forward.
   // A launch with an entry list (c->bail) stops at the first pass that exceeds a table: the world's re-run on the large tables is booked and nothing of this run is kept.
   // DYN = false: the instance of the launches that request nothing of GrxSimDynamics; d is null and not read.
-  template <bool DYN>
-  GRX_MEM void grx_sim_world(const GrxModel* m, GrxCtx* c, int nstep, int forward_only, const GrxSimDynamics* d, size_t w, int lane_) {
-    const int p1 = DYN && ((d->qfrc_bias != nullptr) | (d->qfrc_passive != nullptr) | (d->qfrc_actuator != nullptr));   // wave-uniform: kernel arguments
+  // CON = true (with DYN = true: those kernels carry both optional blocks): the instance of the launches that request a contact output.
+  template <bool DYN, bool CON>
+  GRX_MEM void grx_sim_world(const GrxModel* m, GrxCtx* c, int nstep, int forward_only, const GrxSimDynamics* d, const GrxSimContacts* o, int& crow, int& ckey, size_t w, int lane_) {
+    const int p1 = CON || (DYN && ((d->qfrc_bias != nullptr) | (d->qfrc_passive != nullptr) | (d->qfrc_actuator != nullptr)));   // wave-uniform: kernel arguments
     if (forward_only) {
-      if (p1) grx_sim_forward_p1(m, c, 0, d, w, lane_);
+      if (p1) grx_sim_forward_p1<CON>(m, c, 0, d, o, crow, ckey, w, lane_);
       else E::grx_forward_euler(m, c, 0, lane_);
       if (c->bail) grx_lane_claim(c, lane_);
       return;
@@ -83,7 +164,7 @@ struct GrxSim {
     for (int it = 0; it < total; it++) {
       const int stage = it & 3;
       if (!rk4 || stage == 0) E::grx_check_state(m, c, lane_);
-      if (p1 && it == total - 1) grx_sim_forward_p1(m, c, !rk4, d, w, lane_);
+      if (p1 && it == total - 1) grx_sim_forward_p1<CON>(m, c, !rk4, d, o, crow, ckey, w, lane_);
       else E::grx_forward_euler(m, c, !rk4, lane_);
       if (c->bail && grx_lane_claim(c, lane_)) break;
       if (rk4) E::grx_rk4_after_forward(m, c, stage, lane_);

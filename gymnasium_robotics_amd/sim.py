@@ -22,6 +22,18 @@ The dynamics of the same pass are outputs too: ``qM`` (dense ``mj_fullM``), ``qf
     sim = grx.BatchedSim("my_robot.xml", 4096, outputs=("qfrc_bias", "site_jacp"), jac_sites=("tip",))
     J = sim.site_jacp[:, sim.jac_row("tip")]                       # [N, 3, nv]
 
+The CONTACT LIST of the same pass: ``contacts`` names any of ``sim.CONTACTS`` -- ``contact_geom`` [N, C, 2] (``contact.geom1`` / ``geom2``, geom ids of the compiled model:
+``sim.geom_id(name)``), ``contact_dim`` [N, C], ``contact_efc_address`` [N, C] (-1: no constraint rows), ``contact_dist`` [N, C], ``contact_pos`` [N, C, 3], ``contact_frame``
+[N, C, 9] (the normal, then the two tangents) and ``contact_force`` [N, C, 6] (``mj_contactForce``: normal, two tangential, torsional, two rolling, in the contact frame).
+C = ``sim.contact_capacity``.  World w holds ``ncon[w]`` contacts in its first slots, in the ENGINE's order (sorted by candidate pair; not MuJoCo's order: match by geom pair and
+position); the remaining slots are filled (geom -1, dim 0, efc_address -1, floats 0).  Requesting one routes the launch through grx_sim_step_con.
+
+    sim = grx.BatchedSim("my_robot.xml", 4096, outputs=("ncon",), contacts=("contact_geom", "contact_frame", "contact_force"))
+    sim.step(nstep=20)
+    down = (sim.contact_geom == sim.geom_id("foot")).any(-1)                                   # [N, C]: the slots that involve the foot
+    frame = sim.contact_frame.view(4096, -1, 3, 3)                                             # rows: normal, tangent 1, tangent 2, in world coordinates
+    f_world = (frame.transpose(-1, -2) @ sim.contact_force[..., :3, None]).squeeze(-1)         # [N, C, 3]: frame' force[:3], the force on the pair's second geom
+
 ``xpos`` / ``xquat`` index the COMPILED model's bodies: the compiler merges static children into their parents, ``sim.model.names["body"]`` maps the surviving names to rows.
 Sites keep their identity whatever body they end up on: they are the stable handle for "where is this point of my robot".
 
@@ -40,7 +52,8 @@ which rule; a commit never raises and never synchronises.  Friction is a propert
     sim.commit_params()
     assert not sim.params_invalid.any()
 
-Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses.
+Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
+cfrc_ext, MuJoCo's contact order, elliptic cones.
 """
 import ctypes
 
@@ -55,7 +68,15 @@ OUTPUTS = ("xpos", "xquat", "site_xpos", "site_xmat", "site_xvelp", "site_xvelr"
 PARAMS = ("gravity", "body_mass", "body_inertia", "dof_damping", "dof_armature", "dof_frictionloss", "jnt_stiffness", "jnt_springref", "jnt_range", "act_gear", "act_gainprm",
           "act_biasprm", "act_ctrlrange", "act_forcerange", "pair_friction", "pair_solref", "pair_solimp")      # include/grx_capi.h grx_sim_params_create
 PARAM_BAD = dict(nonfinite=1, frictionloss=2, damping=4, inertial=8, armature=16, jnt_range=32, act_range=64)      # GRX_PARAM_BAD_*: the bits of params_invalid
+CONTACTS = ("contact_geom", "contact_dim", "contact_efc_address", "contact_dist", "contact_pos", "contact_frame", "contact_force")      # grx_sim_contacts, in its order
+_CONTACT_WIDTH = dict(contact_geom=(2,), contact_dim=(), contact_efc_address=(), contact_dist=(), contact_pos=(3,), contact_frame=(9,), contact_force=(6,))
+_INT_TENSORS = ("ncon", "nefc", "contact_geom", "contact_dim", "contact_efc_address")
 MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
+
+
+def _table_maxcon(req):
+    """the contact-list capacity of a handle whose model requests `req` (csrc/grx_host_model.h: the request if it lies in 1 .. 64, else the default 32)"""
+    return req if 0 < req <= 64 else 32
 
 
 class _Params:
@@ -66,13 +87,14 @@ class _Params:
 
 
 class BatchedSim:
-    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=()):
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=()):
         """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
         default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
         again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
         CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
         keep_sites, mutate, ...).  jac_sites: the names of the sites whose Jacobians site_jacp / site_jacr hold, in the order of their rows (None: every site of the model, which must
-        then have at most 16).  model_params: the tables that are per world, any of sim.PARAMS (module docstring).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        then have at most 16).  model_params: the tables that are per world, any of sim.PARAMS (module docstring).  contacts: the members of the contact list to allocate and write, any of sim.CONTACTS
+        (module docstring).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
         if int(num_worlds) < 1:
             raise ValueError("num_worlds must be at least 1")
         if overflow not in ("rerun", "flag"):
@@ -93,6 +115,15 @@ class BatchedSim:
         if len(set(model_params)) != len(model_params):
             raise ValueError(f"model_params names a parameter twice: {model_params}; the per-world parameters are {PARAMS}")
         self.param_names = tuple(p for p in PARAMS if p in model_params)
+        if isinstance(contacts, str):
+            contacts = (contacts,)
+        contacts = tuple(contacts)
+        unknown = [c for c in contacts if c not in CONTACTS]
+        if unknown:
+            raise ValueError(f"unknown contact output(s) {unknown}; the contact outputs are {CONTACTS}")
+        if len(set(contacts)) != len(contacts):
+            raise ValueError(f"contacts names an output twice: {contacts}; the contact outputs are {CONTACTS}")
+        self.contacts = tuple(c for c in CONTACTS if c in contacts)
         kw = dict(compile_kwargs or {})
         if kw.get("origin") is not None or kw.get("shift_body") is not None:
             raise ValueError("BatchedSim returns raw engine coordinates: compile the model in the MJCF's own frame (no origin) and without a shift group")
@@ -148,6 +179,19 @@ class BatchedSim:
     def site_id(self, name):
         return self._lookup("site", name)
 
+    def geom_id(self, name):
+        """id of the geom `name` as contact_geom holds it: a geom of the COMPILED model (the tables pair_geom1 / pair_geom2 index)"""
+        return self._lookup("geom", name)
+
+    @property
+    def contact_capacity(self):
+        """slots per world of the contact outputs: the contact-list capacity (maxcon) of the tables the step launch runs on, or -- when overflow="rerun" runs a world that
+        exceeds them again on the large tables -- of those, so that a re-run world keeps all its contacts"""
+        from .core import rerun_capacity
+
+        big = rerun_capacity() if self.overflow == "rerun" else None
+        return _table_maxcon(int(big["maxcon"]) if big else self.model.dim("maxcon_req"))
+
     def jac_row(self, name):
         """row of the site `name` in site_jacp / site_jacr (its position in jac_sites)"""
         self.site_id(name)
@@ -193,7 +237,8 @@ class BatchedSim:
         return dict(qpos=(n, self.nq), qvel=(n, self.nv), qacc_warmstart=(n, self.nv), ctrl=(n, self.nu), mocap_pos=(n, self.nmocap, 3), mocap_quat=(n, self.nmocap, 4),
                     xpos=(n, self.nbody, 3), xquat=(n, self.nbody, 4), site_xpos=(n, self.nsite, 3), site_xmat=(n, self.nsite, 9), site_xvelp=(n, self.nsite, 3),
                     site_xvelr=(n, self.nsite, 3), sensordata=(n, self.ntouch), ncon=(n,), nefc=(n,), qM=(n, self.nv, self.nv), site_jacp=(n, len(self._jac_ids), 3, self.nv),
-                    site_jacr=(n, len(self._jac_ids), 3, self.nv), **{k: (n, self.nv) for k in DYNAMICS if k not in ("qM",) + JACOBIANS})
+                    site_jacr=(n, len(self._jac_ids), 3, self.nv), **{k: (n, self.nv) for k in DYNAMICS if k not in ("qM",) + JACOBIANS},
+                    **{k: (n, self.contact_capacity) + _CONTACT_WIDTH[k] for k in CONTACTS})
 
     def _ensure(self):
         if self._t is not None:
@@ -213,8 +258,8 @@ class BatchedSim:
         self.lds_bytes = self._L.grx_model_lds_bytes(self._h)
         shapes = self._shapes()
         t = {}
-        for k in STATE + self.outputs:
-            t[k] = torch.zeros(shapes[k], dtype=torch.int32 if k in ("ncon", "nefc") else torch.float32, device=self.device)
+        for k in STATE + self.outputs + self.contacts:
+            t[k] = torch.zeros(shapes[k], dtype=torch.int32 if k in _INT_TENSORS else torch.float32, device=self.device)
         t["status_words"] = torch.zeros(self.num_worlds, dtype=torch.int32, device=self.device)
         tb = self.model.tables
         self._qpos0 = torch.from_numpy(np.asarray(tb["qpos0"], dtype=np.float32).reshape(-1)).to(self.device)
@@ -228,6 +273,9 @@ class BatchedSim:
             if any(k in JACOBIANS for k in self.dynamics):
                 self._dyn.njac = len(self._jac_ids)
                 self._dyn.jac_site[:len(self._jac_ids)] = self._jac_ids
+        self._con = None
+        if self.contacts:      # again one block for both launches: ccap is the capacity of the larger handle
+            self._con = _native.SimContactsStruct(ccap=self.contact_capacity, **{k[len("contact_"):]: t[k].data_ptr() for k in self.contacts})
         if self.overflow == "rerun":
             self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
             if self._h_big is not None:
@@ -257,7 +305,7 @@ class BatchedSim:
         if name in ("device", "lds_bytes"):      # known once the device side exists
             self._ensure()
             return self.__dict__[name]
-        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()):
+        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()) or name in self.__dict__.get("contacts", ()):
             return self._ensure()[name]
         if name in ("params", "params_invalid"):
             if not self.__dict__.get("param_names"):
@@ -266,6 +314,8 @@ class BatchedSim:
             return t["params_invalid"] if name == "params_invalid" else self._params
         if name in OUTPUTS:
             raise AttributeError(f"output {name!r} was not requested: BatchedSim(..., outputs={self.__dict__.get('outputs', ())})")
+        if name in CONTACTS:
+            raise AttributeError(f"contact output {name!r} was not requested: BatchedSim(..., contacts={self.__dict__.get('contacts', ())})")
         raise AttributeError(name)
 
     def _make_bufs(self, mask):
@@ -302,7 +352,11 @@ class BatchedSim:
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            if self._p is not None:      # the kernels that take each world's model from its own descriptor
+            if self._con is not None:      # the kernels that write the contact list; they serve the other two blocks and the per-world parameters as well
+                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
+                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_con(h, self._p, ctypes.byref(b), dyn, ctypes.byref(self._con), self.num_worlds, int(nstep),
+                                                                                  int(forward_only), stream_ptr(self.device))))
+            elif self._p is not None:      # the kernels that take each world's model from its own descriptor
                 dyn = None if self._dyn is None else ctypes.byref(self._dyn)
                 go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_params(h, self._p, ctypes.byref(b), dyn, self.num_worlds, int(nstep), int(forward_only),
                                                                                      stream_ptr(self.device))))

@@ -414,6 +414,31 @@ typedef struct grx_sim_dynamics {
 int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_dynamics), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (13) */
 int grx_sim_dynamics_layout(long long* out, int cap);
+/* The CONTACT LIST of the same pass, a third and optional output block: data.contact[i] and mj_contactForce(model, data, i) for every entry -- which foot is down and with
+ * how much force, a grasp check, a slip or impact penalty.  Every pointer may be NULL (not written); mirrors struct GrxSimContacts (csrc/grx_sim_task.h).  ccap is the number
+ * of slots per world of every buffer.  Same moment as the other outputs (the LAST forward pass of the launch).
+ *   geom          contact.geom1, geom2: geom ids of the COMPILED model (the pair's pair_geom1 / pair_geom2)                     [N,ccap,2] int32
+ *   dim           contact.dim (1, 3, 4, 6)                                                                                      [N,ccap]   int32
+ *   efc_address   first constraint row of the contact, -1 if it has none (outside margin - gap, or cut by a row-table overflow)  [N,ccap]   int32
+ *   dist, pos     contact.dist, contact.pos                                                                                     [N,ccap] [N,ccap,3]
+ *   frame         contact.frame: the normal, then the two tangents the constraint rows were built in                            [N,ccap,9]
+ *   force         mj_contactForce in the contact frame (pyramidal cone): normal, two tangential, torsional, two rolling;
+ *                 components at index dim and above are 0.0f, a contact without rows has zero force                            [N,ccap,6]
+ * ORDER: the slots follow the ENGINE's list (sorted by candidate pair), which is not MuJoCo's order: match by geom pair and position.  A world writes its first
+ * min(ncon, the handle's maxcon, ccap) slots and FILLS every remaining slot up to ccap (geom -1, dim 0, efc_address -1, floats 0.0f): the buffers need no initialisation.
+ * Masked-out worlds keep their rows; the re-run call of the overflow lane takes the same block (ccap may exceed the handle's maxcon: the fast handle of a re-run pair).
+ * grx_sim_step_con: params NULL = grx_sim_step_dyn (dyn may be NULL) with the block, else grx_sim_step_params with it.  A block of NULL pointers launches what those calls
+ * launch; one with a pointer set runs kernels of its own.  Returns -1 (grx_last_error) for everything those calls refuse, for con == NULL and for ccap < 1 with a pointer set. */
+typedef struct grx_sim_contacts {
+  int *geom, *dim, *efc_address;
+  float *dist, *pos, *frame, *force;
+  int ccap;                                /* slots per world */
+} grx_sim_contacts;
+struct grx_sim_params;
+int grx_sim_step_con(const grx_model* m, const struct grx_sim_params* params, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, int n_worlds, int nstep,
+                     int forward_only, void* stream);
+/* host only: out[0] = sizeof(grx_sim_contacts), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (9) */
+int grx_sim_contacts_layout(long long* out, int cap);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)

@@ -6,7 +6,9 @@ size expectations by, not a benchmark (bench.py measures the flagship workload).
 
 --outputs (comma-separated names of sim.OUTPUTS, or `all`) replaces the arm scene's default pair, --jac-sites names the sites of its Jacobian outputs:
 profiles/sim_probe_dynamics.txt.  --model-params (comma-separated names of sim.PARAMS, or `all`) gives both simulations per-world model parameters, left at
-their nominal values and committed: the launches then run the kernels that read each world's own descriptor and records (profiles/sim_probe_params.txt)."""
+their nominal values and committed: the launches then run the kernels that read each world's own descriptor and records (profiles/sim_probe_params.txt).
+--contacts (comma-separated names of sim.CONTACTS, or `all`) makes both simulations write the contact list: the launches then run the kernels of the contact units
+(profiles/sim_probe_contacts.txt)."""
 import argparse
 import os
 import sys
@@ -42,20 +44,24 @@ def main():
     ap.add_argument("--outputs", default="site_xpos,site_xvelp")
     ap.add_argument("--jac-sites", default="")
     ap.add_argument("--model-params", default="")
+    ap.add_argument("--contacts", default="")
     a = ap.parse_args()
     import gymnasium_robotics_amd as grx
     import sim_cases as S
     from gymnasium_robotics_amd import _native
 
-    from gymnasium_robotics_amd.sim import OUTPUTS, PARAMS
+    from gymnasium_robotics_amd.sim import CONTACTS, OUTPUTS, PARAMS
 
     params = PARAMS if a.model_params == "all" else tuple(p for p in a.model_params.split(",") if p)
     kw = dict(model_params=params) if params else {}
+    contacts = CONTACTS if a.contacts == "all" else tuple(c for c in a.contacts.split(",") if c)
+    if contacts:
+        kw["contacts"] = contacts
 
     outputs = OUTPUTS if a.outputs == "all" else tuple(o for o in a.outputs.split(",") if o)
     jac = tuple(s for s in a.jac_sites.split(",") if s) or None
     print(f"command: python tools/sim_probe.py --worlds {a.worlds} --steps {a.steps} --warmup {a.warmup} --nstep {a.nstep} --outputs {a.outputs}" + (f" --jac-sites {a.jac_sites}" if jac else "") +
-          (f" --model-params {a.model_params}" if params else ""))
+          (f" --model-params {a.model_params}" if params else "") + (f" --contacts {a.contacts}" if contacts else ""))
     print(f"build id: {_native.build_id()}   device: {torch.cuda.get_device_name(0)}   SINGLE RUN")
     sc = S.SCENES["arm"]
     st = sc.states(a.worlds)
