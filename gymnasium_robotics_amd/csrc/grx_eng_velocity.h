@@ -23,10 +23,78 @@ GRX_MEM float grx_actuator_force(const GrxModel* m, const GrxCtx* c, int i, int*
   return gear * f;
 }
 
+#if defined(GRX_APPLIED_FORCES)
+// Applied forces (mj_xfrcAccumulate and qfrc_applied), only in the units compiled with GRX_APPLIED_FORCES; called at the end of grx_velocity, so in every forward pass:
+//   Q = qfrc_applied + sum over bodies b >= 1 of jacp_b' f_b + jacr_b' t_b,   qfrc_smooth += Q
+// with (f_b, t_b) = xfrc_applied[b] in world coordinates and the Jacobians of xipos[b] = xpos[b] + xmat[b] body_ipos[b].  The bias force's scheme with another per-body vector:
+// the spatial force of body b about its tree's reference point, (t_b + (xipos_b - cref) x f_b, f_b), takes cacc's place (dead once qfrc_bias is formed), the subtree sums
+// take cfrc's, and dof d's lane dots its motion axis with the sum of its body.  One writer per element, no atomics.  The two rows are read from HBM in each pass (one lane per
+// body and per dof, L2-resident after the first pass): no LDS is added.  grx_applied_load issues those loads at the TOP of the velocity stage, into seven registers per lane
+// (a model has at most 64 bodies -- body_submask -- and 64 dofs: lane l holds body 1 + l and dof l), so their latency passes behind the stage's own work instead of standing
+// between it and the solve.  Row 0 (the world body) is not read.  Either pointer may be null.
+struct GrxAppliedRows { float x[6], q; };
+GRX_MEM void grx_applied_load(const GrxModel* m, const GrxCtx* c, int lane_, GrxAppliedRows& r) {
+  for (int k = 0; k < 6; k++) r.x[k] = 0.0f;
+  r.q = 0.0f;
+  const int b = 1 + lane_;
+  if (c->xfrc_applied && b < GRX_NBC) { const float* x = c->xfrc_applied + 6 * b; for (int k = 0; k < 6; k++) r.x[k] = x[k]; }
+  if (c->qfrc_applied && lane_ < GRX_NVC) r.q = c->qfrc_applied[lane_];
+}
+GRX_MEM void grx_applied_forces(const GrxModel* m, GrxCtx* c, int lane_, const GrxAppliedRows& ap) {
+  if (!c->qfrc_applied && !c->xfrc_applied) return;   // wave-uniform: kernel arguments
+  const int nv = GRX_NVC;
+  if (c->xfrc_applied) {
+    FOR_LANES {
+      const int b = 1 + lane;
+      if (b < GRX_NBC) {
+        const float f[3] = {ap.x[0], ap.x[1], ap.x[2]}, t[3] = {ap.x[3], ap.x[4], ap.x[5]};
+        const float* R = c->xmat + 9 * b; const float* cref = c->xpos + 3 * m->body_rootid[b];
+        float ip[3] = {m->body_ipos[3 * b], m->body_ipos[3 * b + 1], m->body_ipos[3 * b + 2]}, r[3], rf[3];
+        mulMatVec3f(r, R, ip);
+        r[0] += c->xpos[3 * b] - cref[0]; r[1] += c->xpos[3 * b + 1] - cref[1]; r[2] += c->xpos[3 * b + 2] - cref[2];
+        cross3f(rf, r, f);
+        for (int k = 0; k < 3; k++) { c->cacc[6 * b + k] = t[k] + rf[k]; c->cacc[6 * b + 3 + k] = f[k]; }
+      }
+    }
+    WAVE_SYNC();
+    FOR_LANES {
+      for (int it = lane; it < 6 * GRX_NBC; it += 64) {
+        int b = it / 6, k = it - 6 * b;
+        unsigned mlo = (unsigned)m->body_submask[2 * b], mhi = (S::kFixed && S::NB <= 32) ? 0u : (unsigned)m->body_submask[2 * b + 1];
+        float s = 0;
+#pragma unroll 16
+        for (int e = 1; e < GRX_NBC; e++) { unsigned bit = e < 32 ? (mlo >> e) & 1u : (mhi >> (e - 32)) & 1u; s += bit ? c->cacc[6 * e + k] : 0.0f; }
+        c->cfrc[it] = s;
+      }
+    }
+    WAVE_SYNC();
+  }
+  FOR_LANES {
+    if (lane < nv) {
+      const int d = lane;
+      float q = ap.q;
+      if (c->xfrc_applied) {
+        const int b = m->reci_dof[GRX_RDI * d + 6];
+        float s = 0;
+        for (int k = 0; k < 6; k++) s += c->cdof[6 * d + k] * c->cfrc[6 * b + k];
+        q += s;
+      }
+      const float f = c->qfrc_smooth[d] + q;
+      c->qfrc_smooth[d] = f; c->qacc_smooth[d] = f;
+    }
+  }
+  WAVE_SYNC();
+}
+#endif
+
 GRX_MEM void grx_velocity(const GrxModel* m, GrxCtx* c, int lane_) {
   GRX_OPAQUE_STAGE(lane_);   // record addresses and lane masks of this stage are recomputed here, not carried (spilled) across the substep loop
   GRX_FRESH_MODEL(m, c);
   const int nv = GRX_NVC;
+#if defined(GRX_APPLIED_FORCES)
+  GrxAppliedRows applied_rows;
+  grx_applied_load(m, c, lane_, applied_rows);
+#endif
   // One lane per dof (grx_model_create refuses more than 64): everything dof d's lane needs from the model in this stage comes from ONE record (GrxModel::reci_dof / recf_dof),
   // read in one volley -- the table walk it replaces (`j = dof_jntid[d]` ... `jnt_stiffness[j]` ... `jnt_qposadr[j]`, `dof_bodyid[dof_cvelstart[d]]` ... `body_dofadr[..]`) was
   // three dependent vector-L1 round trips (profiles/cpi_r06_fetch.txt).
@@ -154,5 +222,8 @@ GRX_MEM void grx_velocity(const GrxModel* m, GrxCtx* c, int lane_) {
     }
   }
   WAVE_SYNC();
+#if defined(GRX_APPLIED_FORCES)
+  grx_applied_forces(m, c, lane_, applied_rows);
+#endif
 }
 

@@ -248,6 +248,11 @@ struct GrxCtx {
   // NOTE: with this member GrxCtx (like GrxSimModelArg and the signature of grx_sim_step_world in grx_kernels.hip) differs between the units linked into one library.  That holds
   // only because GrxCtx is DEVICE-ONLY and every unit is a code object of its own: no host code, and nothing in the lane emulator, may pass a GrxCtx between units.
 #endif
+#if defined(GRX_APPLIED_FORCES)
+  // the kernels with applied forces (csrc/grx_sim_task.h GrxSimApplied, translation units GRX_TU_SIMFRC / GRX_TU_SIMFRCPRM): this world's rows in HBM, either may be null.
+  // Like pmodel above, the members exist only in the units compiled with the macro: every other unit keeps the GrxCtx and the velocity stage it always had.
+  const float *qfrc_applied, *xfrc_applied;   // [nv] [nbody,6] = (force, torque) in world coordinates at xipos (grx_applied_forces, csrc/grx_eng_velocity.h)
+#endif
   int bail;    // != 0: a step kernel that hands capacity overflows to a re-run at a larger capacity stops simulating at the first overflowing substep (nothing of this run is kept)
   int soft_maxefc, soft_jpool, soft_maxcon;   // > 0 (the large-table kernel of the overflow lane): the capacities of the FAST kernel; exceeding one of them raises GRX_ST_SOFT
   int *lane_entry_count, *lane_entry_list; int lane_entry_cap, lane_world; int* lane_ready; int lane_ready_cap;   // fast kernel with an overflow lane: where a world that overflows claims its re-run (grx_lane_claim)

@@ -12,7 +12,10 @@
 // kernels: they are compiled with GRX_PARAM_MODEL, under which every stage takes its model from the world's own descriptor in HBM (GRX_FRESH_MODEL, csrc/grx_engine.h), so
 // nothing else can share a unit with them and the single-unit build has stubs in their place (GRX_TU_ALL).
 // -DGRX_TU_SIMCON and, with GRX_PARAM_MODEL, -DGRX_TU_SIMCONPRM hold the stepper's kernels for the launches that request a contact output (GrxSimContacts, csrc/grx_sim_task.h).
-#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM)
+// -DGRX_TU_SIMFRC and, with GRX_PARAM_MODEL, -DGRX_TU_SIMFRCPRM hold its kernels for the launches with applied forces (GrxSimApplied): they are compiled with
+// GRX_APPLIED_FORCES, under which GrxCtx carries the two input rows and the velocity stage ends in grx_applied_forces (csrc/grx_eng_velocity.h).  As with GRX_PARAM_MODEL nothing
+// else can share a unit with them, and the single-unit build has stubs in their place.
+#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM) && !defined(GRX_TU_SIMFRC) && !defined(GRX_TU_SIMFRCPRM)
 #define GRX_TU_ALL 1
 #define GRX_TU_FETCH 1
 #define GRX_TU_HAND 1
@@ -29,8 +32,11 @@
 #if GRX_TU_FETCH && !defined(GRX_NO_HULL_HINTS)
 #define GRX_HULL_HINTS 1
 #endif
-#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM
+#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM || GRX_TU_SIMFRCPRM
 #define GRX_PARAM_MODEL 1
+#endif
+#if GRX_TU_SIMFRC || GRX_TU_SIMFRCPRM
+#define GRX_APPLIED_FORCES 1
 #endif
 #include <hip/hip_runtime.h>
 
@@ -67,6 +73,8 @@ static_assert(sizeof(grx_sim_dynamics) == sizeof(GrxSimDynamics) && offsetof(grx
               "grx_sim_dynamics must mirror GrxSimDynamics");
 static_assert(sizeof(grx_sim_contacts) == sizeof(GrxSimContacts) && offsetof(grx_sim_contacts, force) == offsetof(GrxSimContacts, force) && offsetof(grx_sim_contacts, ccap) == offsetof(GrxSimContacts, ccap),
               "grx_sim_contacts must mirror GrxSimContacts");
+static_assert(sizeof(grx_sim_applied) == sizeof(GrxSimApplied) && offsetof(grx_sim_applied, xfrc_applied) == offsetof(GrxSimApplied, xfrc_applied) && offsetof(grx_sim_applied, xipos) == offsetof(GrxSimApplied, xipos),
+              "grx_sim_applied must mirror GrxSimApplied");
 
 // ------------------------------------------------------------------------------------------
 // kernels
@@ -820,8 +828,10 @@ typedef int GrxSimModelArg;
 #endif
 // CON: the instance that serves the third output block (GrxSimContacts) too, again in kernels of its own (grx_sim_step_con_kernel, grx_sim_lane_con_kernel; translation units
 // GRX_TU_SIMCON / GRX_TU_SIMCONPRM).  They carry both optional blocks; the eight kernels without it keep their argument lists and their code.
+// a: the fourth block (GrxSimApplied), read only in the units compiled with GRX_APPLIED_FORCES (grx_sim_step_frc_kernel, grx_sim_lane_frc_kernel): the world's two input rows
+// go into the context, where the velocity stage of every pass finds them, and xipos leaves with the other outputs.
 template <class S, bool DYN, bool CON = false>
-__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o = nullptr) {
+__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o = nullptr, const GrxSimApplied* a = nullptr) {
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
   GrxCtx c;
@@ -837,6 +847,10 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
   c.mslot = mslot;
 #endif
   grx_ctx_carve(&c, lds, grx_shape_dims<S>(m));
+#if defined(GRX_APPLIED_FORCES)
+  c.qfrc_applied = a->qfrc_applied ? a->qfrc_applied + (size_t)w * m.nv : nullptr;
+  c.xfrc_applied = a->xfrc_applied ? a->xfrc_applied + (size_t)w * 6 * m.nbody : nullptr;
+#endif
   GRX_PROF_BEGIN(c, lane_);
   grx_lane_setup(b.lane, c, w, true);
   for (int i = lane_; i < words; i += 64) lds[i] = 0.0f;
@@ -855,6 +869,9 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
   GrxSim<S>::grx_sim_outputs(&m, &c, &b, (size_t)w, lane_);
   if constexpr (CON) GrxSim<S>::grx_sim_contact_force(&m, &c, o, (size_t)w, lane_, crow, ckey);
   if constexpr (DYN) GrxSim<S>::grx_sim_dynamics_out(&m, &c, d, (size_t)w, lane_);
+#if defined(GRX_APPLIED_FORCES)
+  GrxSim<S>::grx_sim_xipos_out(&m, &c, a->xipos, (size_t)w, lane_);
+#endif
   if (lane_ == 0) b.status[w] = grx_status_word(b.status[w], c.cnt[2]);
   GRX_PROF_END(c, lane_);
 }
@@ -896,6 +913,22 @@ grx_sim_lane_con_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimCont
   extern __shared__ float lds[];
   grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o); });
 }
+#if defined(GRX_APPLIED_FORCES)
+// the kernels of the launches with applied forces (GrxSimApplied): all three output blocks ride along, so one pair serves every combination.  The first argument is the slot or,
+// in the unit with per-world model parameters, the descriptor array (GrxSimModelArg): the same two templates are instantiated in GRX_TU_SIMFRC and GRX_TU_SIMFRCPRM.
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_frc_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, true, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a);
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_frc_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a); });
+}
+#endif
 #if defined(GRX_PARAM_MODEL)
 // the same six kernels for worlds with per-world model parameters: desc[w] is world w's descriptor (grx_sim_params_create)
 template <class S>
@@ -986,6 +1019,11 @@ int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* stream, const
 int grx_tu_simprm_commit(const GrxParamCommit* a, void* stream);
 int grx_tu_simconprm_prepare(int bytes);
 int grx_tu_simconprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only);
+// the units with applied forces (GrxSimApplied): all four blocks
+int grx_tu_simfrc_prepare(const GrxModel* g, int bytes, int slot);
+int grx_tu_simfrc_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only);
+int grx_tu_simfrcprm_prepare(int bytes);
+int grx_tu_simfrcprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only);
 }
 // Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
 // overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
@@ -1232,6 +1270,36 @@ extern "C" int grx_tu_simconprm_launch(unsigned grid, size_t lds_bytes, void* st
   return (int)hipGetLastError();
 }
 #endif
+#if GRX_TU_SIMFRC
+// ... and those with applied forces
+extern "C" int grx_tu_simfrc_prepare(const GrxModel* g, int bytes, int slot) {
+  GRX_LDS(grx_sim_step_frc_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_frc_kernel<GrxShapeAny>);
+  return (int)grx_upload_descriptor(g, slot);
+}
+extern "C" int grx_tu_simfrc_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
+#if GRX_TU_SIMFRCPRM
+extern "C" int grx_tu_simfrcprm_prepare(int bytes) {
+  GRX_LDS(grx_sim_step_frc_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_frc_kernel<GrxShapeAny>);
+  return 0;
+}
+extern "C" int grx_tu_simfrcprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
+#if defined(GRX_TU_ALL)
+// ... nor the GRX_APPLIED_FORCES kernels: a model can be created (nothing to prepare), a launch with applied forces fails
+extern "C" int grx_tu_simfrc_prepare(const GrxModel*, int, int) { return 0; }
+extern "C" int grx_tu_simfrc_launch(unsigned, size_t, void*, int, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, int, int, int, int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simfrcprm_prepare(int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simfrcprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, int, int, int, int) { return (int)hipErrorNotSupported; }
+#endif
 #if defined(GRX_TU_ALL)
 // the single-unit build cannot hold the GRX_PARAM_MODEL kernels: a parameter object cannot be created there (grx_sim_params_create fails on the first of these)
 extern "C" int grx_tu_simprm_prepare(int) { return (int)hipErrorNotSupported; }
@@ -1442,6 +1510,7 @@ static int grx_model_create_impl(const int32_t* H, const int32_t* I, const doubl
   if ((e = grx_tu_sim_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_simdyn_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the dynamics block): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_simcon_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the contact block): ") + hipGetErrorString((hipError_t)e));
+  if ((e = grx_tu_simfrc_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with applied forces): ") + hipGetErrorString((hipError_t)e));
   HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), &m->dev, sizeof(GrxModel), sizeof(GrxModel) * (size_t)m->slot, hipMemcpyHostToDevice));
   return 0;
 }
@@ -1596,7 +1665,9 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
 // grx_sim_step is this call without the second block; the messages keep its name.
 // desc: null, or the per-world descriptors of a parameter object made for m (grx_sim_step_params): the launch then goes to the kernels of the parameter units
 // con: null, or the third block (grx_sim_step_con): its own checks follow those of the first two; a launch that requests one of its outputs runs the kernels of the contact units
-static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc, const grx_sim_contacts* con = nullptr, bool need_con = false) {
+// frc: null, or the fourth block (grx_sim_step_frc): a launch with one of its pointers set runs the kernels of the applied-force units, which carry every block
+static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc, const grx_sim_contacts* con = nullptr, bool need_con = false,
+                             const grx_sim_applied* frc = nullptr, bool need_frc = false) {
   if (!m) return fail("grx_sim_step: null model");
   if (!buf) return fail("grx_sim_step: null buffers");
   if (!buf->qpos || !buf->qvel || !buf->qacc_ws) return fail("grx_sim_step: null state buffer (qpos, qvel, qacc_ws)");
@@ -1615,6 +1686,10 @@ static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, con
   if (con) memcpy(&o, con, sizeof(o));
   const bool contacts = o.geom || o.dim || o.efc_address || o.dist || o.pos || o.frame || o.force;
   if (contacts && o.ccap < 1) return fail("grx_sim_step_con: ccap < 1 with a contact buffer set (ccap is the number of slots per world)");
+  if (need_frc && !frc) return fail("grx_sim_step_frc: null applied block (grx_sim_step_con is the call without one)");
+  GrxSimApplied a; memset(&a, 0, sizeof(a));
+  if (frc) memcpy(&a, frc, sizeof(a));
+  const bool applied = a.qfrc_applied || a.xfrc_applied || a.xipos;
   const GrxModel& g = m->dev;
   for (int k = 0; k < d.njac; k++)
     if (d.jac_site[k] < 0 || d.jac_site[k] >= g.nsite) return fail("grx_sim_step_dyn: jac_site[" + std::to_string(k) + "] = " + std::to_string(d.jac_site[k]) + " is outside [0, nsite)");
@@ -1628,7 +1703,9 @@ static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, con
   const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
   const unsigned grid = grx_step_grid(b.lane, 0, 0, n_worlds); const size_t lds_bytes = (size_t)m->words * 4 + m->lds_pad;
   int e;
-  if (contacts) e = desc ? grx_tu_simconprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+  if (applied) e = desc ? grx_tu_simfrcprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+                        : grx_tu_simfrc_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  else if (contacts) e = desc ? grx_tu_simconprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
                          : grx_tu_simcon_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
   else if (desc) e = dynamic ? grx_tu_simdynprm_launch(grid, lds_bytes, stream, desc, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
                         : grx_tu_simprm_launch(grid, lds_bytes, stream, desc, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
@@ -1646,15 +1723,38 @@ extern "C" int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int 
 }
 // The stepper with the third block: p null = the model's own parameters (grx_sim_step_dyn), else the checks and the kernels of grx_sim_step_params.  A block of nulls
 // forwards to those entry points' launches.
-extern "C" int grx_sim_step_con(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, int n_worlds, int nstep, int forward_only, void* stream) {
-  const GrxModel* desc = nullptr;
+// 0 and *desc = null (p null) or the per-world descriptors of p for the handle m; -1 where grx_sim_step_params refuses the pair
+static int grx_sim_params_desc(const grx_model* m, const grx_sim_params* p, int n_worlds, const GrxModel** desc) {
+  *desc = nullptr;
   if (p) {
     if (!m) return fail("grx_sim_step_params: null model");
     if (m != p->model && m != p->large) return fail("grx_sim_step_params: the parameter object was not created for this model handle");
     if (n_worlds != p->n) return fail("grx_sim_step_params: n_worlds = " + std::to_string(n_worlds) + ", the parameter object holds " + std::to_string(p->n) + " worlds");
-    desc = m == p->model ? p->d_desc : p->d_desc_large;
+    *desc = m == p->model ? p->d_desc : p->d_desc_large;
   }
+  return 0;
+}
+extern "C" int grx_sim_step_con(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, int n_worlds, int nstep, int forward_only, void* stream) {
+  const GrxModel* desc;
+  if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
   return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, true);
+}
+// The stepper with the fourth block (applied forces, xipos): dyn and con may be null here.  A block of nulls forwards to what grx_sim_step_con launches for the other arguments.
+extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc, int n_worlds, int nstep, int forward_only,
+                                void* stream) {
+  const GrxModel* desc;
+  if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
+  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, false, frc, true);
+}
+// sizeof(grx_sim_applied) and the byte offset of every member, in declaration order: what _native.SimAppliedStruct must mirror (host only)
+extern "C" int grx_sim_applied_layout(long long* out, int cap) {
+  const grx_sim_applied* z = nullptr;
+#define OFF(f) (long long)((const char*)&z->f - (const char*)z)
+  const long long v[] = {(long long)sizeof(grx_sim_applied), OFF(qfrc_applied), OFF(xfrc_applied), OFF(xipos)};
+#undef OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  if (out) for (int i = 0; i < n && i < cap; i++) out[i] = v[i];
+  return n;
 }
 // sizeof(grx_sim_contacts) and the byte offset of every member, in declaration order: what _native.SimContactsStruct must mirror (host only)
 extern "C" int grx_sim_contacts_layout(long long* out, int cap) {

@@ -43,9 +43,30 @@ struct GrxSimContacts {
   int ccap;
 };
 
+// The fourth optional block (include/grx_capi.h grx_sim_applied), the stepper's only INPUT that is not an actuator: MjData's qfrc_applied and xfrc_applied, held over the
+// substeps of a launch as ctrl is and never written, and xipos, the point xfrc_applied acts at, as an output of the same pass as xpos.  Every pointer may be null.  A launch
+// with a pointer set runs the kernels of the units compiled with GRX_APPLIED_FORCES, whose velocity stage ends in grx_applied_forces (csrc/grx_eng_velocity.h).
+struct GrxSimApplied {
+  const float *qfrc_applied, *xfrc_applied;   // [N,nv] [N,nbody,6]: (force, torque) per compiled body in world coordinates, row 0 ignored
+  float* xipos;                               // [N,nbody,3]
+};
+
 template <class S>
 struct GrxSim {
   typedef GrxEngine<S> E;
+  // data.xipos of the pass xpos is from: xpos + xmat body_ipos, the expression grx_inertia_cdof evaluates (both factors are persistent in GrxCtx); element e on lane e mod 64
+  GRX_MEM void grx_sim_xipos_out(const GrxModel* m, const GrxCtx* c, float* xipos, size_t w, int lane_) {
+    if (!xipos) return;
+    GRX_FRESH_MODEL(m, c);
+    const int nb = GRX_NBC;
+    FOR_LANES {
+      for (int e = lane; e < 3 * nb; e += 64) {
+        const int b = e / 3, k = e - 3 * b;
+        const float* R = c->xmat + 9 * b + 3 * k;
+        xipos[w * 3 * nb + e] = c->xpos[e] + R[0] * m->body_ipos[3 * b] + R[1] * m->body_ipos[3 * b + 1] + R[2] * m->body_ipos[3 * b + 2];
+      }
+    }
+  }
   // The contact list leaves in two parts, because the solve stage reuses the P1 overlay the list lives in (grx_ctx_carve) and efc_force exists only after the solve.
   // Part 1, between grx_make_constraint and the solve of the last pass: geom, dim, efc_address, dist, pos and frame.  A world's rows of a member are contiguous; element e goes
   // to lane e mod 64 (grx_sim_dynamics_out does the same for the Jacobians).  Lane k keeps what part 2 needs of contact k in two registers across the solve: crow = the first

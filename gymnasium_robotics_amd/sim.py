@@ -52,6 +52,17 @@ which rule; a commit never raises and never synchronises.  Friction is a propert
     sim.commit_params()
     assert not sim.params_invalid.any()
 
+APPLIED FORCES, the one input that is not an actuator: ``applied`` names any of ``sim.APPLIED``.  ``qfrc_applied`` [N, nv] and ``xfrc_applied`` [N, nbody, 6] are fp32 tensors the
+caller writes in place (zero-initialised, held over the substeps of a launch as ``ctrl`` is, never written by a launch, zeroed by ``reset``), with MuJoCo's meaning: in every
+forward pass ``qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum_b jacp_b' f_b + jacr_b' t_b``, where ``xfrc_applied[b] = (f_b, t_b)`` is a force and a
+torque in world coordinates (force first) at ``xipos[b]``, the centre of mass of COMPILED body b (rows as ``xpos``; row 0, the world, is ignored).  ``xipos`` [N, nbody, 3] is
+``data.xipos`` of the same pass as ``xpos``: a force at a point p is ``(f, (p - xipos) x f)``.  ``qfrc_bias`` / ``qfrc_passive`` / ``qfrc_actuator`` do not contain the applied
+terms.  Naming one routes the launch through grx_sim_step_frc.  Non-finite applied values are the caller's error and behave as a non-finite ``ctrl`` does.
+
+    sim = grx.BatchedSim("my_robot.xml", 4096, applied=("xfrc_applied", "xipos"))
+    sim.xfrc_applied[:, sim.body_id("torso"), :3] = 50.0 * torch.randn(4096, 3, device="cuda")     # a shove through the torso's centre of mass
+    sim.step(nstep=20)
+
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
 cfrc_ext, MuJoCo's contact order, elliptic cones.
 """
@@ -71,6 +82,8 @@ PARAM_BAD = dict(nonfinite=1, frictionloss=2, damping=4, inertial=8, armature=16
 CONTACTS = ("contact_geom", "contact_dim", "contact_efc_address", "contact_dist", "contact_pos", "contact_frame", "contact_force")      # grx_sim_contacts, in its order
 _CONTACT_WIDTH = dict(contact_geom=(2,), contact_dim=(), contact_efc_address=(), contact_dist=(), contact_pos=(3,), contact_frame=(9,), contact_force=(6,))
 _INT_TENSORS = ("ncon", "nefc", "contact_geom", "contact_dim", "contact_efc_address")
+APPLIED = ("qfrc_applied", "xfrc_applied", "xipos")      # grx_sim_applied, in its order: two inputs the caller writes, one output
+APPLIED_INPUTS = ("qfrc_applied", "xfrc_applied")
 MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
 
 
@@ -87,14 +100,14 @@ class _Params:
 
 
 class BatchedSim:
-    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=()):
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=(), applied=()):
         """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
         default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
         again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
         CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
         keep_sites, mutate, ...).  jac_sites: the names of the sites whose Jacobians site_jacp / site_jacr hold, in the order of their rows (None: every site of the model, which must
         then have at most 16).  model_params: the tables that are per world, any of sim.PARAMS (module docstring).  contacts: the members of the contact list to allocate and write, any of sim.CONTACTS
-        (module docstring).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        (module docstring).  applied: the applied-force inputs and xipos, any of sim.APPLIED (module docstring).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
         if int(num_worlds) < 1:
             raise ValueError("num_worlds must be at least 1")
         if overflow not in ("rerun", "flag"):
@@ -124,6 +137,15 @@ class BatchedSim:
         if len(set(contacts)) != len(contacts):
             raise ValueError(f"contacts names an output twice: {contacts}; the contact outputs are {CONTACTS}")
         self.contacts = tuple(c for c in CONTACTS if c in contacts)
+        if isinstance(applied, str):
+            applied = (applied,)
+        applied = tuple(applied)
+        unknown = [a for a in applied if a not in APPLIED]
+        if unknown:
+            raise ValueError(f"unknown applied name(s) {unknown}; the applied-force tensors are {APPLIED}")
+        if len(set(applied)) != len(applied):
+            raise ValueError(f"applied names a tensor twice: {applied}; the applied-force tensors are {APPLIED}")
+        self.applied = tuple(a for a in APPLIED if a in applied)
         kw = dict(compile_kwargs or {})
         if kw.get("origin") is not None or kw.get("shift_body") is not None:
             raise ValueError("BatchedSim returns raw engine coordinates: compile the model in the MJCF's own frame (no origin) and without a shift group")
@@ -163,7 +185,7 @@ class BatchedSim:
         if wants_jac and not self._jac_ids:
             raise ValueError("site_jacp / site_jacr need at least one site (the model has none, or jac_sites is empty)")
         self._t = None      # the device tensors, made on first use
-        self._h = self._h_big = self.lane = self._p = None
+        self._h = self._h_big = self.lane = self._p = self._frc = None
 
     # ------------------------------------------------------------------ names (CompiledModel.names / tables): no device needed
     def _lookup(self, kind, name):
@@ -238,7 +260,8 @@ class BatchedSim:
                     xpos=(n, self.nbody, 3), xquat=(n, self.nbody, 4), site_xpos=(n, self.nsite, 3), site_xmat=(n, self.nsite, 9), site_xvelp=(n, self.nsite, 3),
                     site_xvelr=(n, self.nsite, 3), sensordata=(n, self.ntouch), ncon=(n,), nefc=(n,), qM=(n, self.nv, self.nv), site_jacp=(n, len(self._jac_ids), 3, self.nv),
                     site_jacr=(n, len(self._jac_ids), 3, self.nv), **{k: (n, self.nv) for k in DYNAMICS if k not in ("qM",) + JACOBIANS},
-                    **{k: (n, self.contact_capacity) + _CONTACT_WIDTH[k] for k in CONTACTS})
+                    **{k: (n, self.contact_capacity) + _CONTACT_WIDTH[k] for k in CONTACTS},
+                    qfrc_applied=(n, self.nv), xfrc_applied=(n, self.nbody, 6), xipos=(n, self.nbody, 3))
 
     def _ensure(self):
         if self._t is not None:
@@ -258,7 +281,7 @@ class BatchedSim:
         self.lds_bytes = self._L.grx_model_lds_bytes(self._h)
         shapes = self._shapes()
         t = {}
-        for k in STATE + self.outputs + self.contacts:
+        for k in STATE + self.outputs + self.contacts + self.applied:
             t[k] = torch.zeros(shapes[k], dtype=torch.int32 if k in _INT_TENSORS else torch.float32, device=self.device)
         t["status_words"] = torch.zeros(self.num_worlds, dtype=torch.int32, device=self.device)
         tb = self.model.tables
@@ -276,6 +299,8 @@ class BatchedSim:
         self._con = None
         if self.contacts:      # again one block for both launches: ccap is the capacity of the larger handle
             self._con = _native.SimContactsStruct(ccap=self.contact_capacity, **{k[len("contact_"):]: t[k].data_ptr() for k in self.contacts})
+        if self.applied:      # the fourth block, again one for both launches: a re-run world takes its applied rows along
+            self._frc = _native.SimAppliedStruct(**{k: t[k].data_ptr() for k in self.applied})
         if self.overflow == "rerun":
             self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
             if self._h_big is not None:
@@ -305,7 +330,7 @@ class BatchedSim:
         if name in ("device", "lds_bytes"):      # known once the device side exists
             self._ensure()
             return self.__dict__[name]
-        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()) or name in self.__dict__.get("contacts", ()):
+        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()) or name in self.__dict__.get("contacts", ()) or name in self.__dict__.get("applied", ()):
             return self._ensure()[name]
         if name in ("params", "params_invalid"):
             if not self.__dict__.get("param_names"):
@@ -314,6 +339,8 @@ class BatchedSim:
             return t["params_invalid"] if name == "params_invalid" else self._params
         if name in OUTPUTS:
             raise AttributeError(f"output {name!r} was not requested: BatchedSim(..., outputs={self.__dict__.get('outputs', ())})")
+        if name in APPLIED:
+            raise AttributeError(f"{name!r} was not requested: BatchedSim(..., applied=...), any of {APPLIED}")
         if name in CONTACTS:
             raise AttributeError(f"contact output {name!r} was not requested: BatchedSim(..., contacts={self.__dict__.get('contacts', ())})")
         raise AttributeError(name)
@@ -352,7 +379,12 @@ class BatchedSim:
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            if self._con is not None:      # the kernels that write the contact list; they serve the other two blocks and the per-world parameters as well
+            if self._frc is not None:      # the kernels with applied forces; they serve every other block and the per-world parameters as well
+                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
+                con = None if self._con is None else ctypes.byref(self._con)
+                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_frc(h, self._p, ctypes.byref(b), dyn, con, ctypes.byref(self._frc), self.num_worlds, int(nstep),
+                                                                                  int(forward_only), stream_ptr(self.device))))
+            elif self._con is not None:      # the kernels that write the contact list; they serve the other two blocks and the per-world parameters as well
                 dyn = None if self._dyn is None else ctypes.byref(self._dyn)
                 go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_con(h, self._p, ctypes.byref(b), dyn, ctypes.byref(self._con), self.num_worlds, int(nstep),
                                                                                   int(forward_only), stream_ptr(self.device))))
@@ -400,15 +432,15 @@ class BatchedSim:
             _native.check(self._L.grx_sim_params_commit(self._p, None if m is None else m.data_ptr(), t["params_invalid"].data_ptr(), stream_ptr(self.device)))
 
     def reset(self, mask=None):
-        """mj_resetData for the masked worlds (all by default): qpos0, zero velocities / warm start / ctrl, the model's mocap poses; then forward().  The model parameters
-        are not state: they stay as committed."""
+        """mj_resetData for the masked worlds (all by default): qpos0, zero velocities / warm start / ctrl / applied forces, the model's mocap poses; then forward().  The
+        model parameters are not state: they stay as committed."""
         import torch
 
         t = self._ensure()
         m = self._mask(mask)
         sel = slice(None) if m is None else m.bool()
         t["qpos"][sel] = self._qpos0
-        for k in ("qvel", "qacc_warmstart", "ctrl"):
+        for k in ("qvel", "qacc_warmstart", "ctrl") + tuple(a for a in self.applied if a in APPLIED_INPUTS):
             t[k][sel] = 0.0
         if self.nmocap:
             t["mocap_pos"][sel], t["mocap_quat"][sel] = self._mocap_pos0, self._mocap_quat0
@@ -447,6 +479,9 @@ class BatchedSim:
         d = {k: t[k].cpu().numpy().copy() for k in STATE + ("status_words",)}
         if self.param_names:      # the rows as written (a row a commit refused included: set_state commits them again, with the same outcome)
             d["params"] = {k: getattr(self._params, k).cpu().numpy().copy() for k in self.param_names}
+        for k in self.applied:      # the named input rows under their names (xipos is an output)
+            if k in APPLIED_INPUTS:
+                d[k] = t[k].cpu().numpy().copy()
         return d
 
     def set_state(self, d):
@@ -472,6 +507,14 @@ class BatchedSim:
             self.commit_params()
         elif "params" in d:
             raise ValueError("the state carries model parameters and this simulation names none")
+        for k in APPLIED_INPUTS:      # the rule of "params": a state without the key leaves the row alone
+            if k not in d:
+                continue
+            if k not in self.applied:
+                raise ValueError(f"the state carries {k!r} and this simulation does not name it (BatchedSim(..., applied=...))")
+            if tuple(np.shape(d[k])) != tuple(t[k].shape):
+                raise ValueError(f"state row {k!r} has shape {tuple(np.shape(d[k]))}, this simulation holds {tuple(t[k].shape)}")
+            t[k].copy_(torch.from_numpy(np.ascontiguousarray(d[k], dtype=np.float32)).to(self.device))
 
     def close(self):
         from .core import release_models

@@ -439,6 +439,30 @@ int grx_sim_step_con(const grx_model* m, const struct grx_sim_params* params, co
                      int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_contacts), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (9) */
 int grx_sim_contacts_layout(long long* out, int cap);
+/* APPLIED FORCES, a fourth and optional block and the stepper's only input that is not an actuator: MjData's qfrc_applied and xfrc_applied.  In every forward pass of a
+ * launch (each substep, each of the four RK4 stages; forward_only as mj_forward)
+ *     qfrc_smooth = qfrc_passive - qfrc_bias + qfrc_actuator + qfrc_applied + sum over bodies b = 1 .. nbody-1 of jacp_b' f_b + jacr_b' t_b
+ * where xfrc_applied[b] = (f_b, t_b) is a force and a torque in world coordinates (force first) and jacp_b, jacr_b are the Jacobians of xipos[b], the centre of mass of
+ * COMPILED body b, in that pass's configuration (mj_xfrcAccumulate).  Rows index the compiled model's bodies as xpos does; for a body that absorbed static children xipos is
+ * the merged inertial frame's origin.  Row 0 (the world body) is ignored.  qfrc_bias, qfrc_passive and qfrc_actuator do not contain the applied terms.
+ *   qfrc_applied   generalised forces, INPUT, held over the nstep substeps as ctrl is, never written            [N,nv]
+ *   xfrc_applied   Cartesian force and torque per body, INPUT, held likewise, never written                       [N,nbody,6]
+ *   xipos          data.xipos of the same pass as xpos (one substep stale after a step), OUTPUT: the point
+ *                  xfrc_applied acts at -- a force f at a point p is (f, (p - xipos) x f)                         [N,nbody,3]
+ * Every pointer may be NULL.  Masked-out worlds read and write nothing; the re-run call of the overflow lane takes the same block.  Non-finite applied values are the
+ * caller's error and behave as a non-finite ctrl does.
+ * grx_sim_step_frc: params, dyn and con may be NULL and mean what they mean to grx_sim_step_con.  A block of three NULL pointers launches exactly what grx_sim_step_con
+ * launches for the other arguments; one with a pointer set runs kernels of its own, which carry every block.  Returns -1 (grx_last_error) for everything those calls refuse
+ * and for frc == NULL. */
+typedef struct grx_sim_applied {
+  const float* qfrc_applied;
+  const float* xfrc_applied;
+  float* xipos;
+} grx_sim_applied;
+int grx_sim_step_frc(const grx_model* m, const struct grx_sim_params* params, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc,
+                     int n_worlds, int nstep, int forward_only, void* stream);
+/* host only: out[0] = sizeof(grx_sim_applied), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (4) */
+int grx_sim_applied_layout(long long* out, int cap);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)
