@@ -223,7 +223,13 @@ GRX_MEM void grx_plane_cylinder(const GrxModel* m, GrxCtx* c, int pair, int g1, 
   const float dist0 = dot3f(dd, n);
   float vec[3] = {ax[0] * prjaxis - n[0], ax[1] * prjaxis - n[1], ax[2] * prjaxis - n[2]};
   const float len2 = dot3f(vec, vec);
-  if (len2 >= 1e-30f) { const float sc = r / sqrtf(len2); vec[0] *= sc; vec[1] *= sc; vec[2] *= sc; }
+  if (len2 >= 1e-30f) {
+    const float len = sqrtf(len2), sc = r / len; vec[0] *= sc; vec[1] *= sc; vec[2] *= sc;
+    // For unit n and ax, vec . n = r (prjaxis^2 - 1) / len = -r len exactly.  The computed difference ax prjaxis - n carries the fp32 rounding of |ax|^2 and |n|^2 (~1e-7)
+    // ALONG n, where the exact component is len2 itself: next to a flat cap (len ~ 3e-4) that is as large as the component, and r / len scales it to 1e-5 .. 1e-4 of
+    // height on the rim points.  Put the component along n where the identity has it; len2 is dominated by the components across n and is accurate.
+    const float fix = -r * len - dot3f(vec, n); vec[0] += fix * n[0]; vec[1] += fix * n[1]; vec[2] += fix * n[2];
+  }
   else { vec[0] = cm[0] * r; vec[1] = cm[3] * r; vec[2] = cm[6] * r; }
   const float prjvec = dot3f(vec, n);
   ax[0] *= hl; ax[1] *= hl; ax[2] *= hl; prjaxis *= hl;

@@ -68,48 +68,52 @@ struct GrxSim {
     }
   }
   // The contact list leaves in two parts, because the solve stage reuses the P1 overlay the list lives in (grx_ctx_carve) and efc_force exists only after the solve.
-  // Part 1, between grx_make_constraint and the solve of the last pass: geom, dim, efc_address, dist, pos and frame.  A world's rows of a member are contiguous; element e goes
-  // to lane e mod 64 (grx_sim_dynamics_out does the same for the Jacobians).  Lane k keeps what part 2 needs of contact k in two registers across the solve: crow = the first
-  // row or -1, ckey = pair << 4 | rows (GRX_MAXCON = 64: one lane per contact).  A contact whose rows do not all lie inside nefc has none: address -1, zero force.
+  // Part 1, between grx_make_constraint and the solve of the last pass: geom, dim, efc_address, dist, pos and frame.  A world's rows of a member are contiguous; one lane
+  // writes one contact (GRX_MAXCON = 64: one lane per contact).  Lane k keeps what part 2 needs of the contact in OUTPUT SLOT k in two registers across the solve: crow = the
+  // first row or -1, ckey = pair << 4 | rows.  A contact whose rows do not all lie inside nefc has none: address -1, zero force.
   GRX_MEM void grx_sim_contacts_p1(const GrxModel* m, const GrxCtx* c, const GrxSimContacts* o, size_t w, int lane_, int& crow, int& ckey) {
     GRX_FRESH_MODEL(m, c);
     const int ncon = c->cnt[0] < c->maxcon ? c->cnt[0] : c->maxcon, nefc = c->cnt[1], cap = o->ccap, nw = ncon < cap ? ncon : cap;
+    // The ORDER of the outputs is by candidate pair, a pair's contacts in the engine's order: the order grx_collision's own re-sort leaves where it runs (noslip models, the
+    // large scenes).  Elsewhere its late queues (box-box, hull pairs, large plane-mesh pairs) append their contacts behind the analytic ones, and the constraint rows are built
+    // in that order: the list stays as it is -- a launch that requests contacts computes what one that does not computes -- and the outputs are permuted.  Lane k is contact k:
+    // it ranks its contact by counting and writes it to slot `rank`; lane r then takes over what part 2 needs of the contact in slot r.
     FOR_LANES {
-      crow = -1; ckey = 0;
+      int rank = lane, r0 = -1, nr = 0, p = 0;
       if (lane < ncon) {
-        const int r0 = c->con_efc[lane], nr = c->con_nr[lane];
-        const int has = r0 >= 0 && nr > 0 && r0 + nr <= nefc;
-        crow = has ? r0 : -1; ckey = (c->con_pair[lane] << 4) | (has ? nr : 0);
+        p = c->con_pair[lane];
+        rank = 0;
+        for (int j = 0; j < ncon; j++) { const int pj = c->con_pair[j]; rank += (pj < p) || (pj == p && j < lane); }
+        r0 = c->con_efc[lane]; nr = c->con_nr[lane];
+        if (!(r0 >= 0 && nr > 0 && r0 + nr <= nefc)) { r0 = -1; nr = 0; }
       }
-      if (o->efc_address)
-        for (int e = lane; e < cap; e += 64) {
-          int a = -1;
-          if (e < nw) { const int r0 = c->con_efc[e], nr = c->con_nr[e]; a = (r0 >= 0 && nr > 0 && r0 + nr <= nefc) ? r0 : -1; }
-          o->efc_address[w * cap + e] = a;
-        }
-      if (o->dim) for (int e = lane; e < cap; e += 64) o->dim[w * cap + e] = e < nw ? m->reci_pair[GRX_RPI * c->con_pair[e]] : 0;
-      if (o->geom)
-        for (int e = lane; e < 2 * cap; e += 64) {
-          const int k = e >> 1;
-          int g = -1;
-          if (k < nw) { const int p = c->con_pair[k]; g = (e & 1) ? m->pair_geom2[p] : m->pair_geom1[p]; }
-          o->geom[w * 2 * cap + e] = g;
-        }
-      if (o->dist) for (int e = lane; e < cap; e += 64) o->dist[w * cap + e] = e < nw ? c->con_dist[e] : 0.0f;
-      if (o->pos) for (int e = lane; e < 3 * cap; e += 64) o->pos[w * 3 * cap + e] = e < 3 * nw ? c->con_pos[e] : 0.0f;
-      if (o->frame)
-        for (int e = lane; e < 9 * cap; e += 64) {
-          const int k = e / 9, j = e - 9 * k;
-          float v = 0.0f;
-          if (k < nw) {   // the frame the contact's rows were built in: the same routine on the same normal (grx_make_constraint)
-            float fr[9] = {c->con_frame[3 * k], c->con_frame[3 * k + 1], c->con_frame[3 * k + 2], 0, 0, 0, 0, 0, 0};
-            E::grx_make_frame(fr);
-            v = fr[0];
+      const int own_key = (p << 4) | nr;
+      int src = lane;   // the contact in slot `lane`: ranks are a permutation of 0 .. ncon - 1, the lanes past the list keep their own (empty) registers
+      for (int j = 0; j < ncon; j++) { if (__shfl(rank, j) == lane) src = j; }   // wave-uniform trip count
+      crow = __shfl(r0, src); ckey = __shfl(own_key, src);
+      if (lane < ncon && rank < cap) {
+        const size_t s = w * cap + rank;
+        if (o->efc_address) o->efc_address[s] = r0;
+        if (o->dim) o->dim[s] = m->reci_pair[GRX_RPI * p];
+        if (o->geom) { o->geom[2 * s] = m->pair_geom1[p]; o->geom[2 * s + 1] = m->pair_geom2[p]; }
+        if (o->dist) o->dist[s] = c->con_dist[lane];
+        if (o->pos) { for (int t = 0; t < 3; t++) o->pos[3 * s + t] = c->con_pos[3 * lane + t]; }
+        if (o->frame) {   // the frame the contact's rows were built in: the same routine on the same normal (grx_make_constraint)
+          float fr[9] = {c->con_frame[3 * lane], c->con_frame[3 * lane + 1], c->con_frame[3 * lane + 2], 0, 0, 0, 0, 0, 0};
+          E::grx_make_frame(fr);
 #pragma unroll
-            for (int q = 1; q < 9; q++) v = (j == q) ? fr[q] : v;   // a select chain: a lane-indexed read would move the frame to scratch
-          }
-          o->frame[w * 9 * cap + e] = v;
+          for (int q = 0; q < 9; q++) o->frame[9 * s + q] = fr[q];
         }
+      }
+      for (int e = nw + lane; e < cap; e += 64) {   // the slots past the list: the fill values
+        const size_t s = w * cap + e;
+        if (o->efc_address) o->efc_address[s] = -1;
+        if (o->dim) o->dim[s] = 0;
+        if (o->geom) { o->geom[2 * s] = -1; o->geom[2 * s + 1] = -1; }
+        if (o->dist) o->dist[s] = 0.0f;
+        if (o->pos) { for (int t = 0; t < 3; t++) o->pos[3 * s + t] = 0.0f; }
+        if (o->frame) { for (int q = 0; q < 9; q++) o->frame[9 * s + q] = 0.0f; }
+      }
     }
   }
   // Part 2, after the pass: mj_contactForce for the pyramidal cone from the contact's rows of efc_force (P2 overlay, untouched since the solve), in flat order as above.  Lane

@@ -91,6 +91,17 @@ class EmuSim:
                                  ctypes.c_int(nstep))
         return ncon.value, nefc.value
 
+    def contact_list(self, cap=64):
+        """the contact list of the loaded state (self.qpos / qvel), copied out between the constraint and the velocity stage, where the device's contact outputs read it;
+        returns dict(ncon, nefc, status, pair [n], dist [n], pos [n, 3], normal [n, 3]) in the order of the device's contact outputs: by candidate pair, a pair's
+        contacts in the engine's order"""
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        cnt, pair = np.zeros(3, np.int32), np.zeros(cap, np.int32)
+        dist, pos, nrm = np.zeros(cap, np.float32), np.zeros(3 * cap, np.float32), np.zeros(3 * cap, np.float32)
+        n = self.L.emu_contact_list(ctypes.c_void_p(self.h), p(self.qpos), p(self.qvel), ctypes.c_int(cap), p(cnt), p(pair), p(dist), p(pos), p(nrm))
+        return dict(ncon=int(cnt[0]), nefc=int(cnt[1]), status=int(cnt[2]), pair=pair[:n].copy(), dist=dist[:n].copy(), pos=pos.reshape(cap, 3)[:n].copy(),
+                    normal=nrm.reshape(cap, 3)[:n].copy())
+
     def kitchen_step(self, action, last_qpos, noise=None, forward_only=False):
         """FrankaKitchen env.step() (or the reset-time forward pass) of one world; last_qpos is updated in place; returns (obs[59], completed mask)"""
         p = lambda x: x.ctypes.data_as(ctypes.c_void_p)

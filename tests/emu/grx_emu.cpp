@@ -118,6 +118,35 @@ void emu_physics_steps(void* h, float* qpos, float* qvel, float* qacc_ws, const 
   store_state(e, qpos, qvel, qacc_ws, mocap, status);
 }
 
+// TEST ONLY (tests/test_cpu_contact_matrix.py): the contact list of the loaded state.  Runs grx_kinematics, grx_inertia_cdof, grx_collision and grx_make_constraint and
+// copies the list out BEFORE anything else runs -- the later stages reuse the words con_frame lives in; this is where grx_sim_contacts_p1 reads it on the device.
+// cnt[3] = (ncon, nefc, status); pair [cap], dist [cap], pos [3 cap], normal [3 cap].  Returns the number of contacts written (ncon clamped to the table and to cap).
+int emu_contact_list(void* h, const float* qpos, const float* qvel, int cap, int* cnt, int* pair, float* dist, float* pos, float* normal) {
+  Emu* e = (Emu*)h; typedef GrxEngine<GrxShapeAny> E;
+  GrxCtx* c = &e->c;
+  float mocap[8] = {0};
+  for (int k = 0; k < e->m.nmocap && k < 1; k++) { memcpy(mocap, e->m.mocap_pos0, 12); memcpy(mocap + 3, e->m.mocap_quat0, 16); }
+  std::vector<float> ws((size_t)e->m.nv + 1, 0.0f);
+  load_state(e, qpos, qvel, ws.data(), mocap);
+  if (e->m.nshift) { for (int k = 0; k < 7; k++) c->shift[k] = (k == 3) ? 1.0f : 0.0f; }
+  E::grx_kinematics(&e->m, c, 0);
+  E::grx_inertia_cdof(&e->m, c, 0);
+  E::grx_collision(&e->m, c, 0);
+  E::grx_make_constraint(&e->m, c, 0);
+  int n = c->cnt[0] < c->maxcon ? c->cnt[0] : c->maxcon;
+  if (n > cap) n = cap;
+  cnt[0] = c->cnt[0]; cnt[1] = c->cnt[1]; cnt[2] = c->cnt[2];
+  const int nc = c->cnt[0] < c->maxcon ? c->cnt[0] : c->maxcon;
+  for (int k = 0; k < nc; k++) {   // the order of the device's outputs (grx_sim_contacts_p1, which this build does not include): by pair, a pair's contacts in the engine's order
+    int r = 0;
+    for (int j = 0; j < nc; j++) r += (c->con_pair[j] < c->con_pair[k]) || (c->con_pair[j] == c->con_pair[k] && j < k);
+    if (r >= n) continue;
+    pair[r] = c->con_pair[k]; dist[r] = (float)c->con_dist[k];
+    for (int t = 0; t < 3; t++) { pos[3 * r + t] = (float)c->con_pos[3 * k + t]; normal[3 * r + t] = (float)c->con_frame[3 * k + t]; }
+  }
+  return n;
+}
+
 // PointMaze env.step() of one world
 void emu_point_step(void* h, const GrxPointTask* t, float* qpos, float* qvel, float* qacc_ws, const float* action, float* obs, float* achieved,
                     int* status) {
