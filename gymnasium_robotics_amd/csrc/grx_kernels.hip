@@ -1451,6 +1451,12 @@ grx_debug_kernel(int mode, int nv, int nefc, const float* A_in, const float* b_i
 // C ABI
 // ------------------------------------------------------------------------------------------
 static int g_slot_used[GRX_MAX_MODELS];
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "grx_rays.h"
+extern "C" int grx_tu_rays_launch(const GrxRayArgs* a, void* stream);   // csrc/grx_rays.hip, a unit of its own
 
 struct grx_model {
   GrxPackedModel pm;
@@ -1462,6 +1468,13 @@ struct grx_model {
   int slot = -1;  // index of the device-side descriptor in g_grx_models (constant memory)
   int shape = 0;  // 0 = generic step kernel, else index of the specialised GrxShape
   int lds_pad = 0;  // GRX_LDS_PAD_BYTES (occupancy experiments)
+  // what the ray calls derive when the handle first serves one (grx_ray_cache): the hulls' face planes with each geom's (first plane, planes), and a device copy of every
+  // ray_site list it has been given.  Handles are shared between simulations, hence the lock; all of it is freed with the handle.
+  mutable std::mutex ray_mu;
+  mutable bool ray_ready = false;
+  mutable float* d_ray_planes = nullptr;
+  mutable int32_t* d_ray_adr = nullptr;   // [2, ngeom]: first plane, number of planes
+  mutable std::vector<std::pair<std::vector<int>, int*>> ray_sites;
 };
 
 static thread_local std::string g_err;
@@ -1476,6 +1489,9 @@ static void grx_model_free(grx_model* m) {
   (void)hipSetDevice(m->device);
   if (m->d_f) (void)hipFree(m->d_f);
   if (m->d_i) (void)hipFree(m->d_i);
+  if (m->d_ray_planes) (void)hipFree(m->d_ray_planes);
+  if (m->d_ray_adr) (void)hipFree(m->d_ray_adr);
+  for (auto& e : m->ray_sites) (void)hipFree(e.second);
   delete m;
 }
 
@@ -1746,6 +1762,7 @@ extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, con
   if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
   return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, false, frc, true);
 }
+#include "grx_rays_api.h"
 // sizeof(grx_sim_applied) and the byte offset of every member, in declaration order: what _native.SimAppliedStruct must mirror (host only)
 extern "C" int grx_sim_applied_layout(long long* out, int cap) {
   const grx_sim_applied* z = nullptr;

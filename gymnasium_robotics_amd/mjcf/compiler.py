@@ -1233,6 +1233,11 @@ class _Lowering:
             site_pos[si] = p + mu.rot_vec(q, s.pos)
             site_quat[si] = mu.quat_normalize(mu.quat_mul(q, s.quat))
             site_size[si] = s.size
+        # <rangefinder> sensors, in sensor order: bookkeeping only (names["rangefinder"]: name -> row, info["rangefinder"]: site name and cutoff per row).  Nothing of it is
+        # packed: BatchedSim.rangefinder casts one ray per row from the named site (sim.py), and is where a sensor without a usable site is reported
+        finders = [e for sec in c.root.findall("sensor") for e in sec.findall("rangefinder")]
+        names["rangefinder"] = {e.attrib.get("name") or f"_rangefinder{k}": k for k, e in enumerate(finders)}
+        info["rangefinder"] = [dict(site=e.attrib.get("site"), cutoff=float(e.attrib.get("cutoff", 0.0))) for e in finders]
 
         # ---- collision candidate pairs
         excludes = set()

@@ -63,8 +63,22 @@ terms.  Naming one routes the launch through grx_sim_step_frc.  Non-finite appli
     sim.xfrc_applied[:, sim.body_id("torso"), :3] = 50.0 * torch.randn(4096, 3, device="cuda")     # a shove through the torso's centre of mass
     sim.step(nstep=20)
 
+RAYS (``mj_ray``, rangefinders, lidar): ``sim.ray(origin, direction)`` casts R rays per world -- ``origin`` / ``direction`` [N, R, 3] (or [R, 3]) in world coordinates, ``direction``
+of any length -- and returns ``(dist [N, R] float32, geom [N, R] int32)``: the ray parameter of the nearest hit (metres for a unit direction) and the geom hit, -1.0 / -1 for none.
+``sim.ray_sites(sites, local_dir)`` starts the rays at sites and skips each site's own body; ``sim.rangefinder()`` is [N, n_rangefinder], one reading per ``<rangefinder>`` of the MJCF
+(along the site's +z, -1 for none or beyond the sensor's cutoff).  The rays see the body poses of the LAST launch -- ``outputs`` must name ``xpos`` and ``xquat`` (and ``site_xpos`` /
+``site_xmat`` for the site variants) -- so exactly what ``MjData.geom_xpos`` holds then: exact after ``forward()``, one substep stale after ``step()``.  Three deviations from ``mj_ray``:
+the rays see the COMPILED model's geoms, i.e. the collidable ones (visual geoms do not exist there); a mesh geom is its CONVEX HULL, the shape the engine collides with; there are no
+geom groups.  A mesh geom whose only candidate pairs are with planes (or that has none) keeps no full hull in the compiled model: the ray calls raise a ``ValueError`` that names
+it rather than cast through it.  The calls run a kernel of their own (grx_sim_ray / grx_sim_ray_sites) on torch's current stream and never synchronise; rays are not state.
+
+    sim = grx.BatchedSim("maze_agent.xml", 4096, outputs=("xpos", "xquat", "site_xpos", "site_xmat"))
+    fan = torch.stack([torch.cos(ang), torch.sin(ang), torch.zeros_like(ang)], dim=1)             # [64, 3] in the frame of the site "lidar"
+    sim.step(nstep=5)
+    dist, geom = sim.ray_sites("lidar", fan, max_dist=10.0)                                        # [N, 64]
+
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-cfrc_ext, MuJoCo's contact order, elliptic cones.
+cfrc_ext, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, cameras.
 """
 import ctypes
 
@@ -445,6 +459,152 @@ class BatchedSim:
         if self.nmocap:
             t["mocap_pos"][sel], t["mocap_quat"][sel] = self._mocap_pos0, self._mocap_quat0
         self.forward(mask)
+
+    # ------------------------------------------------------------------ rays (include/grx_capi.h grx_sim_ray / grx_sim_ray_sites; module docstring, RAYS)
+    def _ray_need(self, what, needed):
+        missing = [o for o in needed if o not in self.outputs]
+        if missing:
+            raise ValueError(f"{what} casts against the body poses of the last launch and needs the output(s) {missing}: BatchedSim(..., outputs={self.outputs + tuple(missing)})")
+        tb = self.model.tables
+        kind, hull = np.asarray(tb["geom_type"]).reshape(-1), np.asarray(tb["geom_hullnum"]).reshape(-1)
+        bare = [int(g) for g in np.nonzero(kind == 7)[0] if g >= len(hull) or hull[g] < 4]
+        if bare:      # the compiler keeps a mesh's full hull only for hull-vs-convex candidate pairs: a ray would pass through such a geom unseen
+            by_id = {i: name for name, i in self.model.names.get("geom", {}).items()}
+            raise ValueError(f"{what}: mesh geom(s) {[by_id.get(g, g) for g in bare]} have no full hull in the compiled model (a mesh keeps it only when it has a candidate pair with a "
+                             "sphere, capsule, ellipsoid, cylinder, box or mesh geom; these meet planes only, or nothing), so rays cannot see them")
+
+    def _ray_exclude(self, exclude_body, n_rays):
+        """[R] int32 device tensor of compiled body ids (-1: none), or None"""
+        import torch
+
+        if exclude_body is None:
+            return None
+        if isinstance(exclude_body, str):
+            exclude_body = self.body_id(exclude_body)
+        if isinstance(exclude_body, (int, np.integer)):
+            exclude_body = [int(exclude_body)] * n_rays
+        if not torch.is_tensor(exclude_body):
+            exclude_body = [self.body_id(b) if isinstance(b, str) else int(b) for b in exclude_body]
+        e = torch.as_tensor(exclude_body, device=self.device).to(torch.int32).contiguous()
+        if e.shape != (n_rays,):
+            raise ValueError(f"exclude_body must be one body or have length {n_rays}, not shape {tuple(e.shape)}")
+        return e
+
+    def _ray_out(self, out, n_rays):
+        import torch
+
+        if out is None:      # fresh tensors start as "no hit": with a mask the rows of the worlds it leaves out read -1.0 / -1
+            return (torch.full((self.num_worlds, n_rays), -1.0, dtype=torch.float32, device=self.device), torch.full((self.num_worlds, n_rays), -1, dtype=torch.int32, device=self.device))
+        dist, geom = out
+        for x, dt in ((dist, torch.float32), (geom, torch.int32)):
+            if x.shape != (self.num_worlds, n_rays) or x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"out= takes a contiguous float32 and an int32 tensor of shape ({self.num_worlds}, {n_rays}) on {self.device}")
+        return dist, geom
+
+    def _ray_launch(self, fn, block, n_rays, keep):
+        import torch
+
+        from . import _native
+        from .core import stream_ptr
+
+        self._ray_keep = keep      # the inputs stay alive until the next ray call has replaced them (the launch is only enqueued)
+        with torch.cuda.device(self.device):
+            _native.check(fn(self._h, ctypes.byref(block), self.num_worlds, int(n_rays), stream_ptr(self.device)))
+
+    def ray(self, origin, direction, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None):
+        """mj_ray for R rays in every world: origin, direction [N, R, 3] device tensors in world coordinates ([R, 3]: the same rays in every world); direction need not be unit.
+        Returns (dist [N, R] float32, geom [N, R] int32): the parameter t of the nearest hit (metres for a unit direction) and the id of the geom hit (sim.geom_id), or -1.0 / -1
+        for no hit, a hit beyond max_dist (when positive), a zero or non-finite direction.  exclude_body: a body name or compiled body id, or a list / tensor of R of them (-1:
+        none): that body's geoms are skipped (mj_ray's bodyexclude).  include_static=False skips the geoms of the world body.  mask: only the worlds with a non-zero entry are
+        written; the rows of the others read -1.0 / -1 in fresh tensors and keep their bits in out= tensors.  out=(dist, geom): write into these tensors.  Casts against the xpos / xquat of the LAST launch (exact after forward(), one substep stale after step()).
+        Enqueues on torch's current stream; never synchronises."""
+        import torch
+
+        from . import _native
+
+        self._ray_need("ray()", ("xpos", "xquat"))
+        t = self._ensure()
+        o, d = (torch.as_tensor(x, device=self.device).to(torch.float32) for x in (origin, direction))
+        if o.dim() == 2 and d.dim() == 3:
+            o = o.expand(d.shape)
+        if d.dim() == 2:
+            d = d.expand((self.num_worlds,) + tuple(d.shape)) if o.dim() == 2 else d.expand(o.shape)
+        if o.dim() == 2:
+            o = o.expand((self.num_worlds,) + tuple(o.shape))
+        if o.dim() != 3 or o.shape != d.shape or o.shape[0] != self.num_worlds or o.shape[2] != 3 or o.shape[1] < 1:
+            raise ValueError(f"origin and direction must have shape ({self.num_worlds}, R, 3) or (R, 3), not {tuple(o.shape)} and {tuple(d.shape)}")
+        o, d = o.contiguous(), d.contiguous()
+        n_rays = o.shape[1]
+        e, m = self._ray_exclude(exclude_body, n_rays), self._mask(mask)
+        dist, geom = self._ray_out(out, n_rays)
+        b = _native.SimRaysStruct(xpos=t["xpos"].data_ptr(), xquat=t["xquat"].data_ptr(), origin=o.data_ptr(), direction=d.data_ptr(), exclude_body=None if e is None else e.data_ptr(),
+                                  mask=None if m is None else m.data_ptr(), dist=dist.data_ptr(), geom=geom.data_ptr(), max_dist=float(max_dist), include_static=int(bool(include_static)))
+        self._ray_launch(self._L.grx_sim_ray, b, n_rays, (o, d, e, m))
+        return dist, geom
+
+    def ray_sites(self, sites, local_dir, exclude_own_body=True, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None):
+        """R rays that start at sites: ray r starts at site sites[r] (a name or id; one name: every ray) and runs along local_dir[r] ([R, 3], in the site's frame), in every
+        world.  exclude_own_body: the geoms of the site's body are skipped (the rangefinder rule); the other arguments and the result are those of ray().  Reads site_xpos /
+        site_xmat of the last launch as well.  The first call with a list of sites the model handle has not seen uploads it (one blocking copy; the handle keeps the 64 most recent
+        lists); every later call with that list only enqueues."""
+        import torch
+
+        from . import _native
+
+        self._ray_need("ray_sites()", ("xpos", "xquat", "site_xpos", "site_xmat"))
+        t = self._ensure()
+        l = torch.as_tensor(local_dir, device=self.device).to(torch.float32).contiguous()
+        if l.dim() != 2 or l.shape[1] != 3 or l.shape[0] < 1:
+            raise ValueError(f"local_dir must have shape (R, 3), not {tuple(l.shape)}")
+        n_rays = l.shape[0]
+        if isinstance(sites, (str, int, np.integer)):
+            sites = [sites] * n_rays
+        ids = [self.site_id(s) if isinstance(s, str) else int(s) for s in sites]
+        if len(ids) != n_rays:
+            raise ValueError(f"sites names {len(ids)} sites for {n_rays} directions")
+        bad = [s for s in ids if not 0 <= s < self.nsite]
+        if bad:
+            raise ValueError(f"site id(s) {bad} outside [0, {self.nsite})")
+        host = (ctypes.c_int * n_rays)(*ids)
+        e, m = self._ray_exclude(exclude_body, n_rays), self._mask(mask)
+        dist, geom = self._ray_out(out, n_rays)
+        b = _native.SimRaysStruct(xpos=t["xpos"].data_ptr(), xquat=t["xquat"].data_ptr(), site_xpos=t["site_xpos"].data_ptr(), site_xmat=t["site_xmat"].data_ptr(),
+                                  ray_site=ctypes.cast(host, ctypes.c_void_p), local_dir=l.data_ptr(), exclude_body=None if e is None else e.data_ptr(),
+                                  mask=None if m is None else m.data_ptr(), dist=dist.data_ptr(), geom=geom.data_ptr(), max_dist=float(max_dist), include_static=int(bool(include_static)),
+                                  exclude_site_body=int(bool(exclude_own_body)))
+        self._ray_launch(self._L.grx_sim_ray_sites, b, n_rays, (l, e, m, host))
+        return dist, geom
+
+    @property
+    def n_rangefinder(self):
+        return len(self.model.info.get("rangefinder", ()))
+
+    def rangefinder_id(self, name):
+        """column of the <rangefinder> sensor `name` in rangefinder()"""
+        return self._lookup("rangefinder", name)
+
+    def rangefinder(self, mask=None):
+        """[N, n_rangefinder] float32: the reading of every <rangefinder> sensor of the MJCF, in sensor order -- the distance along the +z axis of the sensor's site to the
+        nearest geom that does not belong to the site's body, -1 for none or for one beyond the sensor's positive cutoff (mjSENS_RANGEFINDER, over the geoms ray() sees).
+        mask: the rows of the worlds it leaves out read -1."""
+        import torch
+
+        rows = self.model.info.get("rangefinder", ())
+        if not rows:
+            raise ValueError("the model has no <rangefinder> sensor")
+        lost = [name for name, k in self.model.names["rangefinder"].items() if rows[k]["site"] not in self.model.names["site"]]
+        if lost:
+            raise ValueError(f"the site of rangefinder(s) {sorted(lost)} is not among the model's sites (the sensor names none, or keep_sites dropped it: compile_kwargs=dict(keep_sites=...))")
+        self._ray_need("rangefinder()", ("xpos", "xquat", "site_xpos", "site_xmat"))
+        self._ensure()
+        if self.__dict__.get("_rf") is None:
+            self._rf = (torch.tensor([[0.0, 0.0, 1.0]] * len(rows), device=self.device), torch.tensor([[max(float(r["cutoff"]), 0.0) for r in rows]], dtype=torch.float32, device=self.device))
+        z, cut = self._rf
+        dist, _ = self.ray_sites([r["site"] for r in rows], z, exclude_own_body=True, mask=mask)
+        beyond = (cut > 0) & (dist > cut)      # each sensor's own cutoff
+        if mask is not None:
+            beyond &= self._mask(mask).bool()[:, None]
+        return dist.masked_fill_(beyond, -1.0)
 
     # ------------------------------------------------------------------ status words (include/grx_capi.h grx_status_bits), as the env classes report them
     @property

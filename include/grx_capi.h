@@ -463,6 +463,43 @@ int grx_sim_step_frc(const grx_model* m, const struct grx_sim_params* params, co
                      int n_worlds, int nstep, int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_applied), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (4) */
 int grx_sim_applied_layout(long long* out, int cap);
+/* RAY CASTING against the worlds of the task-free stepper: mj_ray for R rays in each of N worlds, and the rangefinder rule (a ray from a site).  Not a step: the calls read
+ * body poses the caller passes in -- the xpos / xquat rows a step launch wrote -- and the model handle's geom tables, and write dist / geom.  A simulation that casts no ray
+ * calls nothing here.
+ * A ray is o + t d, t >= 0, in world coordinates; d need not be unit, the result is t (a unit d gives metres).
+ *   GEOMS   the COMPILED model's geoms, i.e. the collidable ones (visual-only geoms do not exist in a compiled model: unlike mj_ray, rays do not see them), posed as
+ *           x_body o (geom_pos, geom_quat).  A mesh geom is its CONVEX HULL, the shape the engine collides with, not the triangles of its file.  There are no geom groups.
+ *   HIT     per geom the smallest t >= 0 at which the ray meets its surface: the entry point from outside a solid, the exit point from inside.  A plane is one-sided (hit
+ *           only against its normal) and bounded by its positive half sizes.  The ray's answer is the smallest of these and that geom's id (the smaller id on an exact tie);
+ *           dist = -1.0f, geom = -1 for no hit, for a hit beyond max_dist (when max_dist > 0), and for a zero or non-finite d or a non-finite o.
+ *   FILTERS exclude_body[r] (a compiled body id, -1: none; mj_ray's bodyexclude) skips that body's geoms; include_static == 0 skips the geoms of body 0 (flg_static).
+ * grx_sim_ray: origin / direction [N,R,3].  grx_sim_ray_sites: o = site_xpos[n, ray_site[r]], d = site_xmat[n, ray_site[r]] . local_dir[r]; exclude_site_body != 0 also skips
+ * the geoms of the site's body (mjSENS_RANGEFINDER).  ray_site is read from HOST memory during the call (it is checked there); the handle keeps a device copy of the 64 most
+ * recent distinct lists, so repeating a list costs nothing; a list it has not seen is uploaded with one blocking copy.  Everything else is device memory.
+ * Every element of dist (and geom, if given) of an unmasked world is written; a masked-out world's rows keep their bits.  The hulls' face planes are derived from the handle's
+ * tables when it first serves a ray call (one blocking upload, then cached and freed with the handle); after that both calls enqueue and never wait.
+ * A mesh geom has its full hull in the compiled model only if it has a candidate pair with a convex geom (sphere, capsule, ellipsoid, cylinder, box, mesh); a model with a
+ * mesh geom that meets planes only, or nothing, is refused (-1, the message names the geom id) rather than cast through.
+ * Return -1 (grx_last_error) for a NULL model, block, pose or output pointer (and the NULL inputs of the call in question), n_worlds < 1, n_rays < 1, a ray_site outside
+ * [0, nsite), a model compiled with an origin other than 0 or with a per-world shift group. */
+typedef struct grx_sim_rays {
+  const float *xpos, *xquat;               /* [N,nbody,3] [N,nbody,4]: the body poses to cast against */
+  const float *origin, *direction;         /* [N,R,3] world frame                          grx_sim_ray */
+  const float *site_xpos, *site_xmat;      /* [N,nsite,3] [N,nsite,9]                      grx_sim_ray_sites */
+  const int* ray_site;                     /* [R] HOST memory, shared by all worlds        grx_sim_ray_sites */
+  const float* local_dir;                  /* [R,3] in the site frame, shared by all worlds grx_sim_ray_sites */
+  const int* exclude_body;                 /* [R] or NULL */
+  const unsigned char* mask;               /* [N] or NULL */
+  float* dist;                             /* [N,R] */
+  int* geom;                               /* [N,R] or NULL */
+  float max_dist;                          /* > 0: farther hits count as none */
+  int include_static;                      /* 0: skip the geoms of body 0 */
+  int exclude_site_body;                   /* grx_sim_ray_sites: != 0 skips the geoms of each ray's site's body */
+} grx_sim_rays;
+int grx_sim_ray(const grx_model* m, const grx_sim_rays* r, int n_worlds, int n_rays, void* stream);
+int grx_sim_ray_sites(const grx_model* m, const grx_sim_rays* r, int n_worlds, int n_rays, void* stream);
+/* host only: out[0] = sizeof(grx_sim_rays), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (16) */
+int grx_sim_rays_layout(long long* out, int cap);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)

@@ -25,5 +25,5 @@ for u, obj, p in procs:
     assert p.wait() == 0, u
     objs[u] = obj
 out = os.path.join(lib, f"libgrx_hip_{name}.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + list(objs.values()))
+subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + list(objs.values()) + [os.path.join(main_obj, "grx_rays.o")])   # the ray kernel's own unit
 print(out)

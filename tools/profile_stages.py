@@ -11,7 +11,7 @@ prof_so = os.path.join(ROOT, "gymnasium_robotics_amd", "_lib", "libgrx_hip_prof.
 if not os.path.exists(prof_so):
     from __graft_entry__ import HIPCC_FLAGS
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS + ["-DGRX_PROFILE", "-o", prof_so,
-                           os.path.join(ROOT, "gymnasium_robotics_amd", "csrc", "grx_kernels.hip")])
+                           os.path.join(ROOT, "gymnasium_robotics_amd", "csrc", "grx_kernels.hip"), os.path.join(ROOT, "gymnasium_robotics_amd", "csrc", "grx_rays.hip")])
 _native.LIB_PATH = prof_so
 from gymnasium_robotics_amd.envs.fetch import FetchVecEnv
 from gymnasium_robotics_amd.envs.hand import HandBlockVecEnv, HandReachVecEnv
