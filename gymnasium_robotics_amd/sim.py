@@ -14,6 +14,9 @@ of the generic engine kernel (grx_sim_step, include/grx_capi.h) on torch's curre
 Outputs are what ``MjData`` holds at that moment: after ``step`` the derived fields belong to the position / velocity stage of the LAST substep, before its integration (the
 one-substep-stale kinematics the reference's environments read after ``mj_step``), ``qpos`` / ``qvel`` are the integrated state; after ``forward`` they belong to the state as
 given.  ``site_xvelp`` / ``site_xvelr`` are the site Jacobian of that pass times the current ``qvel`` (``get_site_xvelp`` / ``get_site_xvelr``).
+``sensordata`` (the raw ``mjSENS_TOUCH`` readings) belongs to that same pass: it is made from the contact list and row forces the contact outputs report.  Under RK4 that is the
+forward pass of the FOURTH stage of the last substep, at the stage's trial state, not the first stage's at the substep's start; this has not been compared with MuJoCo's own
+``sensordata`` under RK4.
 
 The dynamics of the same pass are outputs too: ``qM`` (dense ``mj_fullM``), ``qfrc_bias`` / ``qfrc_passive`` / ``qfrc_actuator`` / ``qfrc_smooth`` / ``qfrc_constraint``,
 ``qacc_smooth`` / ``qacc``, and ``site_jacp`` / ``site_jacr``: ``mj_jacSite`` of the sites named in ``jac_sites`` (at most 16; ``sim.jac_row(name)`` is a site's row), shape

@@ -1715,7 +1715,8 @@ static double ray_cylinder(const double* p, const double* d, double r, double h)
   return best;
 }
 
-static void touch_sensors(orc_sim* s) {
+/* counted (may be NULL): [n_touch][stride] flags, 1 where contact c added its force to zone t */
+static void touch_sensors_counted(orc_sim* s, unsigned char* counted, int stride) {
   const grx_model_view* m = &s->m;
   for (int t = 0; t < m->n_touch_body; t++) {
     int b = m->touch_body[t];
@@ -1736,11 +1737,12 @@ static void touch_sensors(orc_sim* s) {
       mulMatTVec3(pl, zR, pw); mulMatTVec3(dl, zR, dw);
       double hit = m->touch_type[t] == GRX_GEOM_SPHERE ? ray_sphere(pl, dl, m->touch_size[3 * t])
                  : (m->touch_type[t] == GRX_GEOM_CYLINDER ? ray_cylinder(pl, dl, m->touch_size[3 * t], m->touch_size[3 * t + 1]) : ray_box(pl, dl, m->touch_size + 3 * t));
-      if (hit >= 0) val += fn;
+      if (hit >= 0) { val += fn; if (counted && c < stride) counted[(size_t)t * stride + c] = 1; }
     }
     s->touch[t] = val;
   }
 }
+static void touch_sensors(orc_sim* s) { touch_sensors_counted(s, NULL, 0); }
 
 /* restates mj_forward [3P] */
 void orc_forward(orc_sim* s) {
@@ -1903,6 +1905,12 @@ int orc_int(orc_sim* s, const char* name) {
 void orc_set_int(orc_sim* s, const char* name, int v) {
   if (!strcmp(name, "opt_disable_mesh_plane")) s->opt_disable_mesh_plane = v;
   if (!strcmp(name, "bad_state")) s->bad_state = v;
+}
+/* which contacts each touch zone counted in the current data: out [n_touch][maxn] flags (cleared here); the readings are recomputed to the same values */
+int orc_touch_counted(orc_sim* s, unsigned char* out, int maxn) {
+  memset(out, 0, (size_t)s->m.n_touch_body * (size_t)maxn);
+  touch_sensors_counted(s, out, maxn);
+  return s->m.n_touch_body;
 }
 /* contact dump: 16 doubles per contact: dist, pos3, normal3, geom1, geom2, dim, efc_address, includemargin */
 int orc_contacts(orc_sim* s, double* out, int maxn) {

@@ -53,6 +53,8 @@ def lib():
         L.orc_set_int.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
         L.orc_contacts.restype = ctypes.c_int
         L.orc_contacts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.orc_touch_counted.restype = ctypes.c_int
+        L.orc_touch_counted.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         _LIB = L
     return _LIB
 
@@ -104,6 +106,13 @@ class OracleSim:
         buf = np.zeros((128, 16))
         n = self._L.orc_contacts(self._h, buf.ctypes.data, 128)
         return buf[:n]
+
+    def touch_counted(self):
+        """[ntouch, ncon] bool: which contacts (in the order of contacts()) each touch zone counted in the current data"""
+        nt = len(self.touch)
+        buf = np.zeros((max(nt, 1), 128), dtype=np.uint8)
+        self._L.orc_touch_counted(self._h, buf.ctypes.data, 128)
+        return buf[:nt, :min(self.ncon, 128)].astype(bool)
 
     nefc = property(lambda self: self._L.orc_int(self._h, b"nefc"))
     ncon = property(lambda self: self._L.orc_int(self._h, b"ncon"))

@@ -102,6 +102,31 @@ class EmuSim:
         return dict(ncon=int(cnt[0]), nefc=int(cnt[1]), status=int(cnt[2]), pair=pair[:n].copy(), dist=dist[:n].copy(), pos=pos.reshape(cap, 3)[:n].copy(),
                     normal=nrm.reshape(cap, 3)[:n].copy())
 
+    def touch(self, mode=1, nstep=0, ncon_max=64):
+        """the touch readings of the loaded state (self.qpos / qvel, zero warm start) on the generic engine: mode 1 raw, 2 value > 0, 3 log(value + 1), 4 clip(value, -1, 1);
+        nstep = 0 after one forward pass, nstep > 0 after nstep physics steps (those of the last pass, as BatchedSim's sensordata).  Returns dict(sensordata [ntouch], ncon,
+        nefc, status) and, of the SAME pass, what the readings were made from: xpos [nbody, 3], xquat [nbody, 4], the engine's contact list in its own order -- pair [ncon],
+        pos [ncon, 3], normal [ncon, 3], efc_address [ncon] (-1: no rows), force [ncon] (the sum of the contact's rows of efc_force)"""
+        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+        nt = len(np.asarray(self.model.tables.get("touch_body", [])).reshape(-1))
+        out, cnt = np.zeros(max(nt, 1), np.float32), np.zeros(3, np.int32)
+        self.L.emu_touch(ctypes.c_void_p(self.h), p(self.qpos), p(self.qvel), ctypes.c_int(mode), p(out), ctypes.c_int(nstep), p(cnt))
+        ncon, nefc, nb = int(cnt[0]), int(cnt[1]), self.model.dim("nbody")
+        assert ncon <= ncon_max
+        adr, nr = self.ctx("con_efc", ncon_max, np.int32)[:ncon], self.ctx("con_nr", ncon_max, np.int32)[:ncon]
+        f = self.ctx("efc_force", max(nefc, 1))
+
+        def rows_sum(a, n):      # fp32, row by row: contact_force[..., 0] of the device's contact outputs (grx_sim_contact_force)
+            acc = np.float32(0.0)
+            for x in f[a:min(a + n, nefc)]:
+                acc = np.float32(acc + x)
+            return float(acc)
+
+        force = np.array([rows_sum(a, n) if a >= 0 else 0.0 for a, n in zip(adr, nr)])
+        return dict(sensordata=out[:nt].copy(), ncon=ncon, nefc=nefc, status=int(cnt[2]), xpos=self.ctx("xpos", 3 * nb).reshape(nb, 3), xquat=self.ctx("xquat", 4 * nb).reshape(nb, 4),
+                    pair=self.ctx("con_pair", ncon_max, np.int32)[:ncon], pos=self.ctx("con_pos", 3 * ncon_max).reshape(-1, 3)[:ncon],
+                    normal=self.ctx("con_frame", 3 * ncon_max).reshape(-1, 3)[:ncon], efc_address=adr, force=force)
+
     def kitchen_step(self, action, last_qpos, noise=None, forward_only=False):
         """FrankaKitchen env.step() (or the reset-time forward pass) of one world; last_qpos is updated in place; returns (obs[59], completed mask)"""
         p = lambda x: x.ctypes.data_as(ctypes.c_void_p)

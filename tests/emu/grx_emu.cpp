@@ -147,6 +147,33 @@ int emu_contact_list(void* h, const float* qpos, const float* qvel, int cap, int
   return n;
 }
 
+// TEST ONLY (tests/test_cpu_touch.py): the touch readings of the loaded state on the GENERIC engine, in any mode (1 raw, 2 value > 0, 3 log(value + 1), 4 clip(value, -1, 1)).
+// nstep = 0: one forward pass (mj_forward); nstep > 0: nstep physics steps with a zero warm start and zero ctrl, as grx_sim_world runs them (an Euler model one pass per
+// step, an RK4 model four), the readings being those of the LAST pass -- what grx_sim_outputs writes to sensordata.  out [ntouch]; cnt[3] = (ncon, nefc, status).
+// The working set is left as the pass left it: emu_ctx_ptr reads the contact list (con_pos, con_frame, con_pair, con_efc, con_nr), efc_force and the body poses behind it.
+void emu_touch(void* h, const float* qpos, const float* qvel, int mode, float* out, int nstep, int* cnt) {
+  Emu* e = (Emu*)h; typedef GrxEngine<GrxShapeAny> E;
+  GrxCtx* c = &e->c;
+  float mocap[8] = {0};
+  for (int k = 0; k < e->m.nmocap && k < 1; k++) { memcpy(mocap, e->m.mocap_pos0, 12); memcpy(mocap + 3, e->m.mocap_quat0, 16); }
+  std::vector<float> ws((size_t)e->m.nv + 1, 0.0f);
+  load_state(e, qpos, qvel, ws.data(), mocap);
+  if (e->m.nshift) { for (int k = 0; k < 7; k++) c->shift[k] = (k == 3) ? 1.0f : 0.0f; }
+  if (nstep <= 0) {
+    E::grx_forward_euler(&e->m, c, 0, 0);
+  } else {
+    const int rk4 = (e->m.integrator == 1), total = rk4 ? 4 * nstep : nstep;
+    for (int it = 0; it < total; it++) {
+      const int stage = it & 3;
+      if (!rk4 || stage == 0) E::grx_check_state(&e->m, c, 0);
+      E::grx_forward_euler(&e->m, c, !rk4, 0);
+      if (rk4) E::grx_rk4_after_forward(&e->m, c, stage, 0);
+    }
+  }
+  E::grx_touch_sensors(&e->m, c, out, mode, 0);
+  if (cnt) { cnt[0] = c->cnt[0] < c->maxcon ? c->cnt[0] : c->maxcon; cnt[1] = c->cnt[1]; cnt[2] = c->cnt[2]; }
+}
+
 // PointMaze env.step() of one world
 void emu_point_step(void* h, const GrxPointTask* t, float* qpos, float* qvel, float* qacc_ws, const float* action, float* obs, float* achieved,
                     int* status) {
@@ -260,7 +287,7 @@ float* emu_ctx_ptr(void* h, const char* name) {
 #define P(n) if (!strcmp(name, #n)) return (float*)c->n;
   P(qpos) P(qvel) P(xpos) P(xquat) P(xmat) P(cinert) P(crb) P(cvel) P(cdof) P(cdof_dot) P(M) P(A) P(qfrc_bias) P(qfrc_passive)
   P(qfrc_actuator) P(qfrc_smooth) P(qacc_smooth) P(qfrc_constraint) P(qacc) P(Jp) P(efc_pos) P(efc_D) P(efc_aref) P(efc_force)
-  P(con_dist) P(con_pos) P(con_frame) P(gxpos) P(gxmat) P(sxpos) P(sxmat) P(cnt) P(efc_kind) P(efc_id) P(con_pair) P(janchor) P(jaxis)
+  P(con_dist) P(con_pos) P(con_frame) P(gxpos) P(gxmat) P(sxpos) P(sxmat) P(cnt) P(efc_kind) P(efc_id) P(con_pair) P(con_efc) P(con_nr) P(janchor) P(jaxis)
 #undef P
   return nullptr;
 }
