@@ -105,11 +105,23 @@ GRX_MEM void grx_velocity(const GrxModel* m, GrxCtx* c, int lane_) {
     LV(jqa) = DI[0]; LV(jtyp) = DI[1]; LV(jda) = DI[2]; LV(ve0) = DI[3]; LV(vbb) = DI[4]; LV(vlast) = DI[5]; LV(dbody) = DI[6];
     LV(damp) = DF[0]; LV(stiff) = DF[1]; LV(sref) = DF[2];
   }
+  // The bias forces do not change when a whole tree is watched from a frame that moves with a constant linear velocity, and a free joint's three linear dofs are exactly
+  // that for the tree below it: they are left out of the spatial velocities.  Carried along, they put terms of m |omega| |v| into cdof_dot and v x* I v that cancel in
+  // qfrc_bias and cost it their fp32 rounding (a free root at 10 rad/s and 7 m/s, on the lane emulator: 3e-5 N on a bias of 11 N; 5e-6 N without them).  The generic engine
+  // only: the kernels specialised for one family keep the arithmetic their free-running rollout records (tests/golden/tolerance_table.json) were measured with -- their
+  // free bodies are slow -- and compile to what they compiled to before (nothing below exists in a fixed shape).
+  unsigned long long flinmask = 0ull;
+  if (!S::kFixed) {
+    GRX_LANEVAR_I(flin);
+    FOR_LANES { const int* DI = m->reci_dof + GRX_RDI * (lane < nv ? lane : 0); LV(flin) = (lane < nv && DI[1] == 0 && lane - DI[2] < 3) ? 1 : 0; }
+    flinmask = GRX_BALLOT(flin);
+  }
   // body spatial velocities = sum over the dof chain (parallel, no tree walk)
   FOR_LANES {
     for (int it = lane; it < 6 * GRX_NBC; it += 64) {
       int b = it / 6, k = it - 6 * b;
       unsigned mlo = (unsigned)m->dof_chainmask[2 * b], mhi = (unsigned)m->dof_chainmask[2 * b + 1];
+      if (!S::kFixed) { mlo &= ~(unsigned)flinmask; mhi &= ~(unsigned)(flinmask >> 32); }
       float s = 0;
 #pragma unroll 8
       for (int d = 0; d < nv; d++) { unsigned bit = d < 32 ? (mlo >> d) & 1u : (mhi >> (d - 32)) & 1u; s += bit ? c->cdof[6 * d + k] * c->qvel[d] : 0.0f; }
