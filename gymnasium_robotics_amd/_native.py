@@ -82,6 +82,10 @@ class SimAppliedStruct(ctypes.Structure):       # include/grx_capi.h, grx_sim_ap
     _fields_ = [(n, ctypes.c_void_p) for n in ("qfrc_applied", "xfrc_applied", "xipos")]
 
 
+class SimSensorsStruct(ctypes.Structure):       # include/grx_capi.h, grx_sim_sensors (spec, cutoff: host arrays)
+    _fields_ = [("spec", ctypes.c_void_p), ("cutoff", ctypes.c_void_p), ("nsensor", ctypes.c_int), ("ndata", ctypes.c_int), ("data", ctypes.c_void_p)]
+
+
 class SimRaysStruct(ctypes.Structure):          # include/grx_capi.h, grx_sim_rays
     _fields_ = [(n, ctypes.c_void_p) for n in ("xpos", "xquat", "origin", "direction", "site_xpos", "site_xmat", "ray_site", "local_dir", "exclude_body", "mask", "dist", "geom")] + [
         ("max_dist", ctypes.c_float), ("include_static", ctypes.c_int), ("exclude_site_body", ctypes.c_int)]
@@ -187,6 +191,8 @@ def lib():
         L.grx_sim_contacts_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
         L.grx_sim_step_frc.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
         L.grx_sim_applied_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
+        L.grx_sim_step_sns.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
+        L.grx_sim_sensors_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
         L.grx_sim_ray.argtypes = [vp, vp, ci, ci, vp]
         L.grx_sim_ray_sites.argtypes = [vp, vp, ci, ci, vp]
         L.grx_sim_rays_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
@@ -261,7 +267,7 @@ def check(rc: int):
 
 EXPORTED_SYMBOLS = [
     "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_hull_pair_records", "grx_model_dim",
-    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sim_step", "grx_sim_layout", "grx_sim_step_dyn", "grx_sim_dynamics_layout", "grx_sim_step_con", "grx_sim_contacts_layout", "grx_sim_step_frc", "grx_sim_applied_layout", "grx_sim_ray", "grx_sim_ray_sites", "grx_sim_rays_layout", "grx_sim_params_create", "grx_sim_params_destroy", "grx_sim_params_row", "grx_sim_params_commit", "grx_sim_step_params", "grx_sim_params_names", "grx_sim_params_records", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
+    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sim_step", "grx_sim_layout", "grx_sim_step_dyn", "grx_sim_dynamics_layout", "grx_sim_step_con", "grx_sim_contacts_layout", "grx_sim_step_frc", "grx_sim_applied_layout", "grx_sim_step_sns", "grx_sim_sensors_layout", "grx_sim_ray", "grx_sim_ray_sites", "grx_sim_rays_layout", "grx_sim_params_create", "grx_sim_params_destroy", "grx_sim_params_row", "grx_sim_params_commit", "grx_sim_step_params", "grx_sim_params_names", "grx_sim_params_records", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
     "grx_normstat_geometry", "grx_normstat_layout", "grx_normstat_update", "grx_normstat_refresh", "grx_normstat_apply_batch", "grx_normstat_apply_packed",
 ]
 

@@ -253,6 +253,11 @@ struct GrxCtx {
   // Like pmodel above, the members exist only in the units compiled with the macro: every other unit keeps the GrxCtx and the velocity stage it always had.
   const float *qfrc_applied, *xfrc_applied;   // [nv] [nbody,6] = (force, torque) in world coordinates at xipos (grx_applied_forces, csrc/grx_eng_velocity.h)
 #endif
+#if defined(GRX_SIM_SENSORS)
+  // the kernels with the sensor block (csrc/grx_sim_sensors.h, translation units GRX_TU_SIMSNS / GRX_TU_SIMSNSPRM; again members of those units only): the block, or null for
+  // a launch that names no sensor; this world's output row; and whether the pass that is running is the one the readings belong to (grx_sim_world)
+  const struct GrxSimSensors* sns; float* sns_row; int sns_pass;
+#endif
   int bail;    // != 0: a step kernel that hands capacity overflows to a re-run at a larger capacity stops simulating at the first overflowing substep (nothing of this run is kept)
   int soft_maxefc, soft_jpool, soft_maxcon;   // > 0 (the large-table kernel of the overflow lane): the capacities of the FAST kernel; exceeding one of them raises GRX_ST_SOFT
   int *lane_entry_count, *lane_entry_list; int lane_entry_cap, lane_world; int* lane_ready; int lane_ready_cap;   // fast kernel with an overflow lane: where a world that overflows claims its re-run (grx_lane_claim)

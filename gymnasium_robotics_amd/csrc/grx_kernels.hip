@@ -15,7 +15,9 @@
 // -DGRX_TU_SIMFRC and, with GRX_PARAM_MODEL, -DGRX_TU_SIMFRCPRM hold its kernels for the launches with applied forces (GrxSimApplied): they are compiled with
 // GRX_APPLIED_FORCES, under which GrxCtx carries the two input rows and the velocity stage ends in grx_applied_forces (csrc/grx_eng_velocity.h).  As with GRX_PARAM_MODEL nothing
 // else can share a unit with them, and the single-unit build has stubs in their place.
-#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM) && !defined(GRX_TU_SIMFRC) && !defined(GRX_TU_SIMFRCPRM)
+// -DGRX_TU_SIMSNS and, with GRX_PARAM_MODEL, -DGRX_TU_SIMSNSPRM hold its kernels for the launches that name a sensor (GrxSimSensors, csrc/grx_sim_sensors.h): compiled with
+// GRX_SIM_SENSORS and with GRX_APPLIED_FORCES, so that one kernel pair serves all five blocks.  Stubs in the single-unit build again.
+#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM) && !defined(GRX_TU_SIMFRC) && !defined(GRX_TU_SIMFRCPRM) && !defined(GRX_TU_SIMSNS) && !defined(GRX_TU_SIMSNSPRM)
 #define GRX_TU_ALL 1
 #define GRX_TU_FETCH 1
 #define GRX_TU_HAND 1
@@ -32,11 +34,14 @@
 #if GRX_TU_FETCH && !defined(GRX_NO_HULL_HINTS)
 #define GRX_HULL_HINTS 1
 #endif
-#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM || GRX_TU_SIMFRCPRM
+#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM || GRX_TU_SIMFRCPRM || GRX_TU_SIMSNSPRM
 #define GRX_PARAM_MODEL 1
 #endif
-#if GRX_TU_SIMFRC || GRX_TU_SIMFRCPRM
+#if GRX_TU_SIMFRC || GRX_TU_SIMFRCPRM || GRX_TU_SIMSNS || GRX_TU_SIMSNSPRM
 #define GRX_APPLIED_FORCES 1
+#endif
+#if GRX_TU_SIMSNS || GRX_TU_SIMSNSPRM
+#define GRX_SIM_SENSORS 1
 #endif
 #include <hip/hip_runtime.h>
 
@@ -53,6 +58,7 @@
 #include "grx_adroit_task.h"
 #include "grx_kitchen_task.h"
 #include "grx_sim_task.h"
+#include "grx_sim_sensors.h"
 #include "grx_sim_params.h"
 #include "grx_host_model.h"
 #include "grx_copy.h"
@@ -75,6 +81,8 @@ static_assert(sizeof(grx_sim_contacts) == sizeof(GrxSimContacts) && offsetof(grx
               "grx_sim_contacts must mirror GrxSimContacts");
 static_assert(sizeof(grx_sim_applied) == sizeof(GrxSimApplied) && offsetof(grx_sim_applied, xfrc_applied) == offsetof(GrxSimApplied, xfrc_applied) && offsetof(grx_sim_applied, xipos) == offsetof(GrxSimApplied, xipos),
               "grx_sim_applied must mirror GrxSimApplied");
+static_assert(sizeof(grx_sim_sensors) == sizeof(GrxSimSensors) && offsetof(grx_sim_sensors, cutoff) == offsetof(GrxSimSensors, cutoff) && offsetof(grx_sim_sensors, nsensor) == offsetof(GrxSimSensors, nsensor) &&
+              offsetof(grx_sim_sensors, ndata) == offsetof(GrxSimSensors, ndata) && offsetof(grx_sim_sensors, data) == offsetof(GrxSimSensors, data), "grx_sim_sensors must mirror GrxSimSensors");
 
 // ------------------------------------------------------------------------------------------
 // kernels
@@ -831,7 +839,11 @@ typedef int GrxSimModelArg;
 // a: the fourth block (GrxSimApplied), read only in the units compiled with GRX_APPLIED_FORCES (grx_sim_step_frc_kernel, grx_sim_lane_frc_kernel): the world's two input rows
 // go into the context, where the velocity stage of every pass finds them, and xipos leaves with the other outputs.
 template <class S, bool DYN, bool CON = false>
-__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o = nullptr, const GrxSimApplied* a = nullptr) {
+__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o = nullptr, const GrxSimApplied* a = nullptr
+#if defined(GRX_SIM_SENSORS)
+                                                   , const GrxSimSensors* sn = nullptr   // the fifth block, in the units compiled with GRX_SIM_SENSORS only (grx_sim_step_sns_kernel, grx_sim_lane_sns_kernel)
+#endif
+) {
   if (w >= n_worlds) return;
   if (b.mask && !b.mask[w]) return;
   GrxCtx c;
@@ -850,6 +862,9 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
 #if defined(GRX_APPLIED_FORCES)
   c.qfrc_applied = a->qfrc_applied ? a->qfrc_applied + (size_t)w * m.nv : nullptr;
   c.xfrc_applied = a->xfrc_applied ? a->xfrc_applied + (size_t)w * 6 * m.nbody : nullptr;
+#endif
+#if defined(GRX_SIM_SENSORS)
+  c.sns = sn; c.sns_row = sn->data + (size_t)w * sn->ndata; c.sns_pass = 0;   // (the host launches these kernels only with data set and nsensor > 0)
 #endif
   GRX_PROF_BEGIN(c, lane_);
   grx_lane_setup(b.lane, c, w, true);
@@ -927,6 +942,21 @@ __global__ void __launch_bounds__(64, 2)
 grx_sim_lane_frc_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, int n_worlds, int words, int nstep, int forward_only) {
   extern __shared__ float lds[];
   grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a); });
+}
+#endif
+#if defined(GRX_SIM_SENSORS)
+// the kernels of the launches that name a sensor (GrxSimSensors): the four other blocks ride along.  As above, the same two templates in GRX_TU_SIMSNS and GRX_TU_SIMSNSPRM.
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_step_sns_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, GrxSimSensors sn, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_sim_step_world<S, true, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a, &sn);
+}
+template <class S>
+__global__ void __launch_bounds__(64, 2)
+grx_sim_lane_sns_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, GrxSimSensors sn, int n_worlds, int words, int nstep, int forward_only) {
+  extern __shared__ float lds[];
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a, &sn); });
 }
 #endif
 #if defined(GRX_PARAM_MODEL)
@@ -1024,6 +1054,10 @@ int grx_tu_simfrc_prepare(const GrxModel* g, int bytes, int slot);
 int grx_tu_simfrc_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only);
 int grx_tu_simfrcprm_prepare(int bytes);
 int grx_tu_simfrcprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only);
+int grx_tu_simsns_prepare(const GrxModel* g, int bytes, int slot);
+int grx_tu_simsns_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only);
+int grx_tu_simsnsprm_prepare(int bytes);
+int grx_tu_simsnsprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only);
 }
 // Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
 // overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
@@ -1293,6 +1327,36 @@ extern "C" int grx_tu_simfrcprm_launch(unsigned grid, size_t lds_bytes, void* st
   return (int)hipGetLastError();
 }
 #endif
+#if GRX_TU_SIMSNS
+// ... and those that name a sensor
+extern "C" int grx_tu_simsns_prepare(const GrxModel* g, int bytes, int slot) {
+  GRX_LDS(grx_sim_step_sns_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_sns_kernel<GrxShapeAny>);
+  return (int)grx_upload_descriptor(g, slot);
+}
+extern "C" int grx_tu_simsns_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
+#if GRX_TU_SIMSNSPRM
+extern "C" int grx_tu_simsnsprm_prepare(int bytes) {
+  GRX_LDS(grx_sim_step_sns_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_sns_kernel<GrxShapeAny>);
+  return 0;
+}
+extern "C" int grx_tu_simsnsprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only) {
+  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
+  else hipLaunchKernelGGL(grx_sim_step_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
+  return (int)hipGetLastError();
+}
+#endif
+#if defined(GRX_TU_ALL)
+// ... nor the GRX_SIM_SENSORS kernels: a launch that names a sensor fails
+extern "C" int grx_tu_simsns_prepare(const GrxModel*, int, int) { return 0; }
+extern "C" int grx_tu_simsns_launch(unsigned, size_t, void*, int, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*, int, int, int, int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simsnsprm_prepare(int) { return (int)hipErrorNotSupported; }
+extern "C" int grx_tu_simsnsprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*, int, int, int, int) { return (int)hipErrorNotSupported; }
+#endif
 #if defined(GRX_TU_ALL)
 // ... nor the GRX_APPLIED_FORCES kernels: a model can be created (nothing to prepare), a launch with applied forces fails
 extern "C" int grx_tu_simfrc_prepare(const GrxModel*, int, int) { return 0; }
@@ -1475,6 +1539,9 @@ struct grx_model {
   mutable float* d_ray_planes = nullptr;
   mutable int32_t* d_ray_adr = nullptr;   // [2, ngeom]: first plane, number of planes
   mutable std::vector<std::pair<std::vector<int>, int*>> ray_sites;
+  // the device copies of the sensor tables grx_sim_step_sns has been given (grx_sensor_table, csrc/grx_sensors_api.h), by content: key = spec words then the cutoffs' bits;
+  // the device block holds the spec [4 n] and behind it the cutoffs [n].  Under ray_mu as well; freed with the handle.
+  mutable std::vector<std::pair<std::vector<int>, int*>> sensor_tables;
 };
 
 static thread_local std::string g_err;
@@ -1492,6 +1559,7 @@ static void grx_model_free(grx_model* m) {
   if (m->d_ray_planes) (void)hipFree(m->d_ray_planes);
   if (m->d_ray_adr) (void)hipFree(m->d_ray_adr);
   for (auto& e : m->ray_sites) (void)hipFree(e.second);
+  for (auto& e : m->sensor_tables) (void)hipFree(e.second);
   delete m;
 }
 
@@ -1527,6 +1595,7 @@ static int grx_model_create_impl(const int32_t* H, const int32_t* I, const doubl
   if ((e = grx_tu_simdyn_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the dynamics block): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_simcon_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the contact block): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_simfrc_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with applied forces): ") + hipGetErrorString((hipError_t)e));
+  if ((e = grx_tu_simsns_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with sensors): ") + hipGetErrorString((hipError_t)e));
   HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), &m->dev, sizeof(GrxModel), sizeof(GrxModel) * (size_t)m->slot, hipMemcpyHostToDevice));
   return 0;
 }
@@ -1683,7 +1752,7 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
 // con: null, or the third block (grx_sim_step_con): its own checks follow those of the first two; a launch that requests one of its outputs runs the kernels of the contact units
 // frc: null, or the fourth block (grx_sim_step_frc): a launch with one of its pointers set runs the kernels of the applied-force units, which carry every block
 static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc, const grx_sim_contacts* con = nullptr, bool need_con = false,
-                             const grx_sim_applied* frc = nullptr, bool need_frc = false) {
+                             const grx_sim_applied* frc = nullptr, bool need_frc = false, const GrxSimSensors* sns = nullptr) {
   if (!m) return fail("grx_sim_step: null model");
   if (!buf) return fail("grx_sim_step: null buffers");
   if (!buf->qpos || !buf->qvel || !buf->qacc_ws) return fail("grx_sim_step: null state buffer (qpos, qvel, qacc_ws)");
@@ -1719,7 +1788,10 @@ static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, con
   const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
   const unsigned grid = grx_step_grid(b.lane, 0, 0, n_worlds); const size_t lds_bytes = (size_t)m->words * 4 + m->lds_pad;
   int e;
-  if (applied) e = desc ? grx_tu_simfrcprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+  // sns: null, or the fifth block with the handle's device tables already in place of the caller's host tables (grx_sim_step_sns): the kernels of the sensor units carry every block
+  if (sns) e = desc ? grx_tu_simsnsprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, &a, sns, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
+                    : grx_tu_simsns_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, &a, sns, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  else if (applied) e = desc ? grx_tu_simfrcprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
                         : grx_tu_simfrc_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
   else if (contacts) e = desc ? grx_tu_simconprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
                          : grx_tu_simcon_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
@@ -1763,6 +1835,7 @@ extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, con
   return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, false, frc, true);
 }
 #include "grx_rays_api.h"
+#include "grx_sensors_api.h"
 // sizeof(grx_sim_applied) and the byte offset of every member, in declaration order: what _native.SimAppliedStruct must mirror (host only)
 extern "C" int grx_sim_applied_layout(long long* out, int cap) {
   const grx_sim_applied* z = nullptr;

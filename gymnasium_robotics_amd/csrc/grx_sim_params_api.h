@@ -121,7 +121,7 @@ static int grx_sim_params_create_impl(grx_sim_params* p) {
     HIP_OK(hipMemcpy(pass ? p->d_desc_large : p->d_desc, desc.data(), sizeof(GrxModel) * (size_t)N, hipMemcpyHostToDevice));
     int e;
     const int bytes = h->words * 4 + h->lds_pad;
-    if ((e = grx_tu_simprm_prepare(bytes)) != 0 || (e = grx_tu_simdynprm_prepare(bytes)) != 0 || (e = grx_tu_simconprm_prepare(bytes)) != 0 || (e = grx_tu_simfrcprm_prepare(bytes)) != 0)
+    if ((e = grx_tu_simprm_prepare(bytes)) != 0 || (e = grx_tu_simdynprm_prepare(bytes)) != 0 || (e = grx_tu_simconprm_prepare(bytes)) != 0 || (e = grx_tu_simfrcprm_prepare(bytes)) != 0 || (e = grx_tu_simsnsprm_prepare(bytes)) != 0)
       return fail(std::string("grx_sim_params_create (kernels with per-world parameters): ") + hipGetErrorString((hipError_t)e));
   }
   GrxParamCommit& a = p->args;

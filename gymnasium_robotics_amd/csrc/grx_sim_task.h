@@ -8,6 +8,9 @@
 #pragma once
 #include "grx_engine.h"
 #include "grx_fetch_task.h"   // GrxFetch<S>::grx_point_velocity: J(site) * qvel from the motion axes of the last pass
+#if defined(GRX_SIM_SENSORS)
+#include "grx_sim_sensors.h"  // the fifth optional block (GrxSimSensors), only in the units compiled with GRX_SIM_SENSORS: every other unit compiles the lines it always compiled
+#endif
 
 struct GrxSimBuffers {
   float *qpos, *qvel, *qacc_ws;           // [N,nq] [N,nv] [N,nv]
@@ -169,7 +172,14 @@ struct GrxSim {
         }
       }
     }
+#if defined(GRX_SIM_SENSORS)
+    // the sensor block's two phases stand around the solve of the pass the readings belong to (csrc/grx_sim_sensors.h)
+    if (c->sns_pass) GrxSns<S>::grx_sim_sensors_p1(m, c, c->sns, c->sns_row, lane_);
+#endif
     E::grx_solve_integrate(m, c, do_euler, lane_);
+#if defined(GRX_SIM_SENSORS)
+    if (c->sns_pass) GrxSns<S>::grx_sim_sensors_p2(m, c, c->sns, c->sns_row, lane_);
+#endif
   }
   // nstep x mj_step with ctrl held (GrxPoint::grx_point_sim_world with agent = 1 and no task: Euler models one pass per substep, RK4 models four), or one mj_forward.
   // A launch with an entry list (c->bail) stops at the first pass that exceeds a table: the world's re-run on the large tables is booked and nothing of this run is kept.
@@ -179,6 +189,9 @@ struct GrxSim {
   GRX_MEM void grx_sim_world(const GrxModel* m, GrxCtx* c, int nstep, int forward_only, const GrxSimDynamics* d, const GrxSimContacts* o, int& crow, int& ckey, size_t w, int lane_) {
     const int p1 = CON || (DYN && ((d->qfrc_bias != nullptr) | (d->qfrc_passive != nullptr) | (d->qfrc_actuator != nullptr)));   // wave-uniform: kernel arguments
     if (forward_only) {
+#if defined(GRX_SIM_SENSORS)
+      c->sns_pass = c->sns != nullptr;
+#endif
       if (p1) grx_sim_forward_p1<CON>(m, c, 0, d, o, crow, ckey, w, lane_);
       else E::grx_forward_euler(m, c, 0, lane_);
       if (c->bail) grx_lane_claim(c, lane_);
@@ -189,7 +202,15 @@ struct GrxSim {
     for (int it = 0; it < total; it++) {
       const int stage = it & 3;
       if (!rk4 || stage == 0) E::grx_check_state(m, c, lane_);
+#if defined(GRX_SIM_SENSORS)
+      // sensordata belongs to the pass mj_step runs with sensors: the substep's own forward pass.  Euler: the last substep's only pass (the one the other outputs come from).
+      // RK4: the FIRST stage's pass of the last substep -- mj_RungeKutta's further stages skip the sensors -- so that pass goes through grx_sim_forward_p1 as well; what it
+      // writes of the other blocks there is written again by the fourth stage's pass.
+      c->sns_pass = c->sns != nullptr && it == (rk4 ? total - 4 : total - 1);
+      if ((p1 && it == total - 1) || c->sns_pass) grx_sim_forward_p1<CON>(m, c, !rk4, d, o, crow, ckey, w, lane_);
+#else
       if (p1 && it == total - 1) grx_sim_forward_p1<CON>(m, c, !rk4, d, o, crow, ckey, w, lane_);
+#endif
       else E::grx_forward_euler(m, c, !rk4, lane_);
       if (c->bail && grx_lane_claim(c, lane_)) break;
       if (rk4) E::grx_rk4_after_forward(m, c, stage, lane_);

@@ -78,6 +78,22 @@ def _bool(s, default=None):
     return s.strip().lower() == "true"
 
 
+_SENSOR_DIM = {**{t: 3 for t in ("accelerometer", "velocimeter", "gyro", "force", "torque", "magnetometer", "framepos", "framexaxis", "frameyaxis", "framezaxis", "framelinvel",
+                                 "frameangvel", "framelinacc", "frameangacc", "subtreecom", "subtreelinvel", "subtreeangmom", "ballangvel")}, "framequat": 4, "ballquat": 4}
+
+
+def _sensor_record(e):
+    """one child of <sensor> as info["sensor"] holds it: type (the tag), objtype / objname (what it is attached to: the `site`, `joint`, `actuator`, `tendon` or `body`
+    attribute, or a frame sensor's own objtype / objname), reftype (None unless the sensor names a reference frame), cutoff and dim (mjSENS_*: 1 unless listed; `dim` of <user>)"""
+    a = e.attrib
+    objtype, objname = a.get("objtype"), a.get("objname")
+    for kind in ("site", "joint", "actuator", "tendon", "body"):
+        if objtype is None and kind in a:
+            objtype, objname = kind, a[kind]
+    reftype = a.get("reftype") or ("unnamed" if a.get("refname") else None)
+    return dict(type=e.tag, objtype=objtype, objname=objname, reftype=reftype, cutoff=float(a.get("cutoff", 0.0)), dim=int(a.get("dim", _SENSOR_DIM.get(e.tag, 1))))
+
+
 # ----------------------------------------------------------------------------
 # XML loading with <include> expansion
 # ----------------------------------------------------------------------------
@@ -1238,6 +1254,11 @@ class _Lowering:
         finders = [e for sec in c.root.findall("sensor") for e in sec.findall("rangefinder")]
         names["rangefinder"] = {e.attrib.get("name") or f"_rangefinder{k}": k for k, e in enumerate(finders)}
         info["rangefinder"] = [dict(site=e.attrib.get("site"), cutoff=float(e.attrib.get("cutoff", 0.0))) for e in finders]
+        # every child of every <sensor> section, in document order: bookkeeping only as well (names["sensor"]: name -> row, info["sensor"]: one dict per row).  Nothing is
+        # packed; BatchedSim(sensors=...) decides which rows the engine serves and is where the others are refused by name (sim.py)
+        sensors = [e for sec in c.root.findall("sensor") for e in sec if isinstance(e.tag, str)]
+        names["sensor"] = {e.attrib.get("name") or f"_sensor{k}": k for k, e in enumerate(sensors)}
+        info["sensor"] = [_sensor_record(e) for e in sensors]
 
         # ---- collision candidate pairs
         excludes = set()

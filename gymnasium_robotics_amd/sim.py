@@ -66,6 +66,26 @@ terms.  Naming one routes the launch through grx_sim_step_frc.  Non-finite appli
     sim.xfrc_applied[:, sim.body_id("torso"), :3] = 50.0 * torch.randn(4096, 3, device="cuda")     # a shove through the torso's centre of mass
     sim.step(nstep=20)
 
+SENSORS (``MjData.sensordata`` for the MJCF's ``<sensor>`` children): ``sensors`` names sensors of the MJCF, or is ``"all"`` -- every sensor of a served type, in MJCF order, with
+``sim.sensors_unserved`` a dict name -> reason for the rest.  ``sim.sensor_data`` is [N, ndata] float32, ``sim.sensor(name)`` the [N, dim] view of one sensor, ``sim.sensor_adr(name)``
+its ``(adr, dim)``.  Served: ``jointpos`` / ``jointvel`` (hinge and slide joints), ``actuatorpos`` / ``actuatorvel`` (gear times the joint's), ``actuatorfrc`` (the actuator's scalar
+force before the gear), ``jointactuatorfrc``, and on a site or an ``xbody`` of the compiled model ``framepos``, ``framequat``, ``framexaxis`` / ``yaxis`` / ``zaxis``, ``framelinvel``,
+``frameangvel``, ``framelinacc``, ``frameangacc``; on a site ``velocimeter``, ``gyro``, ``accelerometer``.  With p, R the object's position and rotation and Jp, Jr the Jacobians of
+the material point p: u = Jp qvel, omega = Jr qvel, c = Jp qacc + (d/dt Jp) qvel, alpha = Jr qacc + (d/dt Jr) qvel; velocimeter = R'u, gyro = R'omega, framelinacc = c - g,
+accelerometer = R'(c - g), frameangacc = alpha.  ``- g`` is MuJoCo's convention that the world body accelerates with ``-gravity`` (an accelerometer at rest reads +9.81 along world
+z); it is the DEFINITION of ``framelinacc`` here as well.  A world that names ``gravity`` among ``model_params`` reads its own committed row.  A positive ``cutoff`` clamps a reading to
+[-cutoff, cutoff] (not the quaternion and axis types); ``noise`` is ignored.  Refused by name, with the reason: ``touch`` (``outputs=("sensordata",)`` with ``touch_filter``),
+``rangefinder`` (``sim.rangefinder()``), ``force`` / ``torque`` (they need cfrc_int / cfrc_ext, which the engine does not form), frame sensors on a ``body`` (the inertial frame),
+``geom`` or ``camera``, any ``reftype``, every other type, and an ``xbody`` the compiler merged into its parent or a site ``keep_sites`` dropped.
+WHICH PASS: all readings belong to ONE forward pass, with that pass's own qvel and qacc.  After ``forward()``: that pass.  After ``step(n)`` of an Euler model: the last substep's pass,
+before its integration.  Of an RK4 model: the FIRST stage's pass of the last substep -- ``mj_step`` runs ``mj_forward`` with sensors, then ``mj_RungeKutta`` with the sensors skipped --
+which differs on purpose from the fourth-stage pass of the other outputs.  Either way the readings after ``step(n)`` are those of ``forward()`` at the state ``step(n - 1)`` left.
+Sensors are not state: ``reset()``'s ``forward()`` refreshes them, ``get_state`` / ``set_state`` do not carry them.  Naming one routes the launch through grx_sim_step_sns.
+
+    sim = grx.BatchedSim("quadruped.xml", 4096, sensors=("imu_acc", "imu_gyro", "imu_quat", "hip_pos", "hip_vel"))
+    sim.step(nstep=5)
+    obs = torch.cat([sim.sensor_data, sim.ctrl], dim=1)                                            # or sim.sensor("imu_acc"): [N, 3]
+
 RAYS (``mj_ray``, rangefinders, lidar): ``sim.ray(origin, direction)`` casts R rays per world -- ``origin`` / ``direction`` [N, R, 3] (or [R, 3]) in world coordinates, ``direction``
 of any length -- and returns ``(dist [N, R] float32, geom [N, R] int32)``: the ray parameter of the nearest hit (metres for a unit direction) and the geom hit, -1.0 / -1 for none.
 ``sim.ray_sites(sites, local_dir)`` starts the rays at sites and skips each site's own body; ``sim.rangefinder()`` is [N, n_rangefinder], one reading per ``<rangefinder>`` of the MJCF
@@ -81,7 +101,7 @@ it rather than cast through it.  The calls run a kernel of their own (grx_sim_ra
     dist, geom = sim.ray_sites("lidar", fan, max_dist=10.0)                                        # [N, 64]
 
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-cfrc_ext, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, cameras.
+force / torque sensors (cfrc_int, cfrc_ext), sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, cameras.
 """
 import ctypes
 
@@ -101,6 +121,12 @@ _CONTACT_WIDTH = dict(contact_geom=(2,), contact_dim=(), contact_efc_address=(),
 _INT_TENSORS = ("ncon", "nefc", "contact_geom", "contact_dim", "contact_efc_address")
 APPLIED = ("qfrc_applied", "xfrc_applied", "xipos")      # grx_sim_applied, in its order: two inputs the caller writes, one output
 APPLIED_INPUTS = ("qfrc_applied", "xfrc_applied")
+# grx_sim_sensors: the type and object numbers of csrc/grx_sim_sensors.h, in its order
+SENSOR_TYPES = ("jointpos", "jointvel", "actuatorpos", "actuatorvel", "actuatorfrc", "jointactuatorfrc", "framepos", "framequat", "framexaxis", "frameyaxis", "framezaxis",
+                "framelinvel", "frameangvel", "velocimeter", "gyro", "framelinacc", "frameangacc", "accelerometer")
+SENSOR_OBJECTS = ("joint", "actuator", "site", "xbody")
+_SENSOR_JOINT, _SENSOR_ACTUATOR, _SENSOR_SITE_ONLY = ("jointpos", "jointvel", "jointactuatorfrc"), ("actuatorpos", "actuatorvel", "actuatorfrc"), ("velocimeter", "gyro", "accelerometer")
+_SENSOR_NO_CUTOFF = ("framequat", "framexaxis", "frameyaxis", "framezaxis")
 MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
 
 
@@ -117,14 +143,14 @@ class _Params:
 
 
 class BatchedSim:
-    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=(), applied=()):
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=(), applied=(), sensors=()):
         """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
         default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
         again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
         CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
         keep_sites, mutate, ...).  jac_sites: the names of the sites whose Jacobians site_jacp / site_jacr hold, in the order of their rows (None: every site of the model, which must
         then have at most 16).  model_params: the tables that are per world, any of sim.PARAMS (module docstring).  contacts: the members of the contact list to allocate and write, any of sim.CONTACTS
-        (module docstring).  applied: the applied-force inputs and xipos, any of sim.APPLIED (module docstring).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        (module docstring).  applied: the applied-force inputs and xipos, any of sim.APPLIED (module docstring).  sensors: names of <sensor> children of the MJCF, or "all" (module docstring, SENSORS).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
         if int(num_worlds) < 1:
             raise ValueError("num_worlds must be at least 1")
         if overflow not in ("rerun", "flag"):
@@ -201,8 +227,9 @@ class BatchedSim:
             self._jac_ids = tuple(self.site_id(name) for name in self.jac_sites)
         if wants_jac and not self._jac_ids:
             raise ValueError("site_jacp / site_jacr need at least one site (the model has none, or jac_sites is empty)")
+        self._resolve_sensors(sensors)
         self._t = None      # the device tensors, made on first use
-        self._h = self._h_big = self.lane = self._p = self._frc = None
+        self._h = self._h_big = self.lane = self._p = self._frc = self._sns = None
 
     # ------------------------------------------------------------------ names (CompiledModel.names / tables): no device needed
     def _lookup(self, kind, name):
@@ -237,6 +264,89 @@ class BatchedSim:
         if name not in self.jac_sites:
             raise KeyError(f"site {name!r} is not among jac_sites {self.jac_sites}")
         return self.jac_sites.index(name)
+
+    # ------------------------------------------------------------------ sensors (module docstring, SENSORS): no device needed
+    def _sensor_serve(self, name, rec):
+        """(type, objtype, objid) of csrc/grx_sim_sensors.h for the row `rec` of model.info["sensor"], or ValueError with the reason it is not served"""
+        m, kind, objtype, objname = self.model, rec["type"], rec["objtype"], rec["objname"]
+        who = f"sensor {name!r} (<{kind}>)"
+        if kind == "touch":
+            raise ValueError(f"{who}: touch readings are served by outputs=('sensordata',) with compile_kwargs=dict(touch_filter=...)")
+        if kind == "rangefinder":
+            raise ValueError(f"{who}: rangefinders are served by sim.rangefinder()")
+        if kind in ("force", "torque"):
+            raise ValueError(f"{who}: force and torque sensors need cfrc_int / cfrc_ext, which the engine does not form")
+        if kind not in SENSOR_TYPES:
+            raise ValueError(f"{who}: this type is not served; the served types are {SENSOR_TYPES}")
+        if rec["reftype"] is not None:
+            raise ValueError(f"{who}: a reference frame (reftype / refname) is not served; the reading would be in world coordinates")
+        if kind in _SENSOR_JOINT:
+            if objtype != "joint" or objname not in m.names["joint"]:
+                raise ValueError(f"{who}: no joint named {objname!r} in the compiled model")
+            j = int(m.names["joint"][objname])
+            if int(np.asarray(m.tables["jnt_type"]).reshape(-1)[j]) < 2:
+                raise ValueError(f"{who}: joint {objname!r} is a free or ball joint; the joint sensors read hinge and slide joints only")
+            return SENSOR_TYPES.index(kind), SENSOR_OBJECTS.index("joint"), j
+        if kind in _SENSOR_ACTUATOR:
+            if objtype != "actuator" or objname not in m.names["actuator"]:
+                raise ValueError(f"{who}: no actuator named {objname!r} in the compiled model")
+            return SENSOR_TYPES.index(kind), SENSOR_OBJECTS.index("actuator"), int(m.names["actuator"][objname])
+        if kind in _SENSOR_SITE_ONLY and objtype != "site":
+            raise ValueError(f"{who}: this type is attached to a site")
+        if objtype in ("body", "geom", "camera"):
+            what = "the inertial frame of a body" if objtype == "body" else f"a {objtype}"
+            raise ValueError(f"{who}: frame sensors on {what} are not served; use objtype='xbody' or a site at that frame")
+        if objtype == "site":
+            if objname not in m.names["site"]:
+                raise ValueError(f"{who}: site {objname!r} is not among the compiled model's sites (keep_sites dropped it: compile_kwargs=dict(keep_sites=...))")
+            return SENSOR_TYPES.index(kind), SENSOR_OBJECTS.index("site"), int(m.names["site"][objname])
+        if objtype == "xbody":
+            if objname not in m.names["body"]:
+                raise ValueError(f"{who}: xbody {objname!r} has no row in the compiled model (the compiler merged it into its parent, or it does not exist): attach the sensor "
+                                 "to a site on it -- sites keep their identity (compile_kwargs=dict(keep_sites=...) must keep it)")
+            return SENSOR_TYPES.index(kind), SENSOR_OBJECTS.index("xbody"), int(m.names["body"][objname])
+        raise ValueError(f"{who}: object type {objtype!r} is not served; frame sensors read a site or an xbody")
+
+    def _resolve_sensors(self, sensors):
+        rows, table = self.model.info.get("sensor", ()), self.model.names.get("sensor", {})
+        self.sensors_unserved = {}
+        if isinstance(sensors, str) and sensors == "all":
+            picked = []
+            for name, k in sorted(table.items(), key=lambda kv: kv[1]):
+                try:
+                    picked.append((name, self._sensor_serve(name, rows[k])))
+                except ValueError as e:
+                    self.sensors_unserved[name] = str(e)
+        else:
+            if isinstance(sensors, str):
+                sensors = (sensors,)
+            sensors = tuple(sensors)
+            if len(set(sensors)) != len(sensors):
+                raise ValueError(f"sensors names a sensor twice: {sensors}")
+            unknown = [n for n in sensors if n not in table]
+            if unknown:
+                raise ValueError(f"no sensor(s) named {unknown} in the MJCF; its sensors are {sorted(table, key=table.get)}")
+            picked = [(name, self._sensor_serve(name, rows[table[name]])) for name in sensors]
+        self.sensors = tuple(name for name, _ in picked)
+        self._sensor_spec, self._sensor_cut, self._sensor_adr, adr = [], [], {}, 0
+        for name, (kind, obj, oid) in picked:
+            dim = 4 if SENSOR_TYPES[kind] == "framequat" else (3 if kind >= SENSOR_TYPES.index("framepos") else 1)
+            self._sensor_spec.append((kind, obj, oid, adr))
+            self._sensor_cut.append(0.0 if SENSOR_TYPES[kind] in _SENSOR_NO_CUTOFF else max(float(rows[table[name]]["cutoff"]), 0.0))
+            self._sensor_adr[name] = (adr, dim)
+            adr += dim
+        self.nsensordata = adr
+
+    def sensor_adr(self, name):
+        """(adr, dim): the columns [adr, adr + dim) of sensor_data that hold the sensor `name`"""
+        if name not in self._sensor_adr:
+            raise KeyError(f"sensor {name!r} is not among the requested sensors {self.sensors}: BatchedSim(..., sensors=...)")
+        return self._sensor_adr[name]
+
+    def sensor(self, name):
+        """[N, dim] view of sensor_data: the reading of the sensor `name`"""
+        adr, dim = self.sensor_adr(name)
+        return self.sensor_data[:, adr:adr + dim]
 
     def actuator_id(self, name):
         return self._lookup("actuator", name)
@@ -318,6 +428,11 @@ class BatchedSim:
             self._con = _native.SimContactsStruct(ccap=self.contact_capacity, **{k[len("contact_"):]: t[k].data_ptr() for k in self.contacts})
         if self.applied:      # the fourth block, again one for both launches: a re-run world takes its applied rows along
             self._frc = _native.SimAppliedStruct(**{k: t[k].data_ptr() for k in self.applied})
+        if self.sensors:      # the fifth block, one for both launches; the two host tables live as long as the simulation (each handle keeps a device copy, by content)
+            t["sensor_data"] = torch.zeros((self.num_worlds, self.nsensordata), dtype=torch.float32, device=self.device)
+            self._sns_host = (np.ascontiguousarray(self._sensor_spec, dtype=np.int32).reshape(-1, 4), np.ascontiguousarray(self._sensor_cut, dtype=np.float32))
+            self._sns = _native.SimSensorsStruct(spec=self._sns_host[0].ctypes.data, cutoff=self._sns_host[1].ctypes.data, nsensor=len(self.sensors), ndata=self.nsensordata,
+                                                 data=t["sensor_data"].data_ptr())
         if self.overflow == "rerun":
             self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
             if self._h_big is not None:
@@ -349,6 +464,10 @@ class BatchedSim:
             return self.__dict__[name]
         if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()) or name in self.__dict__.get("contacts", ()) or name in self.__dict__.get("applied", ()):
             return self._ensure()[name]
+        if name == "sensor_data":
+            if not self.__dict__.get("sensors"):
+                raise AttributeError("no sensor was requested: BatchedSim(..., sensors=...), names of the MJCF's <sensor> children or 'all'")
+            return self._ensure()["sensor_data"]
         if name in ("params", "params_invalid"):
             if not self.__dict__.get("param_names"):
                 raise AttributeError(f"no per-world parameters were named: BatchedSim(..., model_params=...), any of {PARAMS}")
@@ -396,7 +515,13 @@ class BatchedSim:
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            if self._frc is not None:      # the kernels with applied forces; they serve every other block and the per-world parameters as well
+            if self._sns is not None:      # the kernels with the sensor block; they serve every other block and the per-world parameters as well
+                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
+                con = None if self._con is None else ctypes.byref(self._con)
+                frc = None if self._frc is None else ctypes.byref(self._frc)
+                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_sns(h, self._p, ctypes.byref(b), dyn, con, frc, ctypes.byref(self._sns), self.num_worlds, int(nstep),
+                                                                                  int(forward_only), stream_ptr(self.device))))
+            elif self._frc is not None:      # the kernels with applied forces; they serve every other block and the per-world parameters as well
                 dyn = None if self._dyn is None else ctypes.byref(self._dyn)
                 con = None if self._con is None else ctypes.byref(self._con)
                 go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_frc(h, self._p, ctypes.byref(b), dyn, con, ctypes.byref(self._frc), self.num_worlds, int(nstep),

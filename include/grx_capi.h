@@ -463,6 +463,39 @@ int grx_sim_step_frc(const grx_model* m, const struct grx_sim_params* params, co
                      int n_worlds, int nstep, int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_applied), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (4) */
 int grx_sim_applied_layout(long long* out, int cap);
+/* SENSORS, the fifth optional block of the task-free stepper: MjData.sensordata for the MJCF's <sensor> children other than touch (grx_sim_buffers.sensordata) and
+ * rangefinder (grx_sim_ray_sites).  The caller describes the sensors in two HOST tables, in the order of the rows of data:
+ *   spec   [nsensor,4] int   = type, objtype, objid, adr     adr: the first column of the sensor in a world's row; the rows tile [0, ndata) in sensor order
+ *   cutoff [nsensor]  float  > 0 clamps every element of the reading to [-cutoff, cutoff]; the quaternion and axis types ignore it
+ *   type    0 jointpos 1 jointvel 2 actuatorpos 3 actuatorvel 4 actuatorfrc 5 jointactuatorfrc 6 framepos 7 framequat 8 framexaxis 9 frameyaxis 10 framezaxis 11 framelinvel
+ *           12 frameangvel 13 velocimeter 14 gyro 15 framelinacc 16 frameangacc 17 accelerometer          dim: 4 for framequat, 3 from framepos on, else 1
+ *   objtype 0 joint (hinge or slide; types 0 1 5)   1 actuator (types 2 3 4)   2 site (types 6 ... 17)   3 xbody = a body of the COMPILED model (types 6 ... 12, 15, 16)
+ * VALUES, all of one forward pass with its own qpos, qvel and qacc; p, R: the object's position and rotation (local -> world), Jp, Jr the Jacobians of the material point p:
+ *   omega = Jr qvel   u = Jp qvel   alpha = Jr qacc + (d/dt Jr) qvel   c = Jp qacc + (d/dt Jp) qvel  (the classical acceleration of the material point)
+ *   jointpos qpos[adr], jointvel qvel[dof]; actuatorpos / actuatorvel gear * those of the actuator's joint; actuatorfrc gain * clamp(ctrl) + bias clamped to forcerange (the
+ *   force BEFORE the gear); jointactuatorfrc qfrc_actuator[dof]; framepos p; framequat the unit quaternion of R; frame?axis a column of R; framelinvel u; frameangvel omega;
+ *   velocimeter R'u; gyro R'omega; framelinacc c - gravity; frameangacc alpha; accelerometer R'(c - gravity).
+ *   "- gravity" is MuJoCo's convention that the world body accelerates with -gravity: an accelerometer at rest reads +9.81 along world z.  This is the DEFINITION of framelinacc
+ *   here too.  With per-world parameters, gravity is the world's committed row.  Sensor noise does not exist.
+ * WHICH PASS: after a forward launch, that pass.  After nstep substeps of an Euler model, the last substep's pass, before its integration -- the pass of the other outputs.  Of an
+ *   RK4 model, the FIRST stage's pass of the last substep: mj_step runs mj_forward with sensors and then mj_RungeKutta with the sensors skipped.  This differs on purpose from the
+ *   fourth-stage pass the other outputs (and grx_sim_buffers.sensordata) belong to.  Either way: the readings after step(n) are those of a forward launch at the state step(n - 1) left.
+ * The tables are checked on the host (a known type, a type / object combination from the list, an object id in range, adr as described) and copied to the device once per
+ * distinct content: the handle keeps the copy, every later launch with the same tables only enqueues.  Every element of a world's row is written by the launch; masked-out
+ * worlds keep theirs bit for bit; the re-run call of the overflow lane takes the same block.
+ * grx_sim_step_sns: params, dyn, con and frc may be NULL and mean what they mean to grx_sim_step_frc.  data == NULL or nsensor == 0 launches exactly what grx_sim_step_frc
+ * launches for the other arguments; otherwise kernels of their own run, which carry every block.  Returns -1 (grx_last_error) for everything those calls refuse, for
+ * sns == NULL and for a table that fails a check. */
+typedef struct grx_sim_sensors {
+  const int* spec;       /* HOST [nsensor,4] */
+  const float* cutoff;   /* HOST [nsensor] */
+  int nsensor, ndata;
+  float* data;           /* device [N,ndata] */
+} grx_sim_sensors;
+int grx_sim_step_sns(const grx_model* m, const struct grx_sim_params* params, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc,
+                     const grx_sim_sensors* sns, int n_worlds, int nstep, int forward_only, void* stream);
+/* host only: out[0] = sizeof(grx_sim_sensors), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (6) */
+int grx_sim_sensors_layout(long long* out, int cap);
 /* RAY CASTING against the worlds of the task-free stepper: mj_ray for R rays in each of N worlds, and the rangefinder rule (a ray from a site).  Not a step: the calls read
  * body poses the caller passes in -- the xpos / xquat rows a step launch wrote -- and the model handle's geom tables, and write dist / geom.  A simulation that casts no ray
  * calls nothing here.
