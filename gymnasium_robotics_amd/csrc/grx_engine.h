@@ -245,7 +245,7 @@ struct GrxCtx {
   int mslot;   // slot of this world's model in g_grx_models (GPU build)
 #if defined(GRX_PARAM_MODEL)
   const GrxModel* pmodel;   // the kernels with per-world model parameters (csrc/grx_sim_params.h): this world's own descriptor in HBM, which GRX_FRESH_MODEL resolves to instead of the slot
-  // NOTE: with this member GrxCtx (like GrxSimModelArg and the signature of grx_sim_step_world in grx_kernels.hip) differs between the units linked into one library.  That holds
+  // NOTE: with this member GrxCtx (like GrxSimModelArg, the first argument of the sim kernels in grx_kernels.hip) differs between the units linked into one library.  That holds
   // only because GrxCtx is DEVICE-ONLY and every unit is a code object of its own: no host code, and nothing in the lane emulator, may pass a GrxCtx between units.
 #endif
 #if defined(GRX_APPLIED_FORCES)

@@ -4,19 +4,17 @@
 // world's whole working set (grx_ctx_words), so the 20 fused substeps of an env.step() read
 // and write HBM exactly once.  Worlds are independent: no inter-workgroup communication.
 //
-// Build: this ONE source is compiled either as a single translation unit (no GRX_TU_* macro: the profiling variant) or, for the product
-// library, eight times in parallel with -DGRX_TU_FETCH / -DGRX_TU_HAND / -DGRX_TU_POINT / -DGRX_TU_ADROIT / -DGRX_TU_KITCHEN / -DGRX_TU_SIM / -DGRX_TU_SIMDYN / -DGRX_TU_API (one family of kernel
-// instantiations each; __graft_entry__.build links the objects).  Every unit has its own copy of the constant-memory model descriptors
-// (g_grx_models is static): grx_model_create uploads a descriptor to each of them through grx_tu_*_prepare.
-// Two more units, -DGRX_TU_SIMPRM / -DGRX_TU_SIMDYNPRM, hold the task-free stepper's kernels for worlds with per-world model parameters (csrc/grx_sim_params.h) and the commit
-// kernels: they are compiled with GRX_PARAM_MODEL, under which every stage takes its model from the world's own descriptor in HBM (GRX_FRESH_MODEL, csrc/grx_engine.h), so
-// nothing else can share a unit with them and the single-unit build has stubs in their place (GRX_TU_ALL).
-// -DGRX_TU_SIMCON and, with GRX_PARAM_MODEL, -DGRX_TU_SIMCONPRM hold the stepper's kernels for the launches that request a contact output (GrxSimContacts, csrc/grx_sim_task.h).
-// -DGRX_TU_SIMFRC and, with GRX_PARAM_MODEL, -DGRX_TU_SIMFRCPRM hold its kernels for the launches with applied forces (GrxSimApplied): they are compiled with
-// GRX_APPLIED_FORCES, under which GrxCtx carries the two input rows and the velocity stage ends in grx_applied_forces (csrc/grx_eng_velocity.h).  As with GRX_PARAM_MODEL nothing
-// else can share a unit with them, and the single-unit build has stubs in their place.
-// -DGRX_TU_SIMSNS and, with GRX_PARAM_MODEL, -DGRX_TU_SIMSNSPRM hold its kernels for the launches that name a sensor (GrxSimSensors, csrc/grx_sim_sensors.h): compiled with
-// GRX_SIM_SENSORS and with GRX_APPLIED_FORCES, so that one kernel pair serves all five blocks.  Stubs in the single-unit build again.
+// Build: this ONE source is compiled either as a single translation unit (no GRX_TU_* macro: the profiling variant) or, for the product library, once per unit in parallel,
+// each with one -DGRX_TU_<UNIT> (__graft_entry__.HIP_UNITS; build() links the objects).  A unit is one family of kernel instantiations with the host code that launches them:
+// -DGRX_TU_FETCH / _HAND / _POINT / _ADROIT / _KITCHEN hold the task families, -DGRX_TU_API the C ABI, and the task-free stepper has one unit per row of GRX_SIM_UNITS
+// (the table above grx_sim_step_world, which says what each of them carries).  Every unit has its own copy of the constant-memory model descriptors (g_grx_models is static):
+// grx_model_create uploads a descriptor to each of them through grx_tu_*_prepare.
+// Three macros change what a whole unit compiles, so the units that set one can share with nothing else, and the single-unit build has stubs in their place:
+//   GRX_PARAM_MODEL      the rows with PRM (worlds with per-world model parameters, csrc/grx_sim_params.h): every stage takes its model from the world's own descriptor in HBM
+//                        (GRX_FRESH_MODEL, csrc/grx_engine.h).  The first of them, -DGRX_TU_SIMPRM, also holds the commit kernels.
+//   GRX_APPLIED_FORCES   the rows that carry GrxSimApplied: GrxCtx has the two input rows and the velocity stage ends in grx_applied_forces (csrc/grx_eng_velocity.h)
+//   GRX_SIM_SENSORS      the rows that carry GrxSimSensors (csrc/grx_sim_sensors.h): GrxCtx has the block and the stages evaluate the sensors of their pass; with
+//                        GRX_APPLIED_FORCES, so that one kernel pair serves all five blocks
 #if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM) && !defined(GRX_TU_SIMFRC) && !defined(GRX_TU_SIMFRCPRM) && !defined(GRX_TU_SIMSNS) && !defined(GRX_TU_SIMSNSPRM)
 #define GRX_TU_ALL 1
 #define GRX_TU_FETCH 1
@@ -24,10 +22,7 @@
 #define GRX_TU_POINT 1
 #define GRX_TU_ADROIT 1
 #define GRX_TU_KITCHEN 1
-#define GRX_TU_SIM 1
-#define GRX_TU_SIMDYN 1
-#define GRX_TU_SIMCON 1
-#define GRX_TU_API 1
+#define GRX_TU_API 1   // (and the sim units whose row of GRX_SIM_UNITS says SINGLE)
 #endif
 // The guessed support vertices of persistent hull contacts (grx_engine.h, grx_mesh_support) need a per-world HBM row, which only the Fetch buffers carry (hullcache): the
 // code is compiled into the Fetch kernels only -- in the hand / kitchen kernels it would be dead weight in a register-starved routine (measured: -1 ... -2.5 %).
@@ -50,6 +45,8 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <tuple>
+#include <type_traits>
 
 #include "../../include/grx_capi.h"
 #include "grx_fetch_task.h"
@@ -823,9 +820,33 @@ grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_
 // The task-free stepper (include/grx_capi.h grx_sim_step, csrc/grx_sim_task.h): mj_step(nstep) or mj_forward of a caller's own model, one wavefront per world, and the MjData
 // fields of the last pass.  Overflow lane in entry mode only: a world that exceeds a table of the fast launch claims a re-run and writes NOTHING; the lane kernel below runs
 // it again from its untouched state rows on the handle with the large tables.  Forward launches claim too: their outputs are the point of the call.
-// DYN: the instance that serves the second output block (GrxSimDynamics), in kernels of its own (grx_sim_step_dyn_kernel, grx_sim_lane_dyn_kernel; translation unit GRX_TU_SIMDYN).  A launch that requests
-// none of its outputs runs the kernels without the block (d = nullptr, DYN = false): the stepper as it was before the block existed, argument list included -- the second
-// inlined copy of the forward pass costs the DYN instance 250 B of scratch per lane and took 5 % off a launch that shared a kernel with it (profiles/sim_probe_dynamics.txt).
+//
+// THE UNITS.  One stepper (grx_sim_step_world) and one kernel pair (grx_sim_step_kernel, grx_sim_lane_kernel) serve every launch; what differs between launches is which of
+// the optional blocks (csrc/grx_sim_task.h, csrc/grx_sim_sensors.h) ride in the kernels' argument list behind GrxSimBuffers, always in the order d, o, a, sn.  Each row below is
+// one translation unit that instantiates the pair for one block list -- kernels of its own, because a block costs the launches that do not ask for it: the second inlined
+// copy of the forward pass costs the DYN instance 250 B of scratch per lane and took 5 % off a launch that shared a kernel with it (profiles/sim_probe_dynamics.txt).  A
+// launch runs on the first row that carries every block it requests; a block that rides along unrequested is a block of nulls and writes nothing.
+//   X(unit, UNIT, DYN, CON, PRM, SINGLE, what, blocks...)
+//   unit / UNIT  the unit exports grx_tu_<unit>_prepare / grx_tu_<unit>_launch and is compiled with -DGRX_TU_<UNIT>
+//   DYN, CON     the instance of the stepper: with the dynamics outputs (GrxSimDynamics), with the contact outputs (GrxSimContacts)
+//   PRM          a GRX_PARAM_MODEL unit: the twin of the row above it for worlds with per-world model parameters (below)
+//   SINGLE       the single-unit build holds it (GRX_TU_ALL: one set of macros, so no unit compiled with GRX_PARAM_MODEL, GRX_APPLIED_FORCES or GRX_SIM_SENSORS); stubs stand in
+//                for the others: a model can be created, a parameter object cannot, a launch that needs one of them fails with hipErrorNotSupported
+//   what         the unit in the words of grx_model_create's failure message
+// A further block is: its struct; a row per new unit (and the unit in __graft_entry__.HIP_UNITS); its pointer in grx_sim_step_world with the lines that use it, and in
+// GRX_SIM_TAIL_BLOCKS; on the host its element of GrxSimRequest::blk, its member of GrxSimStepArgs, its bit of `need` and its place in the request's initialiser in
+// grx_sim_step_impl; an extern "C" entry that fills the arguments; and in sim.py its attribute in _SIM_BLOCKS and its entry in _SIM_ENTRIES.
+#define GRX_SIM_UNITS(X) \
+  X(sim,       SIM,       false, false, 0, 1, "sim kernels") \
+  X(simprm,    SIMPRM,    false, false, 1, 0, "sim kernels") \
+  X(simdyn,    SIMDYN,    true,  false, 0, 1, "sim kernels with the dynamics block", GrxSimDynamics) \
+  X(simdynprm, SIMDYNPRM, true,  false, 1, 0, "sim kernels with the dynamics block", GrxSimDynamics) \
+  X(simcon,    SIMCON,    true,  true,  0, 1, "sim kernels with the contact block", GrxSimDynamics, GrxSimContacts) \
+  X(simconprm, SIMCONPRM, true,  true,  1, 0, "sim kernels with the contact block", GrxSimDynamics, GrxSimContacts) \
+  X(simfrc,    SIMFRC,    true,  true,  0, 0, "sim kernels with applied forces", GrxSimDynamics, GrxSimContacts, GrxSimApplied) \
+  X(simfrcprm, SIMFRCPRM, true,  true,  1, 0, "sim kernels with applied forces", GrxSimDynamics, GrxSimContacts, GrxSimApplied) \
+  X(simsns,    SIMSNS,    true,  true,  0, 0, "sim kernels with sensors", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors) \
+  X(simsnsprm, SIMSNSPRM, true,  true,  1, 0, "sim kernels with sensors", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors)
 // PER-WORLD MODEL PARAMETERS (csrc/grx_sim_params.h): in a unit compiled with GRX_PARAM_MODEL the first argument is the array of per-world descriptors in HBM instead of the
 // slot, and m -- like every GRX_FRESH_MODEL of the stages -- is world w's descriptor.  w is wave-uniform; both halves of the address go through readfirstlane so that it sits
 // in SGPRs and the descriptor's members are scalar loads.  The units without the macro compile the lines they always compiled.
@@ -834,14 +855,18 @@ typedef const GrxModel* GrxSimModelArg;
 #else
 typedef int GrxSimModelArg;
 #endif
-// CON: the instance that serves the third output block (GrxSimContacts) too, again in kernels of its own (grx_sim_step_con_kernel, grx_sim_lane_con_kernel; translation units
-// GRX_TU_SIMCON / GRX_TU_SIMCONPRM).  They carry both optional blocks; the eight kernels without it keep their argument lists and their code.
-// a: the fourth block (GrxSimApplied), read only in the units compiled with GRX_APPLIED_FORCES (grx_sim_step_frc_kernel, grx_sim_lane_frc_kernel): the world's two input rows
-// go into the context, where the velocity stage of every pass finds them, and xipos leaves with the other outputs.
-template <class S, bool DYN, bool CON = false>
-__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o = nullptr, const GrxSimApplied* a = nullptr
+// the block of type T among a kernel's blocks, null if the unit does not carry it
+template <class T> __device__ __forceinline__ const T* grx_sim_blk() { return nullptr; }
+template <class T, class H, class... R> __device__ __forceinline__ const T* grx_sim_blk(const H& h, const R&... r) {
+  if constexpr (std::is_same<T, H>::value) return &h; else return grx_sim_blk<T>(r...);
+}
+// a (GrxSimApplied) is read only in the units compiled with GRX_APPLIED_FORCES: the world's two input rows go into the context, where the velocity stage of every pass finds
+// them, and xipos leaves with the other outputs.  sn (GrxSimSensors) likewise in the units compiled with GRX_SIM_SENSORS.
+// The stepper takes the blocks as pointers (null: the unit does not carry the block); the kernels below look them up in their pack at the call.
+template <class S, bool DYN, bool CON>
+__device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o, const GrxSimApplied* a
 #if defined(GRX_SIM_SENSORS)
-                                                   , const GrxSimSensors* sn = nullptr   // the fifth block, in the units compiled with GRX_SIM_SENSORS only (grx_sim_step_sns_kernel, grx_sim_lane_sns_kernel)
+                                                   , const GrxSimSensors* sn
 #endif
 ) {
   if (w >= n_worlds) return;
@@ -890,118 +915,33 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
   if (lane_ == 0) b.status[w] = grx_status_word(b.status[w], c.cnt[2]);
   GRX_PROF_END(c, lane_);
 }
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_kernel(int mslot, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, false>(mslot, b, nullptr, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_dyn_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
-}
-// the large-table kernels of the entry list: a small fixed grid, one workgroup per entry (grx_lane_walk; no polling workgroups, no tickets: nothing stands between two launches)
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_kernel(int mslot, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, false>(mslot, b, nullptr, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_dyn_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
-}
-// the kernels of the launches that request a contact output: both optional blocks ride along, a block of nulls writes nothing
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_con_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, true, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o);
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_con_kernel(int mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o); });
-}
-#if defined(GRX_APPLIED_FORCES)
-// the kernels of the launches with applied forces (GrxSimApplied): all three output blocks ride along, so one pair serves every combination.  The first argument is the slot or,
-// in the unit with per-world model parameters, the descriptor array (GrxSimModelArg): the same two templates are instantiated in GRX_TU_SIMFRC and GRX_TU_SIMFRCPRM.
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_frc_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, true, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a);
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_frc_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a); });
-}
-#endif
+// the stepper's block pointers behind lane_, from a kernel's pack
 #if defined(GRX_SIM_SENSORS)
-// the kernels of the launches that name a sensor (GrxSimSensors): the four other blocks ride along.  As above, the same two templates in GRX_TU_SIMSNS and GRX_TU_SIMSNSPRM.
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_sns_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, GrxSimSensors sn, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, true, true>(mslot, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a, &sn);
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_sns_kernel(GrxSimModelArg mslot, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, GrxSimApplied a, GrxSimSensors sn, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(mslot, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o, &a, &sn); });
-}
+#define GRX_SIM_TAIL_BLOCKS(blk) grx_sim_blk<GrxSimContacts>(blk...), grx_sim_blk<GrxSimApplied>(blk...), grx_sim_blk<GrxSimSensors>(blk...)
+#else
+#define GRX_SIM_TAIL_BLOCKS(blk) grx_sim_blk<GrxSimContacts>(blk...), grx_sim_blk<GrxSimApplied>(blk...)
 #endif
-#if defined(GRX_PARAM_MODEL)
-// the same six kernels for worlds with per-world model parameters: desc[w] is world w's descriptor (grx_sim_params_create)
-template <class S>
+// the kernels: the unit's blocks sit between the buffers and the counts, so the kernarg segment of a block list is that of the same structs written out
+template <class S, bool DYN, bool CON, class... Blk>
 __global__ void __launch_bounds__(64, 2)
-grx_sim_step_prm_kernel(const GrxModel* desc, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
+grx_sim_step_kernel(GrxSimModelArg mslot, GrxSimBuffers b, Blk... blk, int n_worlds, int words, int nstep, int forward_only) {
   extern __shared__ float lds[];
-  grx_sim_step_world<S, false>(desc, b, nullptr, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
+  grx_sim_step_world<S, DYN, CON>(mslot, b, grx_sim_blk<GrxSimDynamics>(blk...), grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, GRX_SIM_TAIL_BLOCKS(blk));
 }
-template <class S>
+// the large-table kernel of the entry list: a small fixed grid, one workgroup per entry (grx_lane_walk; no polling workgroups, no tickets: nothing stands between two launches)
+template <class S, bool DYN, bool CON, class... Blk>
 __global__ void __launch_bounds__(64, 2)
-grx_sim_lane_prm_kernel(const GrxModel* desc, GrxSimBuffers b, int n_worlds, int words, int nstep, int forward_only) {
+grx_sim_lane_kernel(GrxSimModelArg mslot, GrxSimBuffers b, Blk... blk, int n_worlds, int words, int nstep, int forward_only) {
   extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, false>(desc, b, nullptr, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
+  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) {
+    grx_sim_step_world<S, DYN, CON>(mslot, b, grx_sim_blk<GrxSimDynamics>(blk...), w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, GRX_SIM_TAIL_BLOCKS(blk));
+  });
 }
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_dyn_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, true>(desc, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x);
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_dyn_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true>(desc, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x); });
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_step_con_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_sim_step_world<S, true, true>(desc, b, &d, grx_slot_world(nullptr, blockIdx.x, gridDim.x), n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o);
-}
-template <class S>
-__global__ void __launch_bounds__(64, 2)
-grx_sim_lane_con_prm_kernel(const GrxModel* desc, GrxSimBuffers b, GrxSimDynamics d, GrxSimContacts o, int n_worlds, int words, int nstep, int forward_only) {
-  extern __shared__ float lds[];
-  grx_lane_walk(b.lane, [&](int w) __attribute__((always_inline)) { grx_sim_step_world<S, true, true>(desc, b, &d, w, n_worlds, words, nstep, forward_only, lds, (int)threadIdx.x, &o); });
-}
+#undef GRX_SIM_TAIL_BLOCKS
 #if GRX_TU_SIMPRM
 // the commit (csrc/grx_sim_params.h): two launches behind each other on the caller's stream, one wave per world
 __global__ void __launch_bounds__(64) grx_param_commit_rows_kernel(GrxParamCommit a) { grx_param_commit_rows(a, (int)blockIdx.x, (int)threadIdx.x); }
 __global__ void __launch_bounds__(64) grx_param_commit_records_kernel(GrxParamCommit a) { grx_param_commit_records(a, (int)blockIdx.x, (int)threadIdx.x); }
-#endif
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -1021,6 +961,15 @@ static hipError_t grx_raise_lds_limit(const void* fn, int bytes) {
 static hipError_t grx_upload_descriptor(const GrxModel* g, int slot) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), g, sizeof(GrxModel), sizeof(GrxModel) * (size_t)slot, hipMemcpyHostToDevice);
 }
+// One launch of the task-free stepper, as grx_sim_step_impl hands it to a unit (host only).  A unit reads the members its row names: the slot or the per-world descriptors,
+// and of the blocks those of its list.
+struct GrxSimRequest {
+  unsigned grid; size_t lds_bytes; void* stream;
+  int slot; const GrxModel* desc;
+  const GrxSimBuffers* b;
+  std::tuple<const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*> blk;   // the optional blocks, in the order of the kernels' argument list
+  int n, words, nstep, forward_only;
+};
 // The entry points of the family units, declared once for every unit (the API unit calls them; each is defined in the unit that instantiates the family's kernels).
 // grx_tu_*_prepare: returns a hipError_t (0 = ok); *shape <- id of the shape-specialised kernels that serve the model (unchanged if none)
 extern "C" {
@@ -1029,35 +978,17 @@ int grx_tu_point_prepare(const GrxModel* g, int bytes, int slot, int* shape);
 int grx_tu_hand_prepare(const GrxModel* g, int bytes, int slot, int* shape);
 int grx_tu_adroit_prepare(const GrxModel* g, int bytes, int slot, int* shape);
 int grx_tu_kitchen_prepare(const GrxModel* g, int bytes, int slot, int* shape);
-int grx_tu_sim_prepare(const GrxModel* g, int bytes, int slot);   // generic kernels only: no shape
-int grx_tu_simdyn_prepare(const GrxModel* g, int bytes, int slot);   // the same stepper with the second output block (GrxSimDynamics): a unit of its own, compiled beside the others
 // kind 0: env.step, 1: forward (nstep), 2: compacted reset
 int grx_tu_fetch_launch(int kind, int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxFetchTask* t, const GrxFetchBuffers* b, const GrxFetchResetArgs* r, int n, int words, int nstep);
 int grx_tu_point_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxPointTask* t, const GrxPointBuffers* b, int n, int words);
 int grx_tu_hand_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxHandTask* t, const GrxHandBuffers* b, int n, int words, int forward_only);
 int grx_tu_adroit_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxAdroitTask* t, const GrxAdroitBuffers* b, int n, int words, int forward_only);
 int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxKitchenTask* t, const GrxKitchenBuffers* b, int n, int words, int forward_only);
-int grx_tu_sim_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
-int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
-int grx_tu_simcon_prepare(const GrxModel* g, int bytes, int slot);   // ... and with the third (GrxSimContacts)
-int grx_tu_simcon_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only);
-// the units with per-world model parameters: no descriptor slot (desc: the per-world descriptors in HBM); the first of the two also holds the commit kernels
-int grx_tu_simprm_prepare(int bytes);
-int grx_tu_simdynprm_prepare(int bytes);
-int grx_tu_simprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only);
-int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only);
+// the units of the task-free stepper (GRX_SIM_UNITS): one signature each.  A slot unit takes its copy of the descriptor; a parameter unit has no slot and ignores g and slot
+#define X(unit, ...) int grx_tu_##unit##_prepare(const GrxModel* g, int bytes, int slot); int grx_tu_##unit##_launch(const GrxSimRequest* r);
+GRX_SIM_UNITS(X)
+#undef X
 int grx_tu_simprm_commit(const GrxParamCommit* a, void* stream);
-int grx_tu_simconprm_prepare(int bytes);
-int grx_tu_simconprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only);
-// the units with applied forces (GrxSimApplied): all four blocks
-int grx_tu_simfrc_prepare(const GrxModel* g, int bytes, int slot);
-int grx_tu_simfrc_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only);
-int grx_tu_simfrcprm_prepare(int bytes);
-int grx_tu_simfrcprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only);
-int grx_tu_simsns_prepare(const GrxModel* g, int bytes, int slot);
-int grx_tu_simsns_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only);
-int grx_tu_simsnsprm_prepare(int bytes);
-int grx_tu_simsnsprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only);
 }
 // Shape tables, X(id, shape): GRX_*_SHAPES = the shapes with step kernels (Fetch: forward and reset kernels too), GRX_*_LANES = the same models with the tables of the
 // overflow lane (ids >= 100: lane kernel only, everything else of such a model runs generic).  Which match wins is as it always was: Fetch and Adroit take the FIRST step shape
@@ -1230,149 +1161,70 @@ extern "C" int grx_tu_kitchen_launch(int shape, unsigned grid, size_t lds_bytes,
   return (int)hipGetLastError();
 }
 #endif
-#if GRX_TU_SIM
-// the task-free stepper runs every model on the generic kernels (shape-specialised instances for user models: out of scope)
-extern "C" int grx_tu_sim_prepare(const GrxModel* g, int bytes, int slot) {
-  GRX_LDS(grx_sim_step_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_kernel<GrxShapeAny>);
+// The units of the task-free stepper (GRX_SIM_UNITS): it runs every model on the generic kernels (shape-specialised instances for user models: out of scope).  One prepare and
+// one launch serve whichever unit is being compiled: the LDS limit of its kernel pair and, where the model comes from a slot, its copy of the descriptor; then one launch of
+// the lane kernel (a launch with an entry list) or of the step kernel, with the blocks of the unit's row taken from the request by type.
+template <bool DYN, bool CON, class... Blk>
+static int grx_sim_unit_prepare(const GrxModel* g, int bytes, int slot) {
+  GRX_LDS((grx_sim_step_kernel<GrxShapeAny, DYN, CON, Blk...>)); GRX_LDS((grx_sim_lane_kernel<GrxShapeAny, DYN, CON, Blk...>));
+#if defined(GRX_PARAM_MODEL)
+  return 0;   // no slot: the model of a world is its descriptor in HBM
+#else
   return (int)grx_upload_descriptor(g, slot);
+#endif
 }
-extern "C" int grx_tu_sim_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, n, words, nstep, forward_only);
+template <bool DYN, bool CON, class... Blk>
+static int grx_sim_unit_launch(const GrxSimRequest* r) {
+#if defined(GRX_PARAM_MODEL)
+  const GrxSimModelArg model = r->desc;
+#else
+  const GrxSimModelArg model = r->slot;
+#endif
+  const auto kernel = r->b->lane.list ? grx_sim_lane_kernel<GrxShapeAny, DYN, CON, Blk...> : grx_sim_step_kernel<GrxShapeAny, DYN, CON, Blk...>;
+  hipLaunchKernelGGL(kernel, dim3(r->grid), dim3(64), r->lds_bytes, (hipStream_t)r->stream, model, *r->b, *std::get<const Blk*>(r->blk)..., r->n, r->words, r->nstep, r->forward_only);
   return (int)hipGetLastError();
 }
+#define GRX_SIM_UNIT_BODY(unit, DYN, CON, PRM, ...) \
+  static_assert((PRM != 0) == std::is_pointer<GrxSimModelArg>::value, "a PRM row is compiled with GRX_PARAM_MODEL, every other row without"); \
+  extern "C" int grx_tu_##unit##_prepare(const GrxModel* g, int bytes, int slot) { return grx_sim_unit_prepare<DYN, CON, ##__VA_ARGS__>(g, bytes, slot); } \
+  extern "C" int grx_tu_##unit##_launch(const GrxSimRequest* r) { return grx_sim_unit_launch<DYN, CON, ##__VA_ARGS__>(r); }
+// what the single-unit build has in place of a unit it cannot hold: a model can be created (nothing to prepare), a parameter object cannot (grx_sim_params_create fails on the
+// first of its prepare calls), a launch that needs the unit fails
+#define GRX_SIM_UNIT_STUB(unit, DYN, CON, PRM, ...) \
+  extern "C" int grx_tu_##unit##_prepare(const GrxModel*, int, int) { return PRM ? (int)hipErrorNotSupported : 0; } \
+  extern "C" int grx_tu_##unit##_launch(const GrxSimRequest*) { return (int)hipErrorNotSupported; }
+// Does this translation unit hold a row?  The single-unit build: the row's SINGLE column.  Every other build: whether its compile line has -DGRX_TU_<UNIT>=1
+// (GRX_SIM_IS_1(x) is 1 if x expands to 1, else 0: only GRX_SIM_IS_1_1 expands to two arguments).  GRX_SIM_UNIT_1 defines the unit here, GRX_SIM_UNIT_0 leaves it to another unit.
+// (The rows without a block leave X's variadic argument empty and the bodies use GNU `, ##__VA_ARGS__`: hipcc's clang accepts both under -std=c++17.)
+// Worked, for the row simcon in a build with -DGRX_TU_SIMCON=1 and in one without:
+//   GRX_SIM_IS_1(GRX_TU_SIMCON) -> GRX_SIM_IS_1_(GRX_SIM_IS_1_1)             -> GRX_SIM_SECOND(~, 1, 0, ~)                     -> 1 -> GRX_SIM_UNIT_1(simcon, ...) = the body
+//   GRX_SIM_IS_1(GRX_TU_SIMCON) -> GRX_SIM_IS_1_(GRX_SIM_IS_1_GRX_TU_SIMCON) -> GRX_SIM_SECOND(GRX_SIM_IS_1_GRX_TU_SIMCON, 0, ~) -> 0 -> GRX_SIM_UNIT_0(simcon, ...) = nothing
+#define GRX_SIM_IS_1_1 ~, 1
+#define GRX_SIM_SECOND(a, b, ...) b
+#define GRX_SIM_IS_1_(...) GRX_SIM_SECOND(__VA_ARGS__, 0, ~)
+#define GRX_SIM_CAT_(a, b) a##b
+#define GRX_SIM_CAT(a, b) GRX_SIM_CAT_(a, b)
+#define GRX_SIM_IS_1(x) GRX_SIM_IS_1_(GRX_SIM_CAT(GRX_SIM_IS_1_, x))
+#define GRX_SIM_UNIT_1 GRX_SIM_UNIT_BODY
+#if defined(GRX_TU_ALL)
+#define GRX_SIM_HOLDS(UNIT, SINGLE) SINGLE
+#define GRX_SIM_UNIT_0 GRX_SIM_UNIT_STUB
+#else
+#define GRX_SIM_HOLDS(UNIT, SINGLE) GRX_SIM_IS_1(GRX_TU_##UNIT)
+#define GRX_SIM_UNIT_0(...)
 #endif
-#if GRX_TU_SIMDYN
-// ... and the launches that request one of the dynamics outputs, on kernels of their own (see grx_sim_step_world)
-extern "C" int grx_tu_simdyn_prepare(const GrxModel* g, int bytes, int slot) {
-  GRX_LDS(grx_sim_step_dyn_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_dyn_kernel<GrxShapeAny>);
-  return (int)grx_upload_descriptor(g, slot);
-}
-extern "C" int grx_tu_simdyn_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_dyn_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_dyn_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if GRX_TU_SIMCON
-// ... and those that request a contact output
-extern "C" int grx_tu_simcon_prepare(const GrxModel* g, int bytes, int slot) {
-  GRX_LDS(grx_sim_step_con_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_con_kernel<GrxShapeAny>);
-  return (int)grx_upload_descriptor(g, slot);
-}
-extern "C" int grx_tu_simcon_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_con_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_con_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
+#define X(unit, UNIT, DYN, CON, PRM, SINGLE, what, ...) GRX_SIM_CAT(GRX_SIM_UNIT_, GRX_SIM_HOLDS(UNIT, SINGLE))(unit, DYN, CON, PRM, ##__VA_ARGS__)
+GRX_SIM_UNITS(X)
+#undef X
+// the commit kernels live in the first of the parameter units
 #if GRX_TU_SIMPRM
-extern "C" int grx_tu_simprm_prepare(int bytes) {
-  GRX_LDS(grx_sim_step_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_prm_kernel<GrxShapeAny>);
-  return 0;
-}
-extern "C" int grx_tu_simprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
 extern "C" int grx_tu_simprm_commit(const GrxParamCommit* a, void* stream) {
   hipLaunchKernelGGL(grx_param_commit_rows_kernel, dim3((unsigned)a->n_worlds), dim3(64), 0, (hipStream_t)stream, *a);
   hipLaunchKernelGGL(grx_param_commit_records_kernel, dim3((unsigned)a->n_worlds), dim3(64), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
-#endif
-#if GRX_TU_SIMDYNPRM
-extern "C" int grx_tu_simdynprm_prepare(int bytes) {
-  GRX_LDS(grx_sim_step_dyn_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_dyn_prm_kernel<GrxShapeAny>);
-  return 0;
-}
-extern "C" int grx_tu_simdynprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_dyn_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_dyn_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if GRX_TU_SIMCONPRM
-extern "C" int grx_tu_simconprm_prepare(int bytes) {
-  GRX_LDS(grx_sim_step_con_prm_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_con_prm_kernel<GrxShapeAny>);
-  return 0;
-}
-extern "C" int grx_tu_simconprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_con_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_con_prm_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if GRX_TU_SIMFRC
-// ... and those with applied forces
-extern "C" int grx_tu_simfrc_prepare(const GrxModel* g, int bytes, int slot) {
-  GRX_LDS(grx_sim_step_frc_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_frc_kernel<GrxShapeAny>);
-  return (int)grx_upload_descriptor(g, slot);
-}
-extern "C" int grx_tu_simfrc_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if GRX_TU_SIMFRCPRM
-extern "C" int grx_tu_simfrcprm_prepare(int bytes) {
-  GRX_LDS(grx_sim_step_frc_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_frc_kernel<GrxShapeAny>);
-  return 0;
-}
-extern "C" int grx_tu_simfrcprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_frc_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if GRX_TU_SIMSNS
-// ... and those that name a sensor
-extern "C" int grx_tu_simsns_prepare(const GrxModel* g, int bytes, int slot) {
-  GRX_LDS(grx_sim_step_sns_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_sns_kernel<GrxShapeAny>);
-  return (int)grx_upload_descriptor(g, slot);
-}
-extern "C" int grx_tu_simsns_launch(unsigned grid, size_t lds_bytes, void* stream, int slot, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, slot, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if GRX_TU_SIMSNSPRM
-extern "C" int grx_tu_simsnsprm_prepare(int bytes) {
-  GRX_LDS(grx_sim_step_sns_kernel<GrxShapeAny>); GRX_LDS(grx_sim_lane_sns_kernel<GrxShapeAny>);
-  return 0;
-}
-extern "C" int grx_tu_simsnsprm_launch(unsigned grid, size_t lds_bytes, void* stream, const GrxModel* desc, const GrxSimBuffers* b, const GrxSimDynamics* d, const GrxSimContacts* o, const GrxSimApplied* a, const GrxSimSensors* sn, int n, int words, int nstep, int forward_only) {
-  if (b->lane.list) hipLaunchKernelGGL(grx_sim_lane_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
-  else hipLaunchKernelGGL(grx_sim_step_sns_kernel<GrxShapeAny>, dim3(grid), dim3(64), lds_bytes, (hipStream_t)stream, desc, *b, *d, *o, *a, *sn, n, words, nstep, forward_only);
-  return (int)hipGetLastError();
-}
-#endif
-#if defined(GRX_TU_ALL)
-// ... nor the GRX_SIM_SENSORS kernels: a launch that names a sensor fails
-extern "C" int grx_tu_simsns_prepare(const GrxModel*, int, int) { return 0; }
-extern "C" int grx_tu_simsns_launch(unsigned, size_t, void*, int, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*, int, int, int, int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simsnsprm_prepare(int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simsnsprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*, int, int, int, int) { return (int)hipErrorNotSupported; }
-#endif
-#if defined(GRX_TU_ALL)
-// ... nor the GRX_APPLIED_FORCES kernels: a model can be created (nothing to prepare), a launch with applied forces fails
-extern "C" int grx_tu_simfrc_prepare(const GrxModel*, int, int) { return 0; }
-extern "C" int grx_tu_simfrc_launch(unsigned, size_t, void*, int, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, int, int, int, int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simfrcprm_prepare(int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simfrcprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, int, int, int, int) { return (int)hipErrorNotSupported; }
-#endif
-#if defined(GRX_TU_ALL)
-// the single-unit build cannot hold the GRX_PARAM_MODEL kernels: a parameter object cannot be created there (grx_sim_params_create fails on the first of these)
-extern "C" int grx_tu_simprm_prepare(int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simdynprm_prepare(int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, int, int, int, int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simdynprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, int, int, int, int) { return (int)hipErrorNotSupported; }
+#elif defined(GRX_TU_ALL)
 extern "C" int grx_tu_simprm_commit(const GrxParamCommit*, void*) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simconprm_prepare(int) { return (int)hipErrorNotSupported; }
-extern "C" int grx_tu_simconprm_launch(unsigned, size_t, void*, const GrxModel*, const GrxSimBuffers*, const GrxSimDynamics*, const GrxSimContacts*, int, int, int, int) { return (int)hipErrorNotSupported; }
 #endif
 #undef GRX_LDS
 
@@ -1550,6 +1402,18 @@ static int fail(const std::string& msg) { g_err = msg; return -1; }
 
 extern "C" const char* grx_last_error(void) { return g_err.c_str(); }
 
+// GRX_SIM_UNITS as the host sees it, in the table's order.  blocks: one bit per optional block the unit's kernels carry, bit k = element k of GrxSimRequest::blk.
+template <class T, size_t K = 0> constexpr unsigned grx_sim_block_bit() {
+  if constexpr (std::is_same<const T*, std::tuple_element_t<K, decltype(GrxSimRequest::blk)>>::value) return 1u << K; else return grx_sim_block_bit<T, K + 1>();
+}
+template <class... Blk> constexpr unsigned grx_sim_block_mask() { return (grx_sim_block_bit<Blk>() | ... | 0u); }
+struct GrxSimUnit { int (*prepare)(const GrxModel*, int, int); int (*launch)(const GrxSimRequest*); bool prm; const char* what; unsigned blocks; };
+static const GrxSimUnit g_sim_units[] = {
+#define X(unit, UNIT, DYN, CON, PRM, SINGLE, what, ...) {grx_tu_##unit##_prepare, grx_tu_##unit##_launch, PRM != 0, what, grx_sim_block_mask<__VA_ARGS__>()},
+  GRX_SIM_UNITS(X)
+#undef X
+};
+
 static void grx_model_free(grx_model* m) {
   if (!m) return;
   if (m->slot >= 0) g_slot_used[m->slot] = 0;
@@ -1591,11 +1455,8 @@ static int grx_model_create_impl(const int32_t* H, const int32_t* I, const doubl
   if ((e = grx_tu_hand_prepare(&g, bytes, m->slot, &m->shape)) != 0) return fail(std::string("grx_model_create (hand kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_adroit_prepare(&g, bytes, m->slot, &m->shape)) != 0) return fail(std::string("grx_model_create (adroit kernels): ") + hipGetErrorString((hipError_t)e));
   if ((e = grx_tu_kitchen_prepare(&g, bytes, m->slot, &m->shape)) != 0) return fail(std::string("grx_model_create (kitchen kernels): ") + hipGetErrorString((hipError_t)e));
-  if ((e = grx_tu_sim_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels): ") + hipGetErrorString((hipError_t)e));
-  if ((e = grx_tu_simdyn_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the dynamics block): ") + hipGetErrorString((hipError_t)e));
-  if ((e = grx_tu_simcon_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with the contact block): ") + hipGetErrorString((hipError_t)e));
-  if ((e = grx_tu_simfrc_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with applied forces): ") + hipGetErrorString((hipError_t)e));
-  if ((e = grx_tu_simsns_prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (sim kernels with sensors): ") + hipGetErrorString((hipError_t)e));
+  for (const GrxSimUnit& u : g_sim_units)   // (the parameter units are prepared with a parameter object: grx_sim_params_create)
+    if (!u.prm && (e = u.prepare(&g, bytes, m->slot)) != 0) return fail(std::string("grx_model_create (") + u.what + "): " + hipGetErrorString((hipError_t)e));
   HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_grx_models), &m->dev, sizeof(GrxModel), sizeof(GrxModel) * (size_t)m->slot, hipMemcpyHostToDevice));
   return 0;
 }
@@ -1746,34 +1607,41 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
   return 0;
 }
 
+// What an entry point of the stepper asks of grx_sim_step_impl: the arguments of grx_sim_step_dyn, and behind them what the later entry points added (zero: not given).
+//   desc: null, or the per-world descriptors of a parameter object made for m (grx_sim_step_params): the launch then goes to the parameter twin of its unit
+//   con: null, or the third block (grx_sim_step_con; need_con: that call, where null is an error): its own checks follow those of the first two
+//   frc: null, or the fourth block (grx_sim_step_frc; need_frc likewise)
+//   sns: null, or the fifth block with the handle's device tables already in place of the caller's host tables (grx_sim_step_sns)
+struct GrxSimStepArgs {
+  const grx_model* m; const grx_sim_buffers* buf; const grx_sim_dynamics* dyn; int n_worlds, nstep, forward_only; void* stream;
+  const GrxModel* desc = nullptr; const grx_sim_contacts* con = nullptr; const grx_sim_applied* frc = nullptr; const GrxSimSensors* sns = nullptr;
+  bool need_con = false, need_frc = false;
+};
 // The argument checks that do not need the model come first and read nothing of it (tests/test_cpu_sim.py reaches them without a device).
 // grx_sim_step is this call without the second block; the messages keep its name.
-// desc: null, or the per-world descriptors of a parameter object made for m (grx_sim_step_params): the launch then goes to the kernels of the parameter units
-// con: null, or the third block (grx_sim_step_con): its own checks follow those of the first two; a launch that requests one of its outputs runs the kernels of the contact units
-// frc: null, or the fourth block (grx_sim_step_frc): a launch with one of its pointers set runs the kernels of the applied-force units, which carry every block
-static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream, const GrxModel* desc, const grx_sim_contacts* con = nullptr, bool need_con = false,
-                             const grx_sim_applied* frc = nullptr, bool need_frc = false, const GrxSimSensors* sns = nullptr) {
+static int grx_sim_step_impl(const GrxSimStepArgs& s) {
+  const grx_model* m = s.m; const grx_sim_buffers* buf = s.buf;
   if (!m) return fail("grx_sim_step: null model");
   if (!buf) return fail("grx_sim_step: null buffers");
   if (!buf->qpos || !buf->qvel || !buf->qacc_ws) return fail("grx_sim_step: null state buffer (qpos, qvel, qacc_ws)");
   if (!buf->status) return fail("grx_sim_step: null status buffer");
-  if (n_worlds < 1) return fail("grx_sim_step: n_worlds < 1");
-  if (!forward_only && nstep < 1) return fail("grx_sim_step: nstep < 1 (a launch that is not forward_only runs at least one substep)");
+  if (s.n_worlds < 1) return fail("grx_sim_step: n_worlds < 1");
+  if (!s.forward_only && s.nstep < 1) return fail("grx_sim_step: nstep < 1 (a launch that is not forward_only runs at least one substep)");
   GrxSimDynamics d; memset(&d, 0, sizeof(d));
-  if (dyn) {
-    memcpy(&d, dyn, sizeof(d));
+  if (s.dyn) {
+    memcpy(&d, s.dyn, sizeof(d));
     if (d.njac < 0 || d.njac > GRX_SIM_MAXJAC) return fail("grx_sim_step_dyn: njac outside [0, GRX_SIM_MAXJAC]");
     if (d.njac > 0 && !d.site_jacp && !d.site_jacr) return fail("grx_sim_step_dyn: njac > 0 with site_jacp and site_jacr both null");
     if (d.njac == 0 && (d.site_jacp || d.site_jacr)) return fail("grx_sim_step_dyn: a Jacobian buffer with njac == 0 (no site selected)");
   }
-  if (need_con && !con) return fail("grx_sim_step_con: null contact block (grx_sim_step_dyn is the call without one)");
+  if (s.need_con && !s.con) return fail("grx_sim_step_con: null contact block (grx_sim_step_dyn is the call without one)");
   GrxSimContacts o; memset(&o, 0, sizeof(o));
-  if (con) memcpy(&o, con, sizeof(o));
+  if (s.con) memcpy(&o, s.con, sizeof(o));
   const bool contacts = o.geom || o.dim || o.efc_address || o.dist || o.pos || o.frame || o.force;
   if (contacts && o.ccap < 1) return fail("grx_sim_step_con: ccap < 1 with a contact buffer set (ccap is the number of slots per world)");
-  if (need_frc && !frc) return fail("grx_sim_step_frc: null applied block (grx_sim_step_con is the call without one)");
+  if (s.need_frc && !s.frc) return fail("grx_sim_step_frc: null applied block (grx_sim_step_con is the call without one)");
   GrxSimApplied a; memset(&a, 0, sizeof(a));
-  if (frc) memcpy(&a, frc, sizeof(a));
+  if (s.frc) memcpy(&a, s.frc, sizeof(a));
   const bool applied = a.qfrc_applied || a.xfrc_applied || a.xipos;
   const GrxModel& g = m->dev;
   for (int k = 0; k < d.njac; k++)
@@ -1784,26 +1652,21 @@ static int grx_sim_step_impl(const grx_model* m, const grx_sim_buffers* buf, con
     return fail("grx_sim_step: the model was compiled with an origin; the outputs are raw engine coordinates, so compile it in the MJCF's own frame (origin = None)");
   if (g.nshift > 0) return fail("grx_sim_step: the model has a per-world shift group (compile_mjcf(shift_body=...)), which only the Adroit task layer feeds");
   GrxSimBuffers b; memcpy(&b, buf, sizeof(b));
-  // a launch that requests none of the ten runs the kernels without the block
   const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
-  const unsigned grid = grx_step_grid(b.lane, 0, 0, n_worlds); const size_t lds_bytes = (size_t)m->words * 4 + m->lds_pad;
-  int e;
-  // sns: null, or the fifth block with the handle's device tables already in place of the caller's host tables (grx_sim_step_sns): the kernels of the sensor units carry every block
-  if (sns) e = desc ? grx_tu_simsnsprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, &a, sns, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
-                    : grx_tu_simsns_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, &a, sns, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
-  else if (applied) e = desc ? grx_tu_simfrcprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
-                        : grx_tu_simfrc_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, &a, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
-  else if (contacts) e = desc ? grx_tu_simconprm_launch(grid, lds_bytes, stream, desc, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
-                         : grx_tu_simcon_launch(grid, lds_bytes, stream, m->slot, &b, &d, &o, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
-  else if (desc) e = dynamic ? grx_tu_simdynprm_launch(grid, lds_bytes, stream, desc, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
-                        : grx_tu_simprm_launch(grid, lds_bytes, stream, desc, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
-  else e = dynamic ? grx_tu_simdyn_launch(grid, lds_bytes, stream, m->slot, &b, &d, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0)
-                   : grx_tu_sim_launch(grid, lds_bytes, stream, m->slot, &b, n_worlds, m->words, forward_only ? 0 : nstep, forward_only ? 1 : 0);
+  // The launch runs on the first unit (GRX_SIM_UNITS: plain, dynamics, contacts, applied forces, sensors; each carries the blocks of those before it) that carries every block
+  // it requests, or on that unit's parameter twin: a launch that requests none of a block's members runs kernels without the block
+  const unsigned need = (dynamic ? grx_sim_block_mask<GrxSimDynamics>() : 0u) | (contacts ? grx_sim_block_mask<GrxSimContacts>() : 0u) | (applied ? grx_sim_block_mask<GrxSimApplied>() : 0u) |
+                        (s.sns ? grx_sim_block_mask<GrxSimSensors>() : 0u);
+  const GrxSimRequest rq = {grx_step_grid(b.lane, 0, 0, s.n_worlds), (size_t)m->words * 4 + m->lds_pad, s.stream, m->slot, s.desc, &b, {&d, &o, &a, s.sns},
+                            s.n_worlds, m->words, s.forward_only ? 0 : s.nstep, s.forward_only ? 1 : 0};
+  int e = (int)hipErrorNotSupported;
+  for (const GrxSimUnit& u : g_sim_units)
+    if (u.prm == (s.desc != nullptr) && (need & ~u.blocks) == 0) { e = u.launch(&rq); break; }
   if (e) return fail(std::string("grx_sim_step launch: ") + hipGetErrorString((hipError_t)e));
   return 0;
 }
 extern "C" int grx_sim_step_dyn(const grx_model* m, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, int n_worlds, int nstep, int forward_only, void* stream) {
-  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, nullptr);
+  return grx_sim_step_impl({m, buf, dyn, n_worlds, nstep, forward_only, stream});
 }
 #include "grx_sim_params_api.h"
 extern "C" int grx_sim_step(const grx_model* m, const grx_sim_buffers* buf, int n_worlds, int nstep, int forward_only, void* stream) {
@@ -1825,14 +1688,18 @@ static int grx_sim_params_desc(const grx_model* m, const grx_sim_params* p, int 
 extern "C" int grx_sim_step_con(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, int n_worlds, int nstep, int forward_only, void* stream) {
   const GrxModel* desc;
   if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
-  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, true);
+  GrxSimStepArgs s = {m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con};
+  s.need_con = true;
+  return grx_sim_step_impl(s);
 }
 // The stepper with the fourth block (applied forces, xipos): dyn and con may be null here.  A block of nulls forwards to what grx_sim_step_con launches for the other arguments.
 extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc, int n_worlds, int nstep, int forward_only,
                                 void* stream) {
   const GrxModel* desc;
   if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
-  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, false, frc, true);
+  GrxSimStepArgs s = {m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, frc};
+  s.need_frc = true;
+  return grx_sim_step_impl(s);
 }
 #include "grx_rays_api.h"
 #include "grx_sensors_api.h"

@@ -1,6 +1,6 @@
 // grx_sensors_api.h -- the C ABI of the sensor block (include/grx_capi.h grx_sim_step_sns / grx_sim_sensors_layout).  A FRAGMENT of the API section of grx_kernels.hip (it uses
-// that section's grx_model, fail, HIP_OK and grx_sim_step_impl), as grx_rays_api.h is; the routines are csrc/grx_sim_sensors.h, the kernels grx_sim_step_sns_kernel /
-// grx_sim_lane_sns_kernel of the units GRX_TU_SIMSNS / GRX_TU_SIMSNSPRM.
+// that section's grx_model, fail, HIP_OK and grx_sim_step_impl), as grx_rays_api.h is; the routines are csrc/grx_sim_sensors.h, the kernels the
+// instances of grx_sim_step_kernel / grx_sim_lane_kernel with all five blocks (the rows simsns / simsnsprm of GRX_SIM_UNITS, units GRX_TU_SIMSNS / GRX_TU_SIMSNSPRM).
 
 // The host table, checked on the host: a known type, an object of the kind the type reads with an id in range, rows that tile [0, ndata) in order.
 static int grx_sensor_table_check(const grx_model* m, const grx_sim_sensors* s) {
@@ -60,14 +60,16 @@ extern "C" int grx_sim_step_sns(const grx_model* m, const grx_sim_params* p, con
   if (!sns) return fail("grx_sim_step_sns: null sensor block (grx_sim_step_frc is the call without one)");
   const GrxModel* desc;
   if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
-  if (!sns->data || sns->nsensor == 0) return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, false, frc, false);
+  GrxSimStepArgs s = {m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, frc};
+  if (!sns->data || sns->nsensor == 0) return grx_sim_step_impl(s);
   if (sns->nsensor < 0 || sns->ndata < 1) return fail("grx_sim_step_sns: nsensor < 0 or ndata < 1 with a data buffer set");
   if (!sns->spec || !sns->cutoff) return fail("grx_sim_step_sns: null spec / cutoff table (host arrays [nsensor, 4] and [nsensor])");
   if (!m) return fail("grx_sim_step: null model");
   GrxSimSensors d; memset(&d, 0, sizeof(d));
   d.nsensor = sns->nsensor; d.ndata = sns->ndata; d.data = sns->data;
   if (grx_sensor_table(m, sns, &d.spec, &d.cutoff)) return -1;
-  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, false, frc, false, &d);
+  s.sns = &d;
+  return grx_sim_step_impl(s);
 }
 // sizeof(grx_sim_sensors) and the byte offset of every member, in declaration order: what _native.SimSensorsStruct must mirror (host only)
 extern "C" int grx_sim_sensors_layout(long long* out, int cap) {

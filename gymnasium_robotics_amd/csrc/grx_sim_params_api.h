@@ -121,8 +121,8 @@ static int grx_sim_params_create_impl(grx_sim_params* p) {
     HIP_OK(hipMemcpy(pass ? p->d_desc_large : p->d_desc, desc.data(), sizeof(GrxModel) * (size_t)N, hipMemcpyHostToDevice));
     int e;
     const int bytes = h->words * 4 + h->lds_pad;
-    if ((e = grx_tu_simprm_prepare(bytes)) != 0 || (e = grx_tu_simdynprm_prepare(bytes)) != 0 || (e = grx_tu_simconprm_prepare(bytes)) != 0 || (e = grx_tu_simfrcprm_prepare(bytes)) != 0 || (e = grx_tu_simsnsprm_prepare(bytes)) != 0)
-      return fail(std::string("grx_sim_params_create (kernels with per-world parameters): ") + hipGetErrorString((hipError_t)e));
+    for (const GrxSimUnit& u : g_sim_units)   // the parameter twins of the stepper's units: no descriptor, no slot
+      if (u.prm && (e = u.prepare(nullptr, bytes, 0)) != 0) return fail(std::string("grx_sim_params_create (kernels with per-world parameters): ") + hipGetErrorString((hipError_t)e));
   }
   GrxParamCommit& a = p->args;
   memset(&a, 0, sizeof(a));
@@ -187,7 +187,7 @@ extern "C" int grx_sim_step_params(const grx_model* m, const grx_sim_params* p, 
   if (!p) return fail("grx_sim_step_params: null parameter object");
   if (m != p->model && m != p->large) return fail("grx_sim_step_params: the parameter object was not created for this model handle");
   if (n_worlds != p->n) return fail("grx_sim_step_params: n_worlds = " + std::to_string(n_worlds) + ", the parameter object holds " + std::to_string(p->n) + " worlds");
-  return grx_sim_step_impl(m, buf, dyn, n_worlds, nstep, forward_only, stream, m == p->model ? p->d_desc : p->d_desc_large);
+  return grx_sim_step_impl({m, buf, dyn, n_worlds, nstep, forward_only, stream, m == p->model ? p->d_desc : p->d_desc_large});
 }
 
 // sizeof(GrxParamCommit) is internal; what the Python side mirrors is the list of names, in id order, and the bit of each rule (host only)

@@ -119,6 +119,11 @@ PARAM_BAD = dict(nonfinite=1, frictionloss=2, damping=4, inertial=8, armature=16
 CONTACTS = ("contact_geom", "contact_dim", "contact_efc_address", "contact_dist", "contact_pos", "contact_frame", "contact_force")      # grx_sim_contacts, in its order
 _CONTACT_WIDTH = dict(contact_geom=(2,), contact_dim=(), contact_efc_address=(), contact_dist=(), contact_pos=(3,), contact_frame=(9,), contact_force=(6,))
 _INT_TENSORS = ("ncon", "nefc", "contact_geom", "contact_dim", "contact_efc_address")
+# The optional blocks in the order the C entries take them, and the entries from the one that takes every block down to the plain one: (the attribute that selects the entry,
+# the entry, whether it takes the parameter object behind the handle, how many of _SIM_BLOCKS it takes).  A simulation calls the first entry whose attribute it has.
+_SIM_BLOCKS = ("_dyn", "_con", "_frc", "_sns")
+_SIM_ENTRIES = (("_sns", "grx_sim_step_sns", True, 4), ("_frc", "grx_sim_step_frc", True, 3), ("_con", "grx_sim_step_con", True, 2), ("_p", "grx_sim_step_params", True, 1),
+                ("_dyn", "grx_sim_step_dyn", False, 1), (None, "grx_sim_step", False, 0))
 APPLIED = ("qfrc_applied", "xfrc_applied", "xipos")      # grx_sim_applied, in its order: two inputs the caller writes, one output
 APPLIED_INPUTS = ("qfrc_applied", "xfrc_applied")
 # grx_sim_sensors: the type and object numbers of csrc/grx_sim_sensors.h, in its order
@@ -451,6 +456,10 @@ class BatchedSim:
                 assert int(np.prod(shape[1:])) == cnt.value, (name, shape, cnt.value)
                 self._params.__dict__[name] = device_view(ptr.value, shape, np.float32, self.device)
             t["params_invalid"] = torch.zeros(self.num_worlds, dtype=torch.int32, device=self.device)
+        # the C entry every launch calls and its fixed arguments: the first of _SIM_ENTRIES whose block this simulation has; it takes the blocks up to its own (None: not requested)
+        _, name, takes_params, nblocks = next(e for e in _SIM_ENTRIES if e[0] is None or getattr(self, e[0]) is not None)
+        self._entry = (getattr(self._L, name), (self._p,) if takes_params else (),
+                       tuple(None if getattr(self, a) is None else ctypes.byref(getattr(self, a)) for a in _SIM_BLOCKS[:nblocks]))
         t["qpos"][:] = self._qpos0
         if self.nmocap:
             t["mocap_pos"][:], t["mocap_quat"][:] = self._mocap_pos0, self._mocap_quat0
@@ -512,33 +521,13 @@ class BatchedSim:
         from .core import stream_ptr
 
         self._ensure()
+        if self._entry is None:
+            raise RuntimeError("this BatchedSim is closed: its model handles and its parameter object are gone")
         m = self._mask(mask)
         self._mask_keep = m
         with torch.cuda.device(self.device):
-            if self._sns is not None:      # the kernels with the sensor block; they serve every other block and the per-world parameters as well
-                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
-                con = None if self._con is None else ctypes.byref(self._con)
-                frc = None if self._frc is None else ctypes.byref(self._frc)
-                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_sns(h, self._p, ctypes.byref(b), dyn, con, frc, ctypes.byref(self._sns), self.num_worlds, int(nstep),
-                                                                                  int(forward_only), stream_ptr(self.device))))
-            elif self._frc is not None:      # the kernels with applied forces; they serve every other block and the per-world parameters as well
-                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
-                con = None if self._con is None else ctypes.byref(self._con)
-                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_frc(h, self._p, ctypes.byref(b), dyn, con, ctypes.byref(self._frc), self.num_worlds, int(nstep),
-                                                                                  int(forward_only), stream_ptr(self.device))))
-            elif self._con is not None:      # the kernels that write the contact list; they serve the other two blocks and the per-world parameters as well
-                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
-                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_con(h, self._p, ctypes.byref(b), dyn, ctypes.byref(self._con), self.num_worlds, int(nstep),
-                                                                                  int(forward_only), stream_ptr(self.device))))
-            elif self._p is not None:      # the kernels that take each world's model from its own descriptor
-                dyn = None if self._dyn is None else ctypes.byref(self._dyn)
-                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_params(h, self._p, ctypes.byref(b), dyn, self.num_worlds, int(nstep), int(forward_only),
-                                                                                     stream_ptr(self.device))))
-            elif self._dyn is None:
-                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step(h, ctypes.byref(b), self.num_worlds, int(nstep), int(forward_only), stream_ptr(self.device))))
-            else:
-                go = lambda h: (lambda b: _native.check(self._L.grx_sim_step_dyn(h, ctypes.byref(b), ctypes.byref(self._dyn), self.num_worlds, int(nstep), int(forward_only),
-                                                                                  stream_ptr(self.device))))
+            fn, head, blocks = self._entry
+            go = lambda h: (lambda b: _native.check(fn(h, *head, ctypes.byref(b), *blocks, self.num_worlds, int(nstep), int(forward_only), stream_ptr(self.device))))
             self._bufs.mask = None if m is None else m.data_ptr()
             if self.lane is None:
                 go(self._h)(self._bufs)
@@ -815,6 +804,7 @@ class BatchedSim:
             self._params = None
             self._L.grx_sim_params_destroy(self._p)
             self._p = None
+        self._entry = None      # (it holds the parameter object's pointer: no launch after close)
         release_models(self, ("_h", "_h_big"))
         self.lane = None
 

@@ -37,11 +37,12 @@ def resources():
     print("kernel resources (vgpr / agpr / sgpr / scratch B per lane / vgpr spills / sgpr spills), from the library's code objects:")
     rows = []
     for r in kernel_resources(_native.LIB_PATH):
-        m = re.search(r"grx_sim_(step|lane)(_[a-z]+)*_kernel", r["name"])      # (the names are mangled where the binutils are missing)
-        if m:
-            rows.append((m.group(0), "descriptors" if "GrxModel const*" in r["name"] or "PK8GrxModel" in r["name"] else "slot", r))
-    for head, kind, r in sorted(rows, key=lambda x: (x[0].replace("lane", "step"), x[0], x[1])):
-        print(f"  {head:30s} {kind:12s} {r['vgpr']:>4} / {r['agpr']:>3} / {r['sgpr']:>4} / {r['scratch']:>5} / {r['spill_v']:>4} / {r['spill_s']:>5}")
+        m = re.search(r"grx_sim_(step|lane)_kernel", r["name"])      # (the names are mangled where the binutils are missing)
+        if m:      # the two templates, one instance per unit: told apart by the block list among the template arguments and by the first argument
+            blocks = [b for b in ("Dynamics", "Contacts", "Applied", "Sensors") if "GrxSim" + b in r["name"]]
+            rows.append((len(blocks), m.group(0) + " <" + (", ".join(blocks) or "no block") + ">", "descriptors" if "GrxModel const*" in r["name"] or "PK8GrxModel" in r["name"] else "slot", r))
+    for _, head, kind, r in sorted(rows, key=lambda x: (x[0], x[1].replace("lane", "step"), x[1], x[2])):
+        print(f"  {head:66s} {kind:12s} {r['vgpr']:>4} / {r['agpr']:>3} / {r['sgpr']:>4} / {r['scratch']:>5} / {r['spill_v']:>4} / {r['spill_s']:>5}")
 
 
 def main():
