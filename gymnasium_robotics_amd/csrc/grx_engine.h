@@ -258,6 +258,11 @@ struct GrxCtx {
   // a launch that names no sensor; this world's output row; and whether the pass that is running is the one the readings belong to (grx_sim_world)
   const struct GrxSimSensors* sns; float* sns_row; int sns_pass;
 #endif
+#if defined(GRX_SIM_WRENCHES)
+  // the kernels with the body-wrench block (csrc/grx_sim_wrench.h, translation units GRX_TU_SIMWRN / GRX_TU_SIMWRNPRM; members of those units only): the block; whether the
+  // launch asks for a body row and for a force / torque reading; and what the pass that is running owes of the two (GRX_WRN_*, set by grx_sim_world)
+  const struct GrxSimWrenches* wrn; int wrn_rows, wrn_ft, wrn_pass;
+#endif
   int bail;    // != 0: a step kernel that hands capacity overflows to a re-run at a larger capacity stops simulating at the first overflowing substep (nothing of this run is kept)
   int soft_maxefc, soft_jpool, soft_maxcon;   // > 0 (the large-table kernel of the overflow lane): the capacities of the FAST kernel; exceeding one of them raises GRX_ST_SOFT
   int *lane_entry_count, *lane_entry_list; int lane_entry_cap, lane_world; int* lane_ready; int lane_ready_cap;   // fast kernel with an overflow lane: where a world that overflows claims its re-run (grx_lane_claim)

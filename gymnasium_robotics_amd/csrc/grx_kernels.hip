@@ -15,7 +15,9 @@
 //   GRX_APPLIED_FORCES   the rows that carry GrxSimApplied: GrxCtx has the two input rows and the velocity stage ends in grx_applied_forces (csrc/grx_eng_velocity.h)
 //   GRX_SIM_SENSORS      the rows that carry GrxSimSensors (csrc/grx_sim_sensors.h): GrxCtx has the block and the stages evaluate the sensors of their pass; with
 //                        GRX_APPLIED_FORCES, so that one kernel pair serves all five blocks
-#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM) && !defined(GRX_TU_SIMFRC) && !defined(GRX_TU_SIMFRCPRM) && !defined(GRX_TU_SIMSNS) && !defined(GRX_TU_SIMSNSPRM)
+//   GRX_SIM_WRENCHES     the rows that carry GrxSimWrenches (csrc/grx_sim_wrench.h): the last pass and the sensor pass run the post-constraint Newton-Euler phases; with
+//                        the two macros above, so that one kernel pair serves all six blocks
+#if !defined(GRX_TU_FETCH) && !defined(GRX_TU_HAND) && !defined(GRX_TU_POINT) && !defined(GRX_TU_ADROIT) && !defined(GRX_TU_KITCHEN) && !defined(GRX_TU_SIM) && !defined(GRX_TU_SIMDYN) && !defined(GRX_TU_API) && !defined(GRX_TU_SIMPRM) && !defined(GRX_TU_SIMDYNPRM) && !defined(GRX_TU_SIMCON) && !defined(GRX_TU_SIMCONPRM) && !defined(GRX_TU_SIMFRC) && !defined(GRX_TU_SIMFRCPRM) && !defined(GRX_TU_SIMSNS) && !defined(GRX_TU_SIMSNSPRM) && !defined(GRX_TU_SIMWRN) && !defined(GRX_TU_SIMWRNPRM)
 #define GRX_TU_ALL 1
 #define GRX_TU_FETCH 1
 #define GRX_TU_HAND 1
@@ -29,14 +31,17 @@
 #if GRX_TU_FETCH && !defined(GRX_NO_HULL_HINTS)
 #define GRX_HULL_HINTS 1
 #endif
-#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM || GRX_TU_SIMFRCPRM || GRX_TU_SIMSNSPRM
+#if GRX_TU_SIMPRM || GRX_TU_SIMDYNPRM || GRX_TU_SIMCONPRM || GRX_TU_SIMFRCPRM || GRX_TU_SIMSNSPRM || GRX_TU_SIMWRNPRM
 #define GRX_PARAM_MODEL 1
 #endif
-#if GRX_TU_SIMFRC || GRX_TU_SIMFRCPRM || GRX_TU_SIMSNS || GRX_TU_SIMSNSPRM
+#if GRX_TU_SIMFRC || GRX_TU_SIMFRCPRM || GRX_TU_SIMSNS || GRX_TU_SIMSNSPRM || GRX_TU_SIMWRN || GRX_TU_SIMWRNPRM
 #define GRX_APPLIED_FORCES 1
 #endif
-#if GRX_TU_SIMSNS || GRX_TU_SIMSNSPRM
+#if GRX_TU_SIMSNS || GRX_TU_SIMSNSPRM || GRX_TU_SIMWRN || GRX_TU_SIMWRNPRM
 #define GRX_SIM_SENSORS 1
+#endif
+#if GRX_TU_SIMWRN || GRX_TU_SIMWRNPRM
+#define GRX_SIM_WRENCHES 1
 #endif
 #include <hip/hip_runtime.h>
 
@@ -56,6 +61,7 @@
 #include "grx_kitchen_task.h"
 #include "grx_sim_task.h"
 #include "grx_sim_sensors.h"
+#include "grx_sim_wrench.h"
 #include "grx_sim_params.h"
 #include "grx_host_model.h"
 #include "grx_copy.h"
@@ -822,7 +828,7 @@ grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_
 // it again from its untouched state rows on the handle with the large tables.  Forward launches claim too: their outputs are the point of the call.
 //
 // THE UNITS.  One stepper (grx_sim_step_world) and one kernel pair (grx_sim_step_kernel, grx_sim_lane_kernel) serve every launch; what differs between launches is which of
-// the optional blocks (csrc/grx_sim_task.h, csrc/grx_sim_sensors.h) ride in the kernels' argument list behind GrxSimBuffers, always in the order d, o, a, sn.  Each row below is
+// the optional blocks (csrc/grx_sim_task.h, csrc/grx_sim_sensors.h) ride in the kernels' argument list behind GrxSimBuffers, always in the order d, o, a, sn, wr.  Each row below is
 // one translation unit that instantiates the pair for one block list -- kernels of its own, because a block costs the launches that do not ask for it: the second inlined
 // copy of the forward pass costs the DYN instance 250 B of scratch per lane and took 5 % off a launch that shared a kernel with it (profiles/sim_probe_dynamics.txt).  A
 // launch runs on the first row that carries every block it requests; a block that rides along unrequested is a block of nulls and writes nothing.
@@ -830,7 +836,7 @@ grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_
 //   unit / UNIT  the unit exports grx_tu_<unit>_prepare / grx_tu_<unit>_launch and is compiled with -DGRX_TU_<UNIT>
 //   DYN, CON     the instance of the stepper: with the dynamics outputs (GrxSimDynamics), with the contact outputs (GrxSimContacts)
 //   PRM          a GRX_PARAM_MODEL unit: the twin of the row above it for worlds with per-world model parameters (below)
-//   SINGLE       the single-unit build holds it (GRX_TU_ALL: one set of macros, so no unit compiled with GRX_PARAM_MODEL, GRX_APPLIED_FORCES or GRX_SIM_SENSORS); stubs stand in
+//   SINGLE       the single-unit build holds it (GRX_TU_ALL: one set of macros, so no unit compiled with GRX_PARAM_MODEL, GRX_APPLIED_FORCES GRX_SIM_SENSORS or GRX_SIM_WRENCHES); stubs stand in
 //                for the others: a model can be created, a parameter object cannot, a launch that needs one of them fails with hipErrorNotSupported
 //   what         the unit in the words of grx_model_create's failure message
 // A further block is: its struct; a row per new unit (and the unit in __graft_entry__.HIP_UNITS); its pointer in grx_sim_step_world with the lines that use it, and in
@@ -846,7 +852,9 @@ grx_kitchen_lane_kernel(int mslot, GrxKitchenTask t, GrxKitchenBuffers b, int n_
   X(simfrc,    SIMFRC,    true,  true,  0, 0, "sim kernels with applied forces", GrxSimDynamics, GrxSimContacts, GrxSimApplied) \
   X(simfrcprm, SIMFRCPRM, true,  true,  1, 0, "sim kernels with applied forces", GrxSimDynamics, GrxSimContacts, GrxSimApplied) \
   X(simsns,    SIMSNS,    true,  true,  0, 0, "sim kernels with sensors", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors) \
-  X(simsnsprm, SIMSNSPRM, true,  true,  1, 0, "sim kernels with sensors", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors)
+  X(simsnsprm, SIMSNSPRM, true,  true,  1, 0, "sim kernels with sensors", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors) \
+  X(simwrn,    SIMWRN,    true,  true,  0, 0, "sim kernels with body wrenches", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors, GrxSimWrenches) \
+  X(simwrnprm, SIMWRNPRM, true,  true,  1, 0, "sim kernels with body wrenches", GrxSimDynamics, GrxSimContacts, GrxSimApplied, GrxSimSensors, GrxSimWrenches)
 // PER-WORLD MODEL PARAMETERS (csrc/grx_sim_params.h): in a unit compiled with GRX_PARAM_MODEL the first argument is the array of per-world descriptors in HBM instead of the
 // slot, and m -- like every GRX_FRESH_MODEL of the stages -- is world w's descriptor.  w is wave-uniform; both halves of the address go through readfirstlane so that it sits
 // in SGPRs and the descriptor's members are scalar loads.  The units without the macro compile the lines they always compiled.
@@ -861,12 +869,15 @@ template <class T, class H, class... R> __device__ __forceinline__ const T* grx_
   if constexpr (std::is_same<T, H>::value) return &h; else return grx_sim_blk<T>(r...);
 }
 // a (GrxSimApplied) is read only in the units compiled with GRX_APPLIED_FORCES: the world's two input rows go into the context, where the velocity stage of every pass finds
-// them, and xipos leaves with the other outputs.  sn (GrxSimSensors) likewise in the units compiled with GRX_SIM_SENSORS.
+// them, and xipos leaves with the other outputs.  sn (GrxSimSensors) likewise in the units compiled with GRX_SIM_SENSORS, wr (GrxSimWrenches) in those with GRX_SIM_WRENCHES.
 // The stepper takes the blocks as pointers (null: the unit does not carry the block); the kernels below look them up in their pack at the call.
 template <class S, bool DYN, bool CON>
 __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const GrxSimBuffers& b, const GrxSimDynamics* d, const int w, int n_worlds, int words, int nstep, int forward_only, float* lds, const int lane_, const GrxSimContacts* o, const GrxSimApplied* a
 #if defined(GRX_SIM_SENSORS)
                                                    , const GrxSimSensors* sn
+#endif
+#if defined(GRX_SIM_WRENCHES)
+                                                   , const GrxSimWrenches* wr
 #endif
 ) {
   if (w >= n_worlds) return;
@@ -889,7 +900,13 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
   c.xfrc_applied = a->xfrc_applied ? a->xfrc_applied + (size_t)w * 6 * m.nbody : nullptr;
 #endif
 #if defined(GRX_SIM_SENSORS)
+#if defined(GRX_SIM_WRENCHES)
+  // (these kernels also serve launches without a sensor: a block of zeros, no sensor pass)
+  c.sns = sn->nsensor > 0 ? sn : nullptr; c.sns_row = sn->data + (size_t)w * sn->ndata; c.sns_pass = 0;
+  c.wrn = wr; c.wrn_rows = (wr->cfrc_ext != nullptr) | (wr->cfrc_int != nullptr) | (wr->cacc != nullptr) | (wr->subtree_com != nullptr); c.wrn_ft = wr->nft > 0; c.wrn_pass = 0;
+#else
   c.sns = sn; c.sns_row = sn->data + (size_t)w * sn->ndata; c.sns_pass = 0;   // (the host launches these kernels only with data set and nsensor > 0)
+#endif
 #endif
   GRX_PROF_BEGIN(c, lane_);
   grx_lane_setup(b.lane, c, w, true);
@@ -916,7 +933,9 @@ __device__ __forceinline__ void grx_sim_step_world(GrxSimModelArg mslot, const G
   GRX_PROF_END(c, lane_);
 }
 // the stepper's block pointers behind lane_, from a kernel's pack
-#if defined(GRX_SIM_SENSORS)
+#if defined(GRX_SIM_WRENCHES)
+#define GRX_SIM_TAIL_BLOCKS(blk) grx_sim_blk<GrxSimContacts>(blk...), grx_sim_blk<GrxSimApplied>(blk...), grx_sim_blk<GrxSimSensors>(blk...), grx_sim_blk<GrxSimWrenches>(blk...)
+#elif defined(GRX_SIM_SENSORS)
 #define GRX_SIM_TAIL_BLOCKS(blk) grx_sim_blk<GrxSimContacts>(blk...), grx_sim_blk<GrxSimApplied>(blk...), grx_sim_blk<GrxSimSensors>(blk...)
 #else
 #define GRX_SIM_TAIL_BLOCKS(blk) grx_sim_blk<GrxSimContacts>(blk...), grx_sim_blk<GrxSimApplied>(blk...)
@@ -967,7 +986,7 @@ struct GrxSimRequest {
   unsigned grid; size_t lds_bytes; void* stream;
   int slot; const GrxModel* desc;
   const GrxSimBuffers* b;
-  std::tuple<const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*> blk;   // the optional blocks, in the order of the kernels' argument list
+  std::tuple<const GrxSimDynamics*, const GrxSimContacts*, const GrxSimApplied*, const GrxSimSensors*, const GrxSimWrenches*> blk;   // the optional blocks, in the order of the kernels' argument list
   int n, words, nstep, forward_only;
 };
 // The entry points of the family units, declared once for every unit (the API unit calls them; each is defined in the unit that instantiates the family's kernels).
@@ -1612,9 +1631,11 @@ extern "C" int grx_point_step(const grx_model* m, const grx_point_task* task, co
 //   con: null, or the third block (grx_sim_step_con; need_con: that call, where null is an error): its own checks follow those of the first two
 //   frc: null, or the fourth block (grx_sim_step_frc; need_frc likewise)
 //   sns: null, or the fifth block with the handle's device tables already in place of the caller's host tables (grx_sim_step_sns)
+//   wrn: null, or the sixth block as the kernels see it, with a pointer set or a force / torque row counted (grx_sim_step_wrn)
 struct GrxSimStepArgs {
   const grx_model* m; const grx_sim_buffers* buf; const grx_sim_dynamics* dyn; int n_worlds, nstep, forward_only; void* stream;
   const GrxModel* desc = nullptr; const grx_sim_contacts* con = nullptr; const grx_sim_applied* frc = nullptr; const GrxSimSensors* sns = nullptr;
+  const GrxSimWrenches* wrn = nullptr;
   bool need_con = false, need_frc = false;
 };
 // The argument checks that do not need the model come first and read nothing of it (tests/test_cpu_sim.py reaches them without a device).
@@ -1653,11 +1674,12 @@ static int grx_sim_step_impl(const GrxSimStepArgs& s) {
   if (g.nshift > 0) return fail("grx_sim_step: the model has a per-world shift group (compile_mjcf(shift_body=...)), which only the Adroit task layer feeds");
   GrxSimBuffers b; memcpy(&b, buf, sizeof(b));
   const bool dynamic = d.qM || d.qfrc_smooth || d.qacc_smooth || d.qfrc_constraint || d.qacc || d.qfrc_bias || d.qfrc_passive || d.qfrc_actuator || d.site_jacp || d.site_jacr;
-  // The launch runs on the first unit (GRX_SIM_UNITS: plain, dynamics, contacts, applied forces, sensors; each carries the blocks of those before it) that carries every block
+  // The launch runs on the first unit (GRX_SIM_UNITS: plain, dynamics, contacts, applied forces, sensors, body wrenches; each carries the blocks of those before it) that carries every block
   // it requests, or on that unit's parameter twin: a launch that requests none of a block's members runs kernels without the block
   const unsigned need = (dynamic ? grx_sim_block_mask<GrxSimDynamics>() : 0u) | (contacts ? grx_sim_block_mask<GrxSimContacts>() : 0u) | (applied ? grx_sim_block_mask<GrxSimApplied>() : 0u) |
-                        (s.sns ? grx_sim_block_mask<GrxSimSensors>() : 0u);
-  const GrxSimRequest rq = {grx_step_grid(b.lane, 0, 0, s.n_worlds), (size_t)m->words * 4 + m->lds_pad, s.stream, m->slot, s.desc, &b, {&d, &o, &a, s.sns},
+                        (s.sns ? grx_sim_block_mask<GrxSimSensors>() : 0u) | (s.wrn ? grx_sim_block_mask<GrxSimWrenches>() : 0u);
+  static const GrxSimSensors no_sns = {};   // what the unit with body wrenches carries for a launch without sensors
+  const GrxSimRequest rq = {grx_step_grid(b.lane, 0, 0, s.n_worlds), (size_t)m->words * 4 + m->lds_pad, s.stream, m->slot, s.desc, &b, {&d, &o, &a, s.sns ? s.sns : &no_sns, s.wrn},
                             s.n_worlds, m->words, s.forward_only ? 0 : s.nstep, s.forward_only ? 1 : 0};
   int e = (int)hipErrorNotSupported;
   for (const GrxSimUnit& u : g_sim_units)

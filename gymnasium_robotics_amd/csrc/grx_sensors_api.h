@@ -14,9 +14,9 @@ static int grx_sensor_table_check(const grx_model* m, const grx_sim_sensors* s) 
     if (type < 0 || type >= GRX_SNS_NTYPE) return fail(who + " has the unknown type " + std::to_string(type));
     if (objtype < 0 || objtype >= GRX_SNS_NOBJ) return fail(who + " has the unknown object type " + std::to_string(objtype));
     const bool joint = type == GRX_SNS_JOINTPOS || type == GRX_SNS_JOINTVEL || type == GRX_SNS_JOINTACTFRC, act = type >= GRX_SNS_ACTUATORPOS && type <= GRX_SNS_ACTUATORFRC;
-    const bool site_only = type == GRX_SNS_VELOCIMETER || type == GRX_SNS_GYRO || type == GRX_SNS_ACCELEROMETER;
+    const bool site_only = type == GRX_SNS_VELOCIMETER || type == GRX_SNS_GYRO || type == GRX_SNS_ACCELEROMETER || type == GRX_SNS_FORCE || type == GRX_SNS_TORQUE;
     const bool ok = joint ? objtype == GRX_SNS_OBJ_JOINT : act ? objtype == GRX_SNS_OBJ_ACTUATOR : site_only ? objtype == GRX_SNS_OBJ_SITE : (objtype == GRX_SNS_OBJ_SITE || objtype == GRX_SNS_OBJ_XBODY);
-    if (!ok) return fail(who + ": type " + std::to_string(type) + " does not read an object of type " + std::to_string(objtype) + " (joint types read joints, actuator types actuators, velocimeter / gyro / accelerometer sites, the frame types sites or xbodies)");
+    if (!ok) return fail(who + ": type " + std::to_string(type) + " does not read an object of type " + std::to_string(objtype) + " (joint types read joints, actuator types actuators, velocimeter / gyro / accelerometer / force / torque sites, the frame types sites or xbodies)");
     const int lim = objtype == GRX_SNS_OBJ_JOINT ? g.njnt : objtype == GRX_SNS_OBJ_ACTUATOR ? g.nu : objtype == GRX_SNS_OBJ_SITE ? g.nsite : g.nbody;
     if (id < 0 || id >= lim) return fail(who + ": object id " + std::to_string(id) + " is outside [0, " + std::to_string(lim) + ")");
     if (joint && (!jtype || id >= m->pm.cnt[k_jt] || jtype[id] < 2)) return fail(who + ": joint " + std::to_string(id) + " is a free or ball joint (the joint types read hinge and slide joints)");
@@ -53,6 +53,22 @@ static int grx_sensor_table(const grx_model* m, const grx_sim_sensors* s, const 
   return 0;
 }
 
+// What the two entries that take a sensor table do with it.  *has <- the block carries data and sensors (one that does not launches what the call without it launches).
+// Then the checks, *nft <- the number of force / torque rows (wrn: the caller serves them; otherwise they are refused, before anything is uploaded), and *d <- the block as
+// the kernels see it, with the handle's device tables in place of the caller's host tables.
+static int grx_sim_sensor_block(const grx_model* m, const grx_sim_sensors* sns, bool wrn, GrxSimSensors* d, int* nft, bool* has) {
+  *nft = 0;
+  *has = sns && sns->data && sns->nsensor != 0;
+  if (!*has) return 0;
+  if (sns->nsensor < 0 || sns->ndata < 1) return fail("grx_sim_step_sns: nsensor < 0 or ndata < 1 with a data buffer set");
+  if (!sns->spec || !sns->cutoff) return fail("grx_sim_step_sns: null spec / cutoff table (host arrays [nsensor, 4] and [nsensor])");
+  if (!m) return fail("grx_sim_step: null model");
+  for (int k = 0; k < sns->nsensor; k++) *nft += sns->spec[4 * k] == GRX_SNS_FORCE || sns->spec[4 * k] == GRX_SNS_TORQUE;
+  if (*nft && !wrn) return fail("grx_sim_step_sns: the table holds " + std::to_string(*nft) + " force / torque sensor(s), which read cfrc_int: grx_sim_step_wrn is the call that serves them");
+  memset(d, 0, sizeof(*d));
+  d->nsensor = sns->nsensor; d->ndata = sns->ndata; d->data = sns->data;
+  return grx_sensor_table(m, sns, &d->spec, &d->cutoff);
+}
 // The stepper with the fifth block.  params, dyn, con and frc may be null and mean what they mean to grx_sim_step_frc; a block without data or without sensors launches what
 // that call launches for the other arguments.
 extern "C" int grx_sim_step_sns(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc, const grx_sim_sensors* sns,
@@ -61,15 +77,36 @@ extern "C" int grx_sim_step_sns(const grx_model* m, const grx_sim_params* p, con
   const GrxModel* desc;
   if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
   GrxSimStepArgs s = {m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, frc};
-  if (!sns->data || sns->nsensor == 0) return grx_sim_step_impl(s);
-  if (sns->nsensor < 0 || sns->ndata < 1) return fail("grx_sim_step_sns: nsensor < 0 or ndata < 1 with a data buffer set");
-  if (!sns->spec || !sns->cutoff) return fail("grx_sim_step_sns: null spec / cutoff table (host arrays [nsensor, 4] and [nsensor])");
-  if (!m) return fail("grx_sim_step: null model");
-  GrxSimSensors d; memset(&d, 0, sizeof(d));
-  d.nsensor = sns->nsensor; d.ndata = sns->ndata; d.data = sns->data;
-  if (grx_sensor_table(m, sns, &d.spec, &d.cutoff)) return -1;
-  s.sns = &d;
+  GrxSimSensors d; int nft; bool has;
+  if (grx_sim_sensor_block(m, sns, false, &d, &nft, &has)) return -1;
+  if (has) s.sns = &d;
   return grx_sim_step_impl(s);
+}
+// The stepper with the sixth block (body wrenches, csrc/grx_sim_wrench.h).  sns and wrn may be null; with nothing of the block requested -- no pointer set, no force / torque
+// row in the table -- the launch is grx_sim_step_sns's (or, without sensors, grx_sim_step_frc's).
+extern "C" int grx_sim_step_wrn(const grx_model* m, const grx_sim_params* p, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc, const grx_sim_sensors* sns,
+                                const grx_sim_wrenches* wrn, int n_worlds, int nstep, int forward_only, void* stream) {
+  const GrxModel* desc;
+  if (grx_sim_params_desc(m, p, n_worlds, &desc)) return -1;
+  GrxSimStepArgs s = {m, buf, dyn, n_worlds, nstep, forward_only, stream, desc, con, frc};
+  GrxSimSensors d; GrxSimWrenches r; int nft; bool has;
+  if (grx_sim_sensor_block(m, sns, true, &d, &nft, &has)) return -1;
+  if (has) s.sns = &d;
+  memset(&r, 0, sizeof(r));
+  if (wrn) { r.cfrc_ext = wrn->cfrc_ext; r.cfrc_int = wrn->cfrc_int; r.cacc = wrn->cacc; r.subtree_com = wrn->subtree_com; }
+  r.nft = nft;
+  if (r.cfrc_ext || r.cfrc_int || r.cacc || r.subtree_com || nft) s.wrn = &r;
+  return grx_sim_step_impl(s);
+}
+// sizeof(grx_sim_wrenches) and the byte offset of every member, in declaration order: what _native.SimWrenchesStruct must mirror (host only)
+extern "C" int grx_sim_wrenches_layout(long long* out, int cap) {
+  const grx_sim_wrenches* z = nullptr;
+#define OFF(f) (long long)((const char*)&z->f - (const char*)z)
+  const long long v[] = {(long long)sizeof(grx_sim_wrenches), OFF(cfrc_ext), OFF(cfrc_int), OFF(cacc), OFF(subtree_com)};
+#undef OFF
+  const int n = (int)(sizeof(v) / sizeof(v[0]));
+  if (out) for (int i = 0; i < n && i < cap; i++) out[i] = v[i];
+  return n;
 }
 // sizeof(grx_sim_sensors) and the byte offset of every member, in declaration order: what _native.SimSensorsStruct must mirror (host only)
 extern "C" int grx_sim_sensors_layout(long long* out, int cap) {

@@ -23,7 +23,9 @@
 // sensor types (spec[4 s]) and object types (spec[4 s + 1]); the host table of grx_sim_step_sns names them with these numbers (gymnasium_robotics_amd/sim.py SENSOR_TYPES)
 enum { GRX_SNS_JOINTPOS = 0, GRX_SNS_JOINTVEL, GRX_SNS_ACTUATORPOS, GRX_SNS_ACTUATORVEL, GRX_SNS_ACTUATORFRC, GRX_SNS_JOINTACTFRC, GRX_SNS_FRAMEPOS, GRX_SNS_FRAMEQUAT,
        GRX_SNS_FRAMEXAXIS, GRX_SNS_FRAMEYAXIS, GRX_SNS_FRAMEZAXIS, GRX_SNS_FRAMELINVEL, GRX_SNS_FRAMEANGVEL, GRX_SNS_VELOCIMETER, GRX_SNS_GYRO, GRX_SNS_FRAMELINACC,
-       GRX_SNS_FRAMEANGACC, GRX_SNS_ACCELEROMETER, GRX_SNS_NTYPE };
+       GRX_SNS_FRAMEANGACC, GRX_SNS_ACCELEROMETER,
+       GRX_SNS_FORCE, GRX_SNS_TORQUE,   // read cfrc_int: served by csrc/grx_sim_wrench.h in the units compiled with GRX_SIM_WRENCHES, refused by grx_sim_step_sns
+       GRX_SNS_NTYPE };
 enum { GRX_SNS_OBJ_JOINT = 0, GRX_SNS_OBJ_ACTUATOR, GRX_SNS_OBJ_SITE, GRX_SNS_OBJ_XBODY, GRX_SNS_NOBJ };
 
 // The fifth optional block as the kernels see it: spec and cutoff are the handle's DEVICE copies of the caller's host tables (grx_sim_step_sns swaps them in).
@@ -79,6 +81,9 @@ struct GrxSns {
       for (int s = lane; s < ns; s += 64) {
         const int* sp = sn->spec + 4 * s;
         const int type = sp[0], objtype = sp[1], id = sp[2], adr = sp[3];
+#if defined(GRX_SIM_WRENCHES)
+        if (type >= GRX_SNS_FORCE) continue;   // force / torque: both phases are grx_sim_wrench_p2's (csrc/grx_sim_wrench.h)
+#endif
         const float cut = sn->cutoff[s];
         float out[4] = {0, 0, 0, 0};
         if (type <= GRX_SNS_JOINTACTFRC) {
@@ -139,6 +144,9 @@ struct GrxSns {
         const int* sp = sn->spec + 4 * s;
         const int type = sp[0], objtype = sp[1], id = sp[2], adr = sp[3];
         if (!grx_sensor_is_acc(type)) continue;
+#if defined(GRX_SIM_WRENCHES)
+        if (type >= GRX_SNS_FORCE) continue;
+#endif
         const float cut = sn->cutoff[s];
         int b; const float *p, *R;
         grx_sensor_object(m, c, objtype, id, b, p, R);

@@ -11,6 +11,9 @@
 #if defined(GRX_SIM_SENSORS)
 #include "grx_sim_sensors.h"  // the fifth optional block (GrxSimSensors), only in the units compiled with GRX_SIM_SENSORS: every other unit compiles the lines it always compiled
 #endif
+#if defined(GRX_SIM_WRENCHES)
+#include "grx_sim_wrench.h"   // the sixth optional block (GrxSimWrenches), only in the units compiled with GRX_SIM_WRENCHES (which are compiled with the two macros above as well)
+#endif
 
 struct GrxSimBuffers {
   float *qpos, *qvel, *qacc_ws;           // [N,nq] [N,nv] [N,nv]
@@ -176,9 +179,17 @@ struct GrxSim {
     // the sensor block's two phases stand around the solve of the pass the readings belong to (csrc/grx_sim_sensors.h)
     if (c->sns_pass) GrxSns<S>::grx_sim_sensors_p1(m, c, c->sns, c->sns_row, lane_);
 #endif
+#if defined(GRX_SIM_WRENCHES)
+    // the body-wrench block likewise; what its two phases share crosses the solve in registers (csrc/grx_sim_wrench.h)
+    GrxWrnKeep wk;
+    if (c->wrn_pass) GrxWrn<S>::grx_sim_wrench_p1(m, c, wk, lane_);
+#endif
     E::grx_solve_integrate(m, c, do_euler, lane_);
 #if defined(GRX_SIM_SENSORS)
     if (c->sns_pass) GrxSns<S>::grx_sim_sensors_p2(m, c, c->sns, c->sns_row, lane_);
+#endif
+#if defined(GRX_SIM_WRENCHES)
+    if (c->wrn_pass) GrxWrn<S>::grx_sim_wrench_p2(m, c, c->wrn, wk, c->wrn_pass, w, lane_);
 #endif
   }
   // nstep x mj_step with ctrl held (GrxPoint::grx_point_sim_world with agent = 1 and no task: Euler models one pass per substep, RK4 models four), or one mj_forward.
@@ -191,6 +202,9 @@ struct GrxSim {
     if (forward_only) {
 #if defined(GRX_SIM_SENSORS)
       c->sns_pass = c->sns != nullptr;
+#endif
+#if defined(GRX_SIM_WRENCHES)
+      c->wrn_pass = (c->wrn_rows ? GRX_WRN_ROWS : 0) | (c->sns_pass && c->wrn_ft ? GRX_WRN_SENSORS : 0);
 #endif
       if (p1) grx_sim_forward_p1<CON>(m, c, 0, d, o, crow, ckey, w, lane_);
       else E::grx_forward_euler(m, c, 0, lane_);
@@ -207,6 +221,10 @@ struct GrxSim {
       // RK4: the FIRST stage's pass of the last substep -- mj_RungeKutta's further stages skip the sensors -- so that pass goes through grx_sim_forward_p1 as well; what it
       // writes of the other blocks there is written again by the fourth stage's pass.
       c->sns_pass = c->sns != nullptr && it == (rk4 ? total - 4 : total - 1);
+#if defined(GRX_SIM_WRENCHES)
+      // the body rows belong to the last pass, as the dynamics and contact outputs do; the force / torque readings to the sensor pass.  Under RK4 those are two passes.
+      c->wrn_pass = (c->wrn_rows && it == total - 1 ? GRX_WRN_ROWS : 0) | (c->sns_pass && c->wrn_ft ? GRX_WRN_SENSORS : 0);
+#endif
       if ((p1 && it == total - 1) || c->sns_pass) grx_sim_forward_p1<CON>(m, c, !rk4, d, o, crow, ckey, w, lane_);
 #else
       if (p1 && it == total - 1) grx_sim_forward_p1<CON>(m, c, !rk4, d, o, crow, ckey, w, lane_);

@@ -72,10 +72,10 @@ its ``(adr, dim)``.  Served: ``jointpos`` / ``jointvel`` (hinge and slide joints
 force before the gear), ``jointactuatorfrc``, and on a site or an ``xbody`` of the compiled model ``framepos``, ``framequat``, ``framexaxis`` / ``yaxis`` / ``zaxis``, ``framelinvel``,
 ``frameangvel``, ``framelinacc``, ``frameangacc``; on a site ``velocimeter``, ``gyro``, ``accelerometer``.  With p, R the object's position and rotation and Jp, Jr the Jacobians of
 the material point p: u = Jp qvel, omega = Jr qvel, c = Jp qacc + (d/dt Jp) qvel, alpha = Jr qacc + (d/dt Jr) qvel; velocimeter = R'u, gyro = R'omega, framelinacc = c - g,
-accelerometer = R'(c - g), frameangacc = alpha.  ``- g`` is MuJoCo's convention that the world body accelerates with ``-gravity`` (an accelerometer at rest reads +9.81 along world
+accelerometer = R'(c - g), frameangacc = alpha; on a site ``force`` / ``torque`` (BODY WRENCHES below).  ``- g`` is MuJoCo's convention that the world body accelerates with ``-gravity`` (an accelerometer at rest reads +9.81 along world
 z); it is the DEFINITION of ``framelinacc`` here as well.  A world that names ``gravity`` among ``model_params`` reads its own committed row.  A positive ``cutoff`` clamps a reading to
 [-cutoff, cutoff] (not the quaternion and axis types); ``noise`` is ignored.  Refused by name, with the reason: ``touch`` (``outputs=("sensordata",)`` with ``touch_filter``),
-``rangefinder`` (``sim.rangefinder()``), ``force`` / ``torque`` (they need cfrc_int / cfrc_ext, which the engine does not form), frame sensors on a ``body`` (the inertial frame),
+``rangefinder`` (``sim.rangefinder()``), ``force`` / ``torque`` on anything but a site or without ``cfrc_int`` among ``body_dynamics``, frame sensors on a ``body`` (the inertial frame),
 ``geom`` or ``camera``, any ``reftype``, every other type, and an ``xbody`` the compiler merged into its parent or a site ``keep_sites`` dropped.
 WHICH PASS: all readings belong to ONE forward pass, with that pass's own qvel and qacc.  After ``forward()``: that pass.  After ``step(n)`` of an Euler model: the last substep's pass,
 before its integration.  Of an RK4 model: the FIRST stage's pass of the last substep -- ``mj_step`` runs ``mj_forward`` with sensors, then ``mj_RungeKutta`` with the sensors skipped --
@@ -85,6 +85,26 @@ Sensors are not state: ``reset()``'s ``forward()`` refreshes them, ``get_state``
     sim = grx.BatchedSim("quadruped.xml", 4096, sensors=("imu_acc", "imu_gyro", "imu_quat", "hip_pos", "hip_vel"))
     sim.step(nstep=5)
     obs = torch.cat([sim.sensor_data, sim.ctrl], dim=1)                                            # or sim.sensor("imu_acc"): [N, 3]
+
+BODY WRENCHES (what ``mj_rnePostConstraint`` forms): ``body_dynamics`` names any of ``sim.BODY_DYNAMICS``; rows are the compiled model's bodies, as for ``xpos``, fp32, every
+element written by each launch.  ``subtree_com`` [N, nbody, 3] is ``data.subtree_com`` of the same pass as ``xpos`` (from ``xipos`` and the world's own committed ``body_mass``).  The
+other three are [N, nbody, 6] spatial vectors in MuJoCo's layout -- rotation part first (torque then force, angular then linear), world orientation, about
+``subtree_com[root(b)]`` with root = ``body_rootid``.  ``cfrc_ext[b]`` sums ``xfrc_applied[b]`` acting at ``xipos[b]`` and every contact of the pass that has constraint rows, with the sign
+of ``mj_contactForce``: + on the body of the pair's second geom, - on the first, each about its own root's centre of mass; the torque is ``(contact_pos - com) x f`` plus the
+torsional term along the normal (condim >= 4) and the rolling terms along the tangents (condim 6); row 0 (the world) receives the reactions of world-geom contacts.
+``cacc[b]`` is the spatial acceleration: ``cacc[0] = (0, -gravity)``, ``cacc[b] = cacc[parent] + sum cdof_dot qvel + sum cdof qacc`` over b's own dofs.  ``cfrc_int[b]`` = sum over
+e in subtree(b) of ``cinert_e cacc_e + cvel_e x* (cinert_e cvel_e) - cfrc_ext_e``: the wrench b's parent exerts on b through their joint.  DEVIATION: the forces of weld, connect and
+joint EQUALITY constraints are not added to ``cfrc_ext`` (recent MuJoCo releases add connect / weld forces there); the definition above is self-contained.  WHICH PASS: that of
+``qfrc_bias`` and the contact outputs -- the last forward pass, under RK4 the fourth stage's; after ``step(n)`` the rows are those of ``forward()`` at the state ``step(n - 1)`` left.  Not
+state: ``reset()`` refreshes them, ``get_state`` / ``set_state`` ignore them.  The ``force`` and ``torque`` SENSORS (on a site, dim 3, cutoff clamps) read them: with b the site's body,
+``(tau, f) = cfrc_int[b]``, p / R the site's position / rotation and c = ``subtree_com[root(b)]``, force = ``R' f`` and torque = ``R' (tau - (p - c) x f)``.  They follow the sensor
+block's pass rule (Euler: the last pass; RK4: the FIRST stage of the last substep, so under RK4 they differ from the ``cfrc_int`` output by design).  They are
+served in a simulation whose ``body_dynamics`` names ``cfrc_int``; in any other they stay refused by name, with that reason (``sensors="all"`` lists them in ``sensors_unserved``), so a
+simulation that asks for no body output runs the kernels and gets the sensor columns it had.  Naming a body output routes the launch through grx_sim_step_wrn.
+
+    sim = grx.BatchedSim("humanoid.xml", 4096, body_dynamics=("cfrc_ext", "cfrc_int", "subtree_com"), sensors=("left_foot_force",))
+    sim.step(nstep=5)
+    contact_cost = 5e-7 * sim.cfrc_ext.clamp(-1, 1).square().sum((1, 2))
 
 RAYS (``mj_ray``, rangefinders, lidar): ``sim.ray(origin, direction)`` casts R rays per world -- ``origin`` / ``direction`` [N, R, 3] (or [R, 3]) in world coordinates, ``direction``
 of any length -- and returns ``(dist [N, R] float32, geom [N, R] int32)``: the ray parameter of the nearest hit (metres for a unit direction) and the geom hit, -1.0 / -1 for none.
@@ -101,7 +121,7 @@ it rather than cast through it.  The calls run a kernel of their own (grx_sim_ra
     dist, geom = sim.ray_sites("lidar", fan, max_dist=10.0)                                        # [N, 64]
 
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-force / torque sensors (cfrc_int, cfrc_ext), sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, cameras.
+equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, cameras.
 """
 import ctypes
 
@@ -121,16 +141,18 @@ _CONTACT_WIDTH = dict(contact_geom=(2,), contact_dim=(), contact_efc_address=(),
 _INT_TENSORS = ("ncon", "nefc", "contact_geom", "contact_dim", "contact_efc_address")
 # The optional blocks in the order the C entries take them, and the entries from the one that takes every block down to the plain one: (the attribute that selects the entry,
 # the entry, whether it takes the parameter object behind the handle, how many of _SIM_BLOCKS it takes).  A simulation calls the first entry whose attribute it has.
-_SIM_BLOCKS = ("_dyn", "_con", "_frc", "_sns")
-_SIM_ENTRIES = (("_sns", "grx_sim_step_sns", True, 4), ("_frc", "grx_sim_step_frc", True, 3), ("_con", "grx_sim_step_con", True, 2), ("_p", "grx_sim_step_params", True, 1),
+_SIM_BLOCKS = ("_dyn", "_con", "_frc", "_sns", "_wrn")
+_SIM_ENTRIES = (("_wrn", "grx_sim_step_wrn", True, 5), ("_sns", "grx_sim_step_sns", True, 4), ("_frc", "grx_sim_step_frc", True, 3), ("_con", "grx_sim_step_con", True, 2), ("_p", "grx_sim_step_params", True, 1),
                 ("_dyn", "grx_sim_step_dyn", False, 1), (None, "grx_sim_step", False, 0))
 APPLIED = ("qfrc_applied", "xfrc_applied", "xipos")      # grx_sim_applied, in its order: two inputs the caller writes, one output
 APPLIED_INPUTS = ("qfrc_applied", "xfrc_applied")
+BODY_DYNAMICS = ("cfrc_ext", "cfrc_int", "cacc", "subtree_com")      # grx_sim_wrenches, in its order
 # grx_sim_sensors: the type and object numbers of csrc/grx_sim_sensors.h, in its order
 SENSOR_TYPES = ("jointpos", "jointvel", "actuatorpos", "actuatorvel", "actuatorfrc", "jointactuatorfrc", "framepos", "framequat", "framexaxis", "frameyaxis", "framezaxis",
-                "framelinvel", "frameangvel", "velocimeter", "gyro", "framelinacc", "frameangacc", "accelerometer")
+                "framelinvel", "frameangvel", "velocimeter", "gyro", "framelinacc", "frameangacc", "accelerometer", "force", "torque")
 SENSOR_OBJECTS = ("joint", "actuator", "site", "xbody")
-_SENSOR_JOINT, _SENSOR_ACTUATOR, _SENSOR_SITE_ONLY = ("jointpos", "jointvel", "jointactuatorfrc"), ("actuatorpos", "actuatorvel", "actuatorfrc"), ("velocimeter", "gyro", "accelerometer")
+_SENSOR_JOINT, _SENSOR_ACTUATOR, _SENSOR_SITE_ONLY = ("jointpos", "jointvel", "jointactuatorfrc"), ("actuatorpos", "actuatorvel", "actuatorfrc"), ("velocimeter", "gyro", "accelerometer", "force", "torque")
+_SENSOR_WRENCH = ("force", "torque")      # read cfrc_int: served where body_dynamics names it
 _SENSOR_NO_CUTOFF = ("framequat", "framexaxis", "frameyaxis", "framezaxis")
 MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
 
@@ -148,14 +170,16 @@ class _Params:
 
 
 class BatchedSim:
-    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=(), applied=(), sensors=()):
+    def __init__(self, model, num_worlds, device="cuda:0", capacity=None, overflow="rerun", outputs=(), compile_kwargs=None, jac_sites=None, model_params=(), contacts=(), applied=(), sensors=(),
+                 body_dynamics=()):
         """model: path of an MJCF file, or a mjcf.CompiledModel.  capacity: dict(maxcon=, maxefc=, jpool=) of the tables the step launch runs on (None: the compiler's
         default, 32 contacts / 144 rows / 2 032 Jacobian words).  overflow: "rerun" -- a world that exceeds a table in some substep is left untouched by the step launch and run
         again, right behind it, on the large tables (core.RERUN_CAPACITY), so no contact is dropped; "flag" -- it goes on with the excess contacts dropped and the status bits
         CON_OVERFLOW / EFC_OVERFLOW say so.  outputs: the MjData fields to allocate and write, any of sim.OUTPUTS.  compile_kwargs: passed to compile_mjcf (touch_filter,
         keep_sites, mutate, ...).  jac_sites: the names of the sites whose Jacobians site_jacp / site_jacr hold, in the order of their rows (None: every site of the model, which must
         then have at most 16).  model_params: the tables that are per world, any of sim.PARAMS (module docstring).  contacts: the members of the contact list to allocate and write, any of sim.CONTACTS
-        (module docstring).  applied: the applied-force inputs and xipos, any of sim.APPLIED (module docstring).  sensors: names of <sensor> children of the MJCF, or "all" (module docstring, SENSORS).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
+        (module docstring).  applied: the applied-force inputs and xipos, any of sim.APPLIED (module docstring).  sensors: names of <sensor> children of the MJCF, or "all" (module docstring, SENSORS).  body_dynamics: the per-body
+        outputs of mj_rnePostConstraint to allocate and write, any of sim.BODY_DYNAMICS (module docstring, BODY WRENCHES).  Nothing is allocated and no library is loaded before the first tensor is touched or the first launch: the name lookups work without a device."""
         if int(num_worlds) < 1:
             raise ValueError("num_worlds must be at least 1")
         if overflow not in ("rerun", "flag"):
@@ -194,6 +218,15 @@ class BatchedSim:
         if len(set(applied)) != len(applied):
             raise ValueError(f"applied names a tensor twice: {applied}; the applied-force tensors are {APPLIED}")
         self.applied = tuple(a for a in APPLIED if a in applied)
+        if isinstance(body_dynamics, str):
+            body_dynamics = (body_dynamics,)
+        body_dynamics = tuple(body_dynamics)
+        unknown = [a for a in body_dynamics if a not in BODY_DYNAMICS]
+        if unknown:
+            raise ValueError(f"unknown body_dynamics name(s) {unknown}; the per-body outputs are {BODY_DYNAMICS}")
+        if len(set(body_dynamics)) != len(body_dynamics):
+            raise ValueError(f"body_dynamics names an output twice: {body_dynamics}; the per-body outputs are {BODY_DYNAMICS}")
+        self.body_dynamics = tuple(a for a in BODY_DYNAMICS if a in body_dynamics)
         kw = dict(compile_kwargs or {})
         if kw.get("origin") is not None or kw.get("shift_body") is not None:
             raise ValueError("BatchedSim returns raw engine coordinates: compile the model in the MJCF's own frame (no origin) and without a shift group")
@@ -234,7 +267,7 @@ class BatchedSim:
             raise ValueError("site_jacp / site_jacr need at least one site (the model has none, or jac_sites is empty)")
         self._resolve_sensors(sensors)
         self._t = None      # the device tensors, made on first use
-        self._h = self._h_big = self.lane = self._p = self._frc = self._sns = None
+        self._h = self._h_big = self.lane = self._p = self._frc = self._sns = self._wrn = None
 
     # ------------------------------------------------------------------ names (CompiledModel.names / tables): no device needed
     def _lookup(self, kind, name):
@@ -279,8 +312,10 @@ class BatchedSim:
             raise ValueError(f"{who}: touch readings are served by outputs=('sensordata',) with compile_kwargs=dict(touch_filter=...)")
         if kind == "rangefinder":
             raise ValueError(f"{who}: rangefinders are served by sim.rangefinder()")
-        if kind in ("force", "torque"):
-            raise ValueError(f"{who}: force and torque sensors need cfrc_int / cfrc_ext, which the engine does not form")
+        if kind in _SENSOR_WRENCH and objtype != "site":
+            raise ValueError(f"{who}: force and torque sensors read cfrc_int of a site's body and are attached to a site")
+        if kind in _SENSOR_WRENCH and "cfrc_int" not in self.body_dynamics:
+            raise ValueError(f"{who}: force and torque sensors need cfrc_int / cfrc_ext, which this simulation forms only on request: name 'cfrc_int' in body_dynamics=")
         if kind not in SENSOR_TYPES:
             raise ValueError(f"{who}: this type is not served; the served types are {SENSOR_TYPES}")
         if rec["reftype"] is not None:
@@ -393,7 +428,8 @@ class BatchedSim:
                     site_xvelr=(n, self.nsite, 3), sensordata=(n, self.ntouch), ncon=(n,), nefc=(n,), qM=(n, self.nv, self.nv), site_jacp=(n, len(self._jac_ids), 3, self.nv),
                     site_jacr=(n, len(self._jac_ids), 3, self.nv), **{k: (n, self.nv) for k in DYNAMICS if k not in ("qM",) + JACOBIANS},
                     **{k: (n, self.contact_capacity) + _CONTACT_WIDTH[k] for k in CONTACTS},
-                    qfrc_applied=(n, self.nv), xfrc_applied=(n, self.nbody, 6), xipos=(n, self.nbody, 3))
+                    qfrc_applied=(n, self.nv), xfrc_applied=(n, self.nbody, 6), xipos=(n, self.nbody, 3),
+                    cfrc_ext=(n, self.nbody, 6), cfrc_int=(n, self.nbody, 6), cacc=(n, self.nbody, 6), subtree_com=(n, self.nbody, 3))
 
     def _ensure(self):
         if self._t is not None:
@@ -413,7 +449,7 @@ class BatchedSim:
         self.lds_bytes = self._L.grx_model_lds_bytes(self._h)
         shapes = self._shapes()
         t = {}
-        for k in STATE + self.outputs + self.contacts + self.applied:
+        for k in STATE + self.outputs + self.contacts + self.applied + self.body_dynamics:
             t[k] = torch.zeros(shapes[k], dtype=torch.int32 if k in _INT_TENSORS else torch.float32, device=self.device)
         t["status_words"] = torch.zeros(self.num_worlds, dtype=torch.int32, device=self.device)
         tb = self.model.tables
@@ -438,6 +474,8 @@ class BatchedSim:
             self._sns_host = (np.ascontiguousarray(self._sensor_spec, dtype=np.int32).reshape(-1, 4), np.ascontiguousarray(self._sensor_cut, dtype=np.float32))
             self._sns = _native.SimSensorsStruct(spec=self._sns_host[0].ctypes.data, cutoff=self._sns_host[1].ctypes.data, nsensor=len(self.sensors), ndata=self.nsensordata,
                                                  data=t["sensor_data"].data_ptr())
+        if self.body_dynamics:      # the sixth block, one for both launches (a force / torque sensor is served only next to cfrc_int)
+            self._wrn = _native.SimWrenchesStruct(**{k: t[k].data_ptr() for k in self.body_dynamics})
         if self.overflow == "rerun":
             self._h_big = create_rerun_model(self._L, self.model, dev_index, True)
             if self._h_big is not None:
@@ -471,7 +509,7 @@ class BatchedSim:
         if name in ("device", "lds_bytes"):      # known once the device side exists
             self._ensure()
             return self.__dict__[name]
-        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()) or name in self.__dict__.get("contacts", ()) or name in self.__dict__.get("applied", ()):
+        if name in STATE or name == "status_words" or name in self.__dict__.get("outputs", ()) or name in self.__dict__.get("contacts", ()) or name in self.__dict__.get("applied", ()) or name in self.__dict__.get("body_dynamics", ()):
             return self._ensure()[name]
         if name == "sensor_data":
             if not self.__dict__.get("sensors"):
@@ -486,6 +524,8 @@ class BatchedSim:
             raise AttributeError(f"output {name!r} was not requested: BatchedSim(..., outputs={self.__dict__.get('outputs', ())})")
         if name in APPLIED:
             raise AttributeError(f"{name!r} was not requested: BatchedSim(..., applied=...), any of {APPLIED}")
+        if name in BODY_DYNAMICS:
+            raise AttributeError(f"{name!r} was not requested: BatchedSim(..., body_dynamics=...), any of {BODY_DYNAMICS}")
         if name in CONTACTS:
             raise AttributeError(f"contact output {name!r} was not requested: BatchedSim(..., contacts={self.__dict__.get('contacts', ())})")
         raise AttributeError(name)

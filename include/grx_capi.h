@@ -496,6 +496,32 @@ int grx_sim_step_sns(const grx_model* m, const struct grx_sim_params* params, co
                      const grx_sim_sensors* sns, int n_worlds, int nstep, int forward_only, void* stream);
 /* host only: out[0] = sizeof(grx_sim_sensors), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (6) */
 int grx_sim_sensors_layout(long long* out, int cap);
+/* BODY WRENCHES, the sixth optional block: what mj_rnePostConstraint forms per body, from one post-constraint Newton-Euler pass per world inside the step launch.  Every
+ * pointer may be null; a requested buffer is written whole by each launch, rows are the compiled model's bodies as for xpos.
+ *   subtree_com [N,nbody,3]  data.subtree_com of the same pass as xpos (from xipos and the world's own committed body_mass; a massless subtree: xipos of its body)
+ *   cfrc_ext    [N,nbody,6]  torque then force, world orientation, about subtree_com[body_rootid[b]]: xfrc_applied[b] acting at xipos[b] plus every contact of the pass that
+ *                            has constraint rows, + on the body of the pair's second geom and - on the first (mj_contactForce's sign), each about its own body's root centre of
+ *                            mass: torque (contact_pos - com) x f plus the torsional term along the normal (condim >= 4) and the rolling terms along the tangents (condim 6).
+ *                            Row 0 (the world) receives the reactions of world-geom contacts.
+ *   cacc        [N,nbody,6]  the spatial acceleration in the same frame (angular, then linear): cacc[0] = (0, -gravity), cacc[b] = cacc[parent] + sum cdof_dot qvel + sum cdof
+ *                            qacc over b's own dofs
+ *   cfrc_int    [N,nbody,6]  sum over e in subtree(b) of cinert_e cacc_e + cvel_e x* (cinert_e cvel_e) - cfrc_ext_e: the wrench b's parent exerts on b through their joint
+ * DEVIATION: the forces of equality constraints (weld, connect, joint) are not added to cfrc_ext; recent MuJoCo releases add connect / weld forces there.
+ * WHICH PASS: that of qfrc_bias and the contact outputs -- the last forward pass of the launch, under RK4 the FOURTH stage's; after nstep = n the rows are those of a
+ * forward_only launch at the state nstep = n - 1 left.
+ * SENSORS: the types force (18) and torque (19) of the sensor table (spec[4 k] in grx_sim_sensors) are served by this call only: object a site, dim 3, cutoff clamps.
+ * With b the site's body, (tau, f) = cfrc_int[b], p / R the site's position / rotation and c = subtree_com[body_rootid[b]]: force = R' f, torque = R' (tau - (p - c) x f).
+ * They follow the sensor block's pass rule (Euler: the last pass; RK4: the FIRST stage of the last substep, which under RK4 is not the pass of the cfrc_int output).
+ * grx_sim_step_sns refuses a table that holds one.  A null wrn, or a block of nulls with no force / torque row in sns, launches exactly what grx_sim_step_sns launches for the
+ * other arguments (sns may be null here); otherwise kernels of their own run (translation units GRX_TU_SIMWRN / GRX_TU_SIMWRNPRM), which carry all six blocks.  The table is
+ * checked on the host before anything is uploaded, with the messages of grx_sim_step_sns ("grx_sim_step_sns: sensor k ..."): a force / torque row reads a site with an id in range. */
+typedef struct grx_sim_wrenches {
+  float *cfrc_ext, *cfrc_int, *cacc, *subtree_com;
+} grx_sim_wrenches;
+int grx_sim_step_wrn(const grx_model* m, const struct grx_sim_params* params, const grx_sim_buffers* buf, const grx_sim_dynamics* dyn, const grx_sim_contacts* con, const grx_sim_applied* frc,
+                     const grx_sim_sensors* sns, const grx_sim_wrenches* wrn, int n_worlds, int nstep, int forward_only, void* stream);
+/* host only: out[0] = sizeof(grx_sim_wrenches), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (5) */
+int grx_sim_wrenches_layout(long long* out, int cap);
 /* RAY CASTING against the worlds of the task-free stepper: mj_ray for R rays in each of N worlds, and the rangefinder rule (a ray from a site).  Not a step: the calls read
  * body poses the caller passes in -- the xpos / xquat rows a step launch wrote -- and the model handle's geom tables, and write dist / geom.  A simulation that casts no ray
  * calls nothing here.
