@@ -122,10 +122,15 @@ def combine(parts):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------
 # the description
-def J(type, name, pos=(0, 0, 0), axis=(0, 0, 1), ref=0.0, armature=0.01, damping=0.1, stiffness=0.0, springref=0.0, cls=None, omit=()):
-    """ref and springref of a hinge are in the case's angle unit; omit: the attributes a default class supplies (the values here are then the resolved ones)"""
+ROW_ATTRS = ("range", "margin", "solreflimit", "solimplimit", "frictionloss", "solreffriction", "solimpfriction")      # the constraint-row attributes of a joint (constraint_cases.py)
+
+
+def J(type, name, pos=(0, 0, 0), axis=(0, 0, 1), ref=0.0, armature=0.01, damping=0.1, stiffness=0.0, springref=0.0, cls=None, omit=(), **rows):
+    """ref, springref and range of a hinge are in the case's angle unit; omit: the attributes a default class supplies (the values here are then the resolved ones);
+    rows: any of ROW_ATTRS, written to the MJCF as they are (a range makes the joint limited)"""
+    assert set(rows) <= set(ROW_ATTRS), rows
     return dict(type=type, name=name, pos=rd(pos), axis=rd(axis), ref=float(ref), armature=float(armature), damping=float(damping), stiffness=float(stiffness), springref=float(springref),
-                cls=cls, omit=tuple(omit))
+                cls=cls, omit=tuple(omit), rows={k: (float(v) if np.ndim(v) == 0 else tuple(float(x) for x in v)) for k, v in rows.items()})
 
 
 def G(type, size, pos=(0, 0, 0), ori=None, density=1000.0, mass=None, fromto=None, cls=None, omit=()):
@@ -142,8 +147,12 @@ def B(name, parent, pos=(0, 0, 0), ori=None, joints=(), geoms=(), inertial=None,
 
 
 class Case:
-    def __init__(self, name, seed, bodies, angle="radian", eulerseq="xyz", defaults="", vscale=3.0, spin=None):
+    def __init__(self, name, seed, bodies, angle="radian", eulerseq="xyz", defaults="", vscale=3.0, spin=None, tendons=(), equalities=(), actuators=(), integrator="Euler",
+                 timestep=TIMESTEP):
+        """tendons: dict(joints [(joint, coef)], range, margin, solref, solimp); equalities: dict(joint1, joint2, polycoef, solref, solimp, active); actuators: dict(tag
+        "motor" / "position" / "velocity" / "general", joint, gear, kp / kv or gain and bias [3], ctrlrange, forcerange) -- the input of tests/constraint_refs.py"""
         self.name, self.seed, self.bodies, self.angle, self.eulerseq, self.defaults, self.vscale, self.spin = name, seed, bodies, angle, eulerseq, defaults, vscale, spin
+        self.tendons, self.equalities, self.actuators, self.integrator, self.timestep = list(tendons), list(equalities), list(actuators), integrator, timestep
         self.scale = np.pi / 180.0 if angle == "degree" else 1.0
         self._tree = self._model = self._states = None
         names = [b["name"] for b in bodies]
@@ -196,11 +205,20 @@ class Case:
                     a = self.scale if j["type"] == "hinge" else 1.0
                     ax = np.asarray(j["axis"], dtype=np.float64)
                     joints.append(dict(type=j["type"], name=j["name"], pos=j["pos"], axis=ax / np.linalg.norm(ax), ref=j["ref"] * a, armature=j["armature"], damping=j["damping"],
-                                       stiffness=j["stiffness"], springref=j["springref"] * a))
+                                       stiffness=j["stiffness"], springref=j["springref"] * a, **{k: (tuple(a * x for x in v) if k == "range" else v) for k, v in j.get("rows", {}).items()}))
                 out.append(dict(name=b["name"], parent=-1 if b["parent"] is None else idx[b["parent"]], pos=b["pos"], quat=ori_quat(b["ori"], self.scale, self.eulerseq), joints=joints,
                                 mass=m, ipos=c, inertia=I, sites=[dict(name=s["name"], pos=s["pos"], quat=ori_quat(s["ori"], self.scale, self.eulerseq)) for s in b["sites"]]))
-            self._tree = dict(gravity=GRAVITY, timestep=TIMESTEP, bodies=out)
+            self._tree = dict(gravity=GRAVITY, timestep=self.timestep, bodies=out)
+            if self.tendons or self.equalities or self.actuators or self.integrator != "Euler":
+                self._tree.update(tendons=self.tendons, equalities=self.equalities, actuators=[self._actuator(a) for a in self.actuators], integrator=self.integrator)
         return self._tree
+
+    @staticmethod
+    def _actuator(a):
+        """the documented meaning of the actuator shortcuts: <motor> gain 1; <position kp> gain kp, bias (0, -kp, 0); <velocity kv> gain kv, bias (0, 0, -kv)"""
+        gain, bias = {"motor": lambda: (1.0, (0.0, 0.0, 0.0)), "position": lambda: (a["kp"], (0.0, -a["kp"], 0.0)), "velocity": lambda: (a["kv"], (0.0, 0.0, -a["kv"])),
+                      "general": lambda: (a["gain"], tuple(a["bias"]))}[a["tag"]]()
+        return dict(joint=a["joint"], gear=a.get("gear", 1.0), gain=gain, bias=bias, ctrlrange=a.get("ctrlrange"), forcerange=a.get("forcerange"))
 
     # -- the MJCF ------------------------------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -223,6 +241,9 @@ class Case:
                 continue
             a = dict(type=j["type"], pos=self._num(j["pos"]), axis=self._num(j["axis"]), ref=self._num(j["ref"]), armature=self._num(j["armature"]), damping=self._num(j["damping"]),
                      stiffness=self._num(j["stiffness"]), springref=self._num(j["springref"]))
+            a.update({n: self._num(v) for n, v in j.get("rows", {}).items()})
+            if "range" in j.get("rows", {}):
+                a["limited"] = "true"
             cls = f' class="{j["cls"]}"' if j["cls"] else ""
             out.append(f'<joint name="{j["name"]}"{cls} ' + " ".join(f'{n}="{v}"' for n, v in a.items() if n not in j["omit"]) + "/>")
         for g in b["geoms"]:
@@ -240,11 +261,35 @@ class Case:
         out += [self._body_xml(c) for c in range(len(self.bodies)) if self.bodies[c]["parent"] == b["name"]]
         return "".join(out) + "</body>"
 
+    def _sections_xml(self):
+        """<equality>, <tendon> and <actuator>, each only if the case has entries (the trees of the smooth-dynamics cases have none)"""
+        opt = lambda d, *keys: "".join(f' {k}="{self._num(d[k])}"' for k in keys if d.get(k) is not None)
+        out = ""
+        if self.equalities:
+            out += "<equality>" + "".join(f'<joint joint1="{e["joint1"]}" joint2="{e["joint2"]}" polycoef="{self._num(e["polycoef"])}"{opt(e, "solref", "solimp")}'
+                                          + ("" if e.get("active", True) else ' active="false"') + "/>" for e in self.equalities) + "</equality>"
+        if self.tendons:
+            lim = lambda t: "".join(f' {k}limit="{self._num(t[k])}"' for k in ("solref", "solimp") if k in t)
+            out += "<tendon>" + "".join(f'<fixed limited="true" range="{self._num(t["range"])}"{opt(t, "margin")}{lim(t)}>'
+                                        + "".join(f'<joint joint="{j}" coef="{c!r}"/>' for j, c in t["joints"]) + "</fixed>" for t in self.tendons) + "</tendon>"
+        if self.actuators:
+            acts = []
+            for a in self.actuators:
+                own = {"motor": "", "position": f' kp="{a.get("kp")!r}"', "velocity": f' kv="{a.get("kv")!r}"'}.get(a["tag"])
+                if own is None:
+                    own = f' gainprm="{a["gain"]!r} 0 0" biastype="affine" biasprm="{self._num(a["bias"])}"'
+                lims = (f' ctrllimited="true" ctrlrange="{self._num(a["ctrlrange"])}"' if a.get("ctrlrange") is not None else "") + (
+                    f' forcelimited="true" forcerange="{self._num(a["forcerange"])}"' if a.get("forcerange") is not None else "")
+                acts.append(f'<{a["tag"]} joint="{a["joint"]}" gear="{float(a.get("gear", 1.0))!r}"{own}{lims}/>')
+            out += "<actuator>" + "".join(acts) + "</actuator>"
+        return out
+
     @property
     def xml(self):
         roots = "".join(self._body_xml(k) for k, b in enumerate(self.bodies) if b["parent"] is None)
-        return (f'<mujoco><compiler angle="{self.angle}" eulerseq="{self.eulerseq}"/><option timestep="{TIMESTEP!r}" gravity="{self._num(GRAVITY)}"/>{self.defaults}'
-                f"<worldbody>{roots}</worldbody></mujoco>")
+        integ = "" if self.integrator == "Euler" else f' integrator="{self.integrator}"'
+        return (f'<mujoco><compiler angle="{self.angle}" eulerseq="{self.eulerseq}"/><option timestep="{self.timestep!r}"{integ} gravity="{self._num(GRAVITY)}"/>{self.defaults}'
+                f"<worldbody>{roots}</worldbody>{self._sections_xml()}</mujoco>")
 
     @property
     def model(self):

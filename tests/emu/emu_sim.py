@@ -10,6 +10,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.abspath(os.path.join(_HERE, "..", ".."))
 
 
+def build_from(root, so, flags=("-O2",)):
+    """the emulator of ANOTHER tree (a patched copy of tests/emu/grx_emu.cpp, gymnasium_robotics_amd/csrc and include under `root`) as the library `so`: mutation tests"""
+    subprocess.check_call(["g++", *flags, "-fPIC", "-shared", "-std=c++17", "-Wno-misleading-indentation", "-o", so, os.path.join(root, "tests", "emu", "grx_emu.cpp")])
+    return so
+
+
 def build(force=False):
     so = os.path.join(_HERE, "libgrx_emu.so")
     import glob
@@ -31,9 +37,9 @@ def build(force=False):
 
 
 class EmuSim:
-    def __init__(self, model, task_struct):
+    def __init__(self, model, task_struct, lib=None):
         self.model, self.task = model, task_struct
-        self.L = ctypes.CDLL(build())
+        self.L = ctypes.CDLL(lib or build())
         self.L.emu_create.restype = ctypes.c_void_p
         self.L.emu_create.argtypes = [ctypes.c_void_p] * 3
         self.L.emu_ctx_ptr.restype = ctypes.POINTER(ctypes.c_float)
