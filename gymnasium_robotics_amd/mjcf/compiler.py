@@ -469,6 +469,7 @@ class MjcfCompiler:
         self.inertiagrouprange = (0, 5)
         self.bodies: List[_Body] = []
         self.meshes: Dict[str, Dict[str, object]] = {}
+        self.cameras: List[Dict[str, object]] = []
         self.opt = dict(timestep=0.002, gravity=np.array([0, 0, -9.81]), tolerance=1e-8, impratio=1.0,
                         integrator=0, iterations=100, cone=0, noslip_iterations=0, eulerdamp=1, mpr_tolerance=1e-6, mpr_iterations=50,
                         noslip_tolerance=1e-6)
@@ -585,6 +586,8 @@ class MjcfCompiler:
                 body.geoms.append(self._parse_geom(ch, childclass, bid))
             elif ch.tag == "site":
                 body.sites.append(self._parse_site(ch, childclass, bid))
+            elif ch.tag == "camera":
+                self.cameras.append(self._parse_camera(ch, childclass, bid))
         for ch in elem:
             if ch.tag == "body":
                 self._parse_body(ch, bid, childclass)
@@ -684,6 +687,13 @@ class MjcfCompiler:
             quat = mu.zaxis2quat(ft[3:] - ft[:3])
             size = np.array([size[0], 0.5 * np.linalg.norm(ft[3:] - ft[:3]), 0.0])
         return _Site(name=a.get("name", ""), type=st, pos=pos, quat=quat, size=size, body=bid)
+
+    def _parse_camera(self, elem, childclass, bid) -> Dict[str, object]:
+        """one <camera>: bookkeeping only (info["camera"]); the pose is in the frame of body `bid` until the lowering has fused the static bodies"""
+        a = self._attrs(elem, "camera", childclass)
+        res = a.get("resolution")
+        return dict(elem=elem, name=a.get("name", ""), body=bid, pos=_floats(a.get("pos"), 3, [0, 0, 0]), quat=self._orientation(a), fovy=float(a.get("fovy", 45.0)),
+                    mode=a.get("mode", "fixed"), target=a.get("target"), resolution=None if res is None else [int(x) for x in res.split()])
 
     # -- mesh hulls -----------------------------------------------------------------
     def _load_mesh_hull(self, name: str):
@@ -803,6 +813,8 @@ class MjcfCompiler:
                     world.geoms.append(self._parse_geom(ch, None, 0))
                 elif ch.tag == "site":
                     world.sites.append(self._parse_site(ch, None, 0))
+                elif ch.tag == "camera":
+                    self.cameras.append(self._parse_camera(ch, None, 0))
             for ch in wb:
                 if ch.tag == "body":
                     self._parse_body(ch, 0, None)
@@ -813,6 +825,9 @@ class MjcfCompiler:
                 g.pos = g.pos - self.origin
             for st in world.sites:
                 st.pos = st.pos - self.origin
+            for cam in self.cameras:
+                if cam["body"] == 0:
+                    cam["pos"] = cam["pos"] - self.origin
             for b in self.bodies[1:]:
                 if b.parent == 0:
                     b.pos = b.pos - self.origin
@@ -1249,6 +1264,16 @@ class _Lowering:
             site_pos[si] = p + mu.rot_vec(q, s.pos)
             site_quat[si] = mu.quat_normalize(mu.quat_mul(q, s.quat))
             site_size[si] = s.size
+        # <camera> elements of the worldbody tree, in document order: bookkeeping only (names["camera"]: name -> row, info["camera"]: one dict per row with the surviving
+        # body and the pose in its frame, composed through the fused static bodies as a site's is).  Nothing of it is packed: BatchedSim.render reads it (sim.py)
+        order = {id(e): k for k, e in enumerate(c.root.iter("camera"))}
+        cams = sorted(c.cameras, key=lambda cam: order[id(cam["elem"])])
+        names["camera"], info["camera"] = {}, []
+        for ci, cam in enumerate(cams):
+            k, p, q = anchor_of(cam["body"])
+            names["camera"][cam["name"] or f"_camera{ci}"] = ci
+            info["camera"].append(dict(body=int(new_id[k]), pos=(p + mu.rot_vec(q, cam["pos"])).tolist(), quat=mu.quat_normalize(mu.quat_mul(q, cam["quat"])).tolist(),
+                                       fovy=cam["fovy"], mode=cam["mode"], target=cam["target"], resolution=cam["resolution"]))
         # <rangefinder> sensors, in sensor order: bookkeeping only (names["rangefinder"]: name -> row, info["rangefinder"]: site name and cutoff per row).  Nothing of it is
         # packed: BatchedSim.rangefinder casts one ray per row from the named site (sim.py), and is where a sensor without a usable site is reported
         finders = [e for sec in c.root.findall("sensor") for e in sec.findall("rangefinder")]

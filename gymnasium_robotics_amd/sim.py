@@ -120,8 +120,26 @@ it rather than cast through it.  The calls run a kernel of their own (grx_sim_ra
     sim.step(nstep=5)
     dist, geom = sim.ray_sites("lidar", fan, max_dist=10.0)                                        # [N, 64]
 
+CAMERAS (depth and segmentation): ``sim.render(cameras, height, width)`` returns ``depth [N, K, H, W]`` float32 for K ``<camera>`` elements of the MJCF (a name or a sequence of
+names, at most 16 per call, 1 <= H, W <= 1024); ``segmentation=True`` returns ``(depth, seg)`` with ``seg`` int32 the id of the geom seen.  MuJoCo's conventions: a camera looks along
+-z of its frame, +x right, +y up, row 0 is the top row, and the centre of pixel (r, c) has the camera-frame direction ``((2 (c + .5) / W - 1) tan(fovy / 2) W / H,
+(1 - 2 (r + .5) / H) tan(fovy / 2), -1)``.  ``depth`` is the PLANAR depth, metres along the optical axis (the ray parameter along that direction); the Euclidean range is depth times
+the direction's length.  No hit, or one deeper than a positive ``max_dist``: -1.0 / -1.  ``sim.render_pose(pos, xmat, fovy, height, width)`` is the same for cameras the caller
+places (``pos`` [N, K, 3] or [K, 3], ``xmat`` [N, K, 9] or [K, 9] as ``site_xmat`` is, ``fovy`` a float or K of them).  ``exclude_own_body`` skips the geoms of each camera's body,
+``exclude_body`` (one per camera, -1: none) those of another, ``include_static=False`` the world body's; ``mask`` renders only the worlds with a non-zero entry (the others read -1 in
+fresh tensors and keep their bits in ``out=``).  A named camera sees the body poses of the LAST launch, as a ray does -- ``outputs`` must name ``xpos`` and ``xquat`` -- exact after
+``forward()``, one substep stale after ``step()``.  ``sim.camera_id(name)`` is the row in ``model.info["camera"]`` (body, pose in the body's frame, fovy, mode, resolution; unnamed
+cameras are ``_camera{k}``); ``sim.cameras_unserved`` maps the cameras whose ``mode`` is not ``fixed`` (``track*``, ``target*``) to the reason.  A kernel of its own (grx_sim_render): one
+workgroup per image bins the geoms' bounding spheres to screen tiles once and each tile tests only what may touch it (``binning=False`` gives every tile every geom: the same image
+bit for bit).  Deviations from MuJoCo's renderer: collidable geoms only, meshes as their convex hulls, no geom groups, no near-plane clipping (a surface 1 mm in front of the camera
+is seen), no ``track`` / ``target`` modes, no colour: this is depth and geom id.
+
+    sim = grx.BatchedSim("quadruped.xml", 4096, outputs=("xpos", "xquat"))
+    sim.step(nstep=5)
+    depth = sim.render("head_cam", 64, 64, exclude_own_body=True, max_dist=10.0)                   # [N, 1, 64, 64]
+
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, cameras.
+equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, colour images, tracking and targeting cameras.
 """
 import ctypes
 
@@ -155,6 +173,8 @@ _SENSOR_JOINT, _SENSOR_ACTUATOR, _SENSOR_SITE_ONLY = ("jointpos", "jointvel", "j
 _SENSOR_WRENCH = ("force", "torque")      # read cfrc_int: served where body_dynamics names it
 _SENSOR_NO_CUTOFF = ("framequat", "framexaxis", "frameyaxis", "framezaxis")
 MAXJAC = 16      # GRX_SIM_MAXJAC: the site selection rides inside the launch's argument block
+MAXCAM = 16      # GRX_CAM_MAX: the cameras of one render call ride there as well
+MAXSIDE = 1024   # GRX_CAM_MAX_SIDE: largest image height / width
 
 
 def _table_maxcon(req):
@@ -762,6 +782,112 @@ class BatchedSim:
         if mask is not None:
             beyond &= self._mask(mask).bool()[:, None]
         return dist.masked_fill_(beyond, -1.0)
+
+    # ------------------------------------------------------------------ cameras (include/grx_capi.h grx_sim_render; module docstring, CAMERAS)
+    def camera_id(self, name):
+        """row of the <camera> `name` in model.info["camera"]"""
+        return self._lookup("camera", name)
+
+    @property
+    def cameras_unserved(self):
+        """name -> reason for the MJCF's cameras render() does not serve: the ones whose mode is not `fixed`"""
+        rows = self.model.info.get("camera", ())
+        return {name: f'mode="{rows[k]["mode"]}": render() serves fixed cameras only (a tracking or targeting camera turns with the scene; place it with render_pose())'
+                for name, k in self.model.names.get("camera", {}).items() if rows[k]["mode"] != "fixed"}
+
+    def _render(self, what, n_cams, height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill):
+        """the checks and the launch both render calls share; fill(block, t) -> what to keep alive: sets the block's camera poses once the device tensors exist"""
+        import torch
+
+        from . import _native
+        from .core import stream_ptr
+
+        if not 1 <= n_cams <= MAXCAM:
+            raise ValueError(f"{what} takes 1 .. {MAXCAM} cameras per call, not {n_cams}")
+        height, width = int(height), int(width)
+        if not (1 <= height <= MAXSIDE and 1 <= width <= MAXSIDE):
+            raise ValueError(f"{what}: height x width = {height} x {width} is outside 1 .. {MAXSIDE}")
+        if tile not in (None, "16x4", "8x8"):
+            raise ValueError(f'{what}: tile is "16x4" or "8x8", not {tile!r}')
+        fovy = [float(fovy)] * n_cams if isinstance(fovy, (int, float, np.floating, np.integer)) else [float(f) for f in fovy]
+        if len(fovy) != n_cams or not all(0.0 < f < 180.0 for f in fovy):
+            raise ValueError(f"{what}: fovy is one angle or {n_cams} of them, in degrees inside (0, 180), not {fovy}")
+        if exclude_body is None:
+            exclude = [-1] * n_cams
+        elif isinstance(exclude_body, (str, int, np.integer)):
+            exclude = [exclude_body] * n_cams
+        else:
+            exclude = list(exclude_body)
+        exclude = [self.body_id(b) if isinstance(b, str) else int(b) for b in exclude]
+        if len(exclude) != n_cams:
+            raise ValueError(f"{what}: exclude_body must be one body or name {n_cams} of them (-1: none), not {len(exclude)}")
+        self._ray_need(what, ("xpos", "xquat"))
+        t = self._ensure()
+        m = self._mask(mask)
+        shape = (self.num_worlds, n_cams, height, width)
+        if out is None:      # fresh tensors start as "no hit", which is what the images of masked-out worlds then read
+            depth = torch.full(shape, -1.0, dtype=torch.float32, device=self.device)
+            seg = torch.full(shape, -1, dtype=torch.int32, device=self.device) if segmentation else None
+        else:
+            depth, seg = out if segmentation else (out, None)
+            for x, dt in ((depth, torch.float32),) + (((seg, torch.int32),) if segmentation else ()):
+                if not torch.is_tensor(x) or x.shape != shape or x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                    raise ValueError(f"out= takes a contiguous float32 tensor{' and an int32 tensor' if segmentation else ''} of shape {shape} on {self.device}")
+        host = ((ctypes.c_float * n_cams)(*fovy), (ctypes.c_int * n_cams)(*exclude))
+        b = _native.SimCamerasStruct(xpos=t["xpos"].data_ptr(), xquat=t["xquat"].data_ptr(), cam_fovy=ctypes.cast(host[0], ctypes.c_void_p), exclude_body=ctypes.cast(host[1], ctypes.c_void_p),
+                                     mask=None if m is None else m.data_ptr(), depth=depth.data_ptr(), seg=None if seg is None else seg.data_ptr(), max_dist=float(max_dist),
+                                     include_static=int(bool(include_static)), no_binning=int(not binning), tile_16x4=int(tile == "16x4"))
+        self._ray_keep = (fill(b, t), m, host)      # alive until the next ray or camera call has replaced them (the launch is only enqueued)
+        with torch.cuda.device(self.device):
+            _native.check(self._L.grx_sim_render(self._h, ctypes.byref(b), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
+        return (depth, seg) if segmentation else depth
+
+    def render(self, cameras, height, width, segmentation=False, exclude_own_body=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None):
+        """Depth images of the MJCF's cameras: `cameras` a <camera> name or a sequence of K of them (at most 16 per call).  Returns depth [N, K, height, width] float32, the planar
+        depth in metres along each camera's optical axis (module docstring, CAMERAS); with segmentation=True (depth, seg), seg int32 the id of the geom seen (sim.geom_id).  No
+        hit, or one deeper than max_dist (when positive): -1.0 / -1.  exclude_own_body skips the geoms of each camera's body, exclude_body (one body or K, names or ids, -1:
+        none) those of another; include_static=False the world body's.  mask: only the worlds with a non-zero entry are rendered; the images of the others read -1 in fresh
+        tensors and keep their bits in out= (a depth tensor, or (depth, seg) with segmentation).  binning=False gives every screen tile every geom and tile="16x4" traces wide
+        tiles instead of 8 x 8: the same image bit for bit, for A/B timing.  Sees the xpos / xquat of the LAST launch (exact after forward(), one substep stale after step()).  Enqueues on
+        torch's current stream; never synchronises."""
+        names = [cameras] if isinstance(cameras, str) else list(cameras)
+        rows = [self.model.info["camera"][self.camera_id(n)] for n in names]
+        unserved = self.cameras_unserved
+        for n in names:
+            if n in unserved:
+                raise ValueError(f"camera {n!r}: {unserved[n]}")
+
+        def fill(b, t):
+            host = ((ctypes.c_int * len(rows))(*[r["body"] for r in rows]), (ctypes.c_float * (3 * len(rows)))(*[x for r in rows for x in r["pos"]]),
+                    (ctypes.c_float * (4 * len(rows)))(*[x for r in rows for x in r["quat"]]))
+            b.cam_body, b.cam_pos, b.cam_quat = (ctypes.cast(h, ctypes.c_void_p) for h in host)
+            b.exclude_own_body = int(bool(exclude_own_body))
+            return host
+
+        return self._render("render()", len(rows), height, width, [r["fovy"] for r in rows], segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill)
+
+    def render_pose(self, pos, xmat, fovy, height, width, segmentation=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None):
+        """render() for cameras the caller places: pos [N, K, 3] or [K, 3] (the same cameras in every world), xmat [N, K, 9] or [K, 9] the camera frames' rotations (camera ->
+        world, row-major as site_xmat is: the columns are the camera's right, up and backward axes), fovy one angle or K in degrees.  The other arguments and the result are
+        those of render(); there is no body of its own to exclude."""
+        import torch
+
+        self._ray_need("render_pose()", ("xpos", "xquat"))
+        self._ensure()
+        p, x = (torch.as_tensor(v, device=self.device).to(torch.float32) for v in (pos, xmat))
+        if p.dim() == 2:
+            p = p.expand((self.num_worlds,) + tuple(p.shape))
+        if x.dim() == 2:
+            x = x.expand((self.num_worlds,) + tuple(x.shape))
+        if p.dim() != 3 or x.dim() != 3 or p.shape[0] != self.num_worlds or p.shape[2] != 3 or x.shape != (self.num_worlds, p.shape[1], 9):
+            raise ValueError(f"pos must have shape ({self.num_worlds}, K, 3) or (K, 3) and xmat ({self.num_worlds}, K, 9) or (K, 9), not {tuple(p.shape)} and {tuple(x.shape)}")
+        p, x = p.contiguous(), x.contiguous()
+
+        def fill(b, t):
+            b.pose_pos, b.pose_mat = p.data_ptr(), x.data_ptr()
+            return (p, x)
+
+        return self._render("render_pose()", int(p.shape[1]), height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill)
 
     # ------------------------------------------------------------------ status words (include/grx_capi.h grx_status_bits), as the env classes report them
     @property

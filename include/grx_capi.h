@@ -559,6 +559,39 @@ int grx_sim_ray(const grx_model* m, const grx_sim_rays* r, int n_worlds, int n_r
 int grx_sim_ray_sites(const grx_model* m, const grx_sim_rays* r, int n_worlds, int n_rays, void* stream);
 /* host only: out[0] = sizeof(grx_sim_rays), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (16) */
 int grx_sim_rays_layout(long long* out, int cap);
+/* CAMERAS of the task-free stepper: a depth image and, optionally, a segmentation image (the id of the geom seen) of H x W pixels for each of K cameras in each of N
+ * worlds, over the geoms, with the hit rule, the filters and the cached hull planes of the ray calls above (so the same model refusals).  Not a step and not state.
+ *   CONVENTIONS  MuJoCo's: a camera looks along -z of its frame, +x right, +y up; row 0 is the top row; the centre of pixel (r, c) has the camera-frame direction
+ *           ((2 (c + .5) / W - 1) tan(fovy / 2) W / H, (1 - 2 (r + .5) / H) tan(fovy / 2), -1).  depth is the ray parameter of the nearest hit along that direction: the
+ *           PLANAR depth, metres along the optical axis (the Euclidean range is depth * |direction|).  No hit, or one beyond max_dist (> 0, in depth): -1.0f / -1.
+ *   POSES   either the cameras ride on bodies -- cam_body / cam_pos / cam_quat, HOST tables of K rows read during the call: the camera's frame is x_body o (cam_pos,
+ *           cam_quat) with the xpos / xquat passed in -- or the caller places them: pose_pos [N,K,3] and pose_mat [N,K,9] (a rotation, camera -> world, row-major) in DEVICE
+ *           memory, chosen when pose_pos != NULL.  cam_fovy [K] (HOST, degrees, inside (0, 180)) serves both.  A camera with a non-finite pose sees nothing.
+ *   FILTERS exclude_body [K] (HOST, a compiled body id per camera, -1: none; NULL: none); exclude_own_body != 0 skips the geoms of cam_body (body cameras only);
+ *           include_static == 0 skips the geoms of body 0.  no_binning != 0 gives every screen tile every geom (the image is the same bit for bit; for A/B timing);
+ *           tile_16x4 != 0 traces 16 x 4 pixel tiles instead of 8 x 8 (likewise).
+ * Every pixel of an unmasked world is written; a masked-out world's images keep their bits.  The call enqueues one launch and never waits (but for the one-time hull plane
+ * upload of the ray calls).  Return -1 (grx_last_error) for a NULL model, block, pose or depth pointer, neither kind of camera pose given, a NULL cam_fovy or a fovy outside
+ * (0, 180), n_worlds < 1, n_cams outside 1 .. 16, height or width outside 1 .. 1024, a cam_body outside [0, nbody), a zero cam_quat, and the models the ray calls refuse. */
+typedef struct grx_sim_cameras {
+  const float *xpos, *xquat;               /* [N,nbody,3] [N,nbody,4]: the body poses to render against */
+  const int* cam_body;                     /* [K] HOST: compiled body ids */
+  const float *cam_pos, *cam_quat;         /* [K,3] [K,4] HOST: the camera in its body's frame */
+  const float* cam_fovy;                   /* [K] HOST: vertical field of view, degrees */
+  const float *pose_pos, *pose_mat;        /* [N,K,3] [N,K,9] DEVICE, or NULL: the body cameras above */
+  const int* exclude_body;                 /* [K] HOST or NULL */
+  const unsigned char* mask;               /* [N] or NULL */
+  float* depth;                            /* [N,K,H,W] */
+  int* seg;                                /* [N,K,H,W] or NULL */
+  float max_dist;                          /* > 0: deeper hits count as none */
+  int include_static;                      /* 0: skip the geoms of body 0 */
+  int exclude_own_body;                    /* != 0: skip the geoms of each camera's cam_body */
+  int no_binning;                          /* != 0: every tile tests every geom */
+  int tile_16x4;                           /* != 0: 16 x 4 tiles instead of 8 x 8 */
+} grx_sim_cameras;
+int grx_sim_render(const grx_model* m, const grx_sim_cameras* c, int n_worlds, int n_cams, int height, int width, void* stream);
+/* host only: out[0] = sizeof(grx_sim_cameras), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (18) */
+int grx_sim_cameras_layout(long long* out, int cap);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)
