@@ -100,6 +100,11 @@ class SimCamerasStruct(ctypes.Structure):       # include/grx_capi.h, grx_sim_ca
         ("max_dist", ctypes.c_float)] + [(n, ctypes.c_int) for n in ("include_static", "exclude_own_body", "no_binning", "tile_16x4")]
 
 
+class SimShadeStruct(ctypes.Structure):         # include/grx_capi.h, grx_sim_shade; checked against grx_sim_shade_layout when the library loads
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rgba", "normal", "colors")] + [("colors_per_world", ctypes.c_int), ("ambient", ctypes.c_float), ("diffuse", ctypes.c_float),
+                                                                               ("sun", ctypes.c_float * 3), ("sun_diffuse", ctypes.c_float), ("background", ctypes.c_float * 3)]
+
+
 class KitchenBookStruct(ctypes.Structure):      # include/grx_capi.h, grx_kitchen_book
     _fields_ = [(n, ctypes.c_void_p) for n in ("completed", "stepped", "tasks_to_complete", "episode_completions", "elapsed", "step_completions", "reward", "terminated",
                                                "truncated", "needs_reset", "reset_now", "qpos", "qvel", "qacc_ws", "init_qpos")] + [
@@ -209,10 +214,13 @@ def lib():
         L.grx_sim_rays_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
         L.grx_sim_render.argtypes = [vp, vp, ci, ci, ci, ci, vp]
         L.grx_sim_cameras_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
-        want = [ctypes.sizeof(SimCamerasStruct)] + [getattr(SimCamerasStruct, f).offset for f, _ in SimCamerasStruct._fields_]
-        got = (ctypes.c_longlong * len(want))()
-        if L.grx_sim_cameras_layout(got, len(want)) != len(want) or list(got) != want:
-            raise RuntimeError(f"_native.SimCamerasStruct does not mirror grx_sim_cameras of {LIB_PATH} (a stale build?): rebuild with __graft_entry__.build(force=True)")
+        L.grx_sim_render_rgb.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+        L.grx_sim_shade_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
+        for struct, layout, name in ((SimCamerasStruct, L.grx_sim_cameras_layout, "grx_sim_cameras"), (SimShadeStruct, L.grx_sim_shade_layout, "grx_sim_shade")):
+            want = [ctypes.sizeof(struct)] + [getattr(struct, f).offset for f, _ in struct._fields_]
+            got = (ctypes.c_longlong * len(want))()
+            if layout(got, len(want)) != len(want) or list(got) != want:
+                raise RuntimeError(f"_native.{struct.__name__} does not mirror {name} of {LIB_PATH} (a stale build?): rebuild with __graft_entry__.build(force=True)")
         L.grx_sim_params_create.argtypes = [vp, vp, ci, ctypes.POINTER(ctypes.c_char_p), ci, ctypes.POINTER(vp)]
         L.grx_sim_params_destroy.argtypes = [vp]
         L.grx_sim_params_row.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(ci)]
@@ -284,7 +292,7 @@ def check(rc: int):
 
 EXPORTED_SYMBOLS = [
     "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_hull_pair_records", "grx_model_dim",
-    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sim_step", "grx_sim_layout", "grx_sim_step_dyn", "grx_sim_dynamics_layout", "grx_sim_step_con", "grx_sim_contacts_layout", "grx_sim_step_frc", "grx_sim_applied_layout", "grx_sim_step_sns", "grx_sim_sensors_layout", "grx_sim_step_wrn", "grx_sim_wrenches_layout", "grx_sim_ray", "grx_sim_ray_sites", "grx_sim_rays_layout", "grx_sim_render", "grx_sim_cameras_layout", "grx_sim_params_create", "grx_sim_params_destroy", "grx_sim_params_row", "grx_sim_params_commit", "grx_sim_step_params", "grx_sim_params_names", "grx_sim_params_records", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
+    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sim_step", "grx_sim_layout", "grx_sim_step_dyn", "grx_sim_dynamics_layout", "grx_sim_step_con", "grx_sim_contacts_layout", "grx_sim_step_frc", "grx_sim_applied_layout", "grx_sim_step_sns", "grx_sim_sensors_layout", "grx_sim_step_wrn", "grx_sim_wrenches_layout", "grx_sim_ray", "grx_sim_ray_sites", "grx_sim_rays_layout", "grx_sim_render", "grx_sim_cameras_layout", "grx_sim_render_rgb", "grx_sim_shade_layout", "grx_sim_params_create", "grx_sim_params_destroy", "grx_sim_params_row", "grx_sim_params_commit", "grx_sim_step_params", "grx_sim_params_names", "grx_sim_params_records", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
     "grx_normstat_geometry", "grx_normstat_layout", "grx_normstat_update", "grx_normstat_refresh", "grx_normstat_apply_batch", "grx_normstat_apply_packed",
 ]
 

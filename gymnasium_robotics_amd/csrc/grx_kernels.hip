@@ -1394,6 +1394,8 @@ static int g_slot_used[GRX_MAX_MODELS];
 extern "C" int grx_tu_rays_launch(const GrxRayArgs* a, void* stream);   // csrc/grx_rays.hip, a unit of its own
 #include "grx_camera.h"
 extern "C" int grx_tu_camera_launch(const GrxCamArgs* a, void* stream);   // csrc/grx_camera.hip, likewise
+#include "grx_shade.h"
+extern "C" int grx_tu_camera_rgb_launch(const GrxCamRgbArgs* s, void* stream);   // csrc/grx_camera_rgb.hip, likewise
 
 struct grx_model {
   GrxPackedModel pm;
@@ -1727,6 +1729,7 @@ extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, con
 }
 #include "grx_rays_api.h"
 #include "grx_camera_api.h"
+#include "grx_camera_rgb_api.h"
 #include "grx_sensors_api.h"
 // sizeof(grx_sim_applied) and the byte offset of every member, in declaration order: what _native.SimAppliedStruct must mirror (host only)
 extern "C" int grx_sim_applied_layout(long long* out, int cap) {

@@ -235,6 +235,8 @@ class _Geom:
     group: int
     mesh: Optional[str]
     body: int = -1
+    rgba: Optional[np.ndarray] = None      # the geom's own (or its default class's) rgba, if any; with `material`: bookkeeping only (info["geom_rgba"])
+    material: Optional[str] = None
 
 
 @dataclass
@@ -469,6 +471,7 @@ class MjcfCompiler:
         self.inertiagrouprange = (0, 5)
         self.bodies: List[_Body] = []
         self.meshes: Dict[str, Dict[str, object]] = {}
+        self.materials: Dict[str, np.ndarray] = {}
         self.cameras: List[Dict[str, object]] = []
         self.opt = dict(timestep=0.002, gravity=np.array([0, 0, -9.81]), tolerance=1e-8, impratio=1.0,
                         integrator=0, iterations=100, cone=0, noslip_iterations=0, eulerdamp=1, mpr_tolerance=1e-6, mpr_iterations=50,
@@ -552,6 +555,10 @@ class MjcfCompiler:
                 a.update(m.attrib)
                 name = a.get("name") or os.path.splitext(os.path.basename(a["file"]))[0]
                 self.meshes[name] = dict(file=a["file"], scale=_floats(a.get("scale"), 3, [1, 1, 1]))
+            for m in asset.findall("material"):      # its rgba only (MuJoCo's default: 1 1 1 1); a texture it names is not served
+                a = dict(self.defaults.get(m.attrib.get("class"), "material"))
+                a.update(m.attrib)
+                self.materials[a.get("name")] = _floats(a.get("rgba"), 4, [1.0, 1.0, 1.0, 1.0])
 
     # -- bodies ------------------------------------------------------------------
     def _parse_body(self, elem: ET.Element, parent: int, childclass: Optional[str]):
@@ -673,6 +680,8 @@ class MjcfCompiler:
             group=int(a.get("group", 0)),
             mesh=a.get("mesh"),
             body=bid,
+            rgba=_floats(a["rgba"], 4, [0.5, 0.5, 0.5, 1.0]) if "rgba" in a else None,
+            material=a.get("material"),
         )
 
     def _parse_site(self, elem, childclass, bid) -> _Site:
@@ -1264,6 +1273,10 @@ class _Lowering:
             site_pos[si] = p + mu.rot_vec(q, s.pos)
             site_quat[si] = mu.quat_normalize(mu.quat_mul(q, s.quat))
             site_size[si] = s.size
+        # the colour of every compiled geom, in names["geom"] order: its own rgba (through the default classes), else its material's, else MuJoCo's 0.5 0.5 0.5 1.  Bookkeeping
+        # only: nothing of it is packed; BatchedSim.render(rgb=True) uploads the first three columns (sim.py).  Textures are not served and alpha makes nothing transparent
+        grey = np.array([0.5, 0.5, 0.5, 1.0])
+        info["geom_rgba"] = np.array([g.rgba if g.rgba is not None else c.materials.get(g.material, grey) for _, g in geoms], dtype=np.float64).reshape(ng, 4).tolist()      # (a list, as every info entry: save_model writes JSON)
         # <camera> elements of the worldbody tree, in document order: bookkeeping only (names["camera"]: name -> row, info["camera"]: one dict per row with the surviving
         # body and the pose in its frame, composed through the fused static bodies as a site's is).  Nothing of it is packed: BatchedSim.render reads it (sim.py)
         order = {id(e): k for k, e in enumerate(c.root.iter("camera"))}

@@ -132,14 +132,30 @@ fresh tensors and keep their bits in ``out=``).  A named camera sees the body po
 cameras are ``_camera{k}``); ``sim.cameras_unserved`` maps the cameras whose ``mode`` is not ``fixed`` (``track*``, ``target*``) to the reason.  A kernel of its own (grx_sim_render): one
 workgroup per image bins the geoms' bounding spheres to screen tiles once and each tile tests only what may touch it (``binning=False`` gives every tile every geom: the same image
 bit for bit).  Deviations from MuJoCo's renderer: collidable geoms only, meshes as their convex hulls, no geom groups, no near-plane clipping (a surface 1 mm in front of the camera
-is seen), no ``track`` / ``target`` modes, no colour: this is depth and geom id.
+is seen), no ``track`` / ``target`` modes.
+
+CAMERAS (colour and surface normals): ``rgb=True`` and ``normals=True`` of both render calls add a colour image and the surface normals; the result is then the tuple ``depth, [seg],
+[rgb], [normal]`` in that fixed order (``out=`` takes the same tuple), and depth and seg are bit for bit what they are without the two keywords.  ``rgb`` is uint8 [N, K, H, W, 4],
+bytes R, G, B, A -- packed RGBA8, not planar RGB: the kernel's lane is a pixel, so a packed pixel is ONE 32-bit store per lane and a tile row one 32-byte segment, where planar or
+3-byte pixels would be byte stores; slice ``[..., :3]``.  A is 255 on a hit and 0 on a miss, which carries ``background``.  ``normal`` is float32 [N, K, H, W, 3]: the world-frame
+OUTWARD unit normal of the geom's surface at the hit (outward also when seen from inside), 0 on a miss; where a surface has faces, the face the hit point x (geom frame) lies nearest
+(plane +z; sphere x / |x|; capsule from the nearest point of its axis segment; ellipsoid (x / a^2, y / b^2, z / c^2) normalised; cylinder cap or side; box the face with the
+smallest ||x_i| - s_i|; mesh, i.e. its hull, the plane with the smallest |n . x - c|).  The colour, in fp32 with d the pixel's direction: v = -d / |d|, s = ``ambient`` +
+``diffuse`` |n . v|, plus ``sun_diffuse`` max(0, n_f . -sun) for a directional light travelling along the world-frame ``sun`` (n_f: n turned towards the viewer; ``sun=None``: none),
+channel = floor(255 min(1, c s) + 0.5).  c is the geom's colour clamped to [0, 1]: ``colors``, a float32 device tensor [ngeom, 3], or [N, ngeom, 3] for each world its own colours
+(visual domain randomisation); ``None``: ``model.info["geom_rgba"]``, which the compiler records per COMPILED geom -- the geom's own ``rgba`` through the default classes, else its
+``<material>``'s, else MuJoCo's 0.5 0.5 0.5 1 -- uploaded once.  With ``mask``, the worlds left out read depth -1, the background with alpha 0 and normal 0 in fresh tensors.  A
+kernel of its own again (grx_sim_render_rgb, csrc/grx_camera_rgb.hip): the depth kernel's stage, bin and trace, and a shade phase in which a wave walks the DISTINCT winners of its
+tile, so that the normal's type switch stays wave-uniform.  This is a self-contained shading model, not MuJoCo's OpenGL renderer: no textures (a textured material counts with its
+``rgba``), no transparency (alpha makes no geom transparent), no shadows, no specular term, no visual-only geoms, no mesh triangles (a mesh is shaded as its hull).
 
     sim = grx.BatchedSim("quadruped.xml", 4096, outputs=("xpos", "xquat"))
     sim.step(nstep=5)
     depth = sim.render("head_cam", 64, 64, exclude_own_body=True, max_dist=10.0)                   # [N, 1, 64, 64]
+    depth, rgb = sim.render("head_cam", 64, 64, rgb=True, colors=my_rgb, sun=(0.3, -0.5, -0.8))    # rgb: uint8 [N, 1, 64, 64, 4]
 
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, colour images, tracking and targeting cameras.
+equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, textures, shadows, specular light, transparency, visual-only geoms, tracking and targeting cameras.
 """
 import ctypes
 
@@ -795,8 +811,32 @@ class BatchedSim:
         return {name: f'mode="{rows[k]["mode"]}": render() serves fixed cameras only (a tracking or targeting camera turns with the scene; place it with render_pose())'
                 for name, k in self.model.names.get("camera", {}).items() if rows[k]["mode"] != "fixed"}
 
-    def _render(self, what, n_cams, height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill):
-        """the checks and the launch both render calls share; fill(block, t) -> what to keep alive: sets the block's camera poses once the device tensors exist"""
+    def _shade(self, what, rgb, normals, colors, ambient, diffuse, sun, sun_diffuse, background):
+        """the shading keywords of both render calls, checked without touching the device: None when neither rgb nor normals is set, else the host half of the shade block"""
+        if not (rgb or normals):
+            return None
+        ngeom = int(self.model.dim("ngeom"))
+        if colors is not None and (not hasattr(colors, "shape") or tuple(colors.shape) not in ((ngeom, 3), (self.num_worlds, ngeom, 3))):
+            raise ValueError(f"{what}: colors is a tensor of shape ({ngeom}, 3) or ({self.num_worlds}, {ngeom}, 3), not {tuple(getattr(colors, 'shape', ())) or type(colors).__name__}")
+        if colors is None and rgb and len(self.model.info.get("geom_rgba", ())) != ngeom:
+            raise ValueError(f'{what}: the model carries no info["geom_rgba"] (it was saved before the compiler recorded colours): compile it again or pass colors=')
+        terms = [float(ambient), float(diffuse), float(sun_diffuse)]
+        if not all(0.0 <= x < float("inf") for x in terms):
+            raise ValueError(f"{what}: ambient, diffuse and sun_diffuse must be finite and >= 0, not {terms}")
+        background = [float(x) for x in np.asarray(background, dtype=np.float64).reshape(-1)]
+        if len(background) != 3 or not np.isfinite(background).all():
+            raise ValueError(f"{what}: background is three finite values, not {background}")
+        if sun is not None:
+            sun = [float(x) for x in np.asarray(sun, dtype=np.float64).reshape(-1)]
+            if len(sun) != 3 or not np.isfinite(sun).all() or not np.linalg.norm(sun) > 1e-10:
+                raise ValueError(f"{what}: sun is a non-zero finite direction [3], not {sun}")
+        level = np.floor(np.float32(255.0) * np.clip(np.asarray(background, dtype=np.float32), 0.0, 1.0) + np.float32(0.5)).astype(np.uint8)      # the kernel's rounding
+        return dict(ambient=terms[0], diffuse=terms[1], sun=sun or [0.0, 0.0, 0.0], sun_diffuse=terms[2] if sun is not None else 0.0, background=background,
+                    word=int(level[0]) | int(level[1]) << 8 | int(level[2]) << 16)      # the packed pixel of a miss: bytes R, G, B and alpha 0
+
+    def _render(self, what, n_cams, height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill, rgb=False, normals=False, colors=None, shade=None):
+        """the checks and the launch both render calls share; fill(block, t) -> what to keep alive: sets the block's camera poses once the device tensors exist.  shade: what
+        _shade() returned; with it the launch is grx_sim_render_rgb and the result the tuple depth, [seg], [rgb], [normal]"""
         import torch
 
         from . import _native
@@ -825,31 +865,65 @@ class BatchedSim:
         t = self._ensure()
         m = self._mask(mask)
         shape = (self.num_worlds, n_cams, height, width)
-        if out is None:      # fresh tensors start as "no hit", which is what the images of masked-out worlds then read
-            depth = torch.full(shape, -1.0, dtype=torch.float32, device=self.device)
-            seg = torch.full(shape, -1, dtype=torch.int32, device=self.device) if segmentation else None
+        rgb, normals = bool(rgb) and shade is not None, bool(normals) and shade is not None
+        # the images of the call in the order of its result: (wanted, trailing shape, dtype, what a fresh tensor starts as -- "no hit", which the masked-out worlds then read)
+        kinds = ((True, (), torch.float32, -1.0), (segmentation, (), torch.int32, -1), (rgb, (4,), torch.uint8, None), (normals, (3,), torch.float32, 0.0))
+        wanted = [k for k in kinds if k[0]]
+        if out is None:
+            images = [torch.full(shape + tail, 0 if start is None else start, dtype=dt, device=self.device) for _, tail, dt, start in wanted]
+            if rgb:      # the background colour, alpha 0: a fill of the packed words, no copy from the host
+                images[1 + bool(segmentation)].view(torch.int32).fill_(shade["word"])
         else:
-            depth, seg = out if segmentation else (out, None)
-            for x, dt in ((depth, torch.float32),) + (((seg, torch.int32),) if segmentation else ()):
-                if not torch.is_tensor(x) or x.shape != shape or x.dtype != dt or x.device != self.device or not x.is_contiguous():
+            images = [out] if len(wanted) == 1 else list(out)
+            if len(images) != len(wanted) or any(not torch.is_tensor(x) or x.shape != shape + tail or x.dtype != dt or x.device != self.device or not x.is_contiguous()
+                                                 for x, (_, tail, dt, _) in zip(images, wanted)):
+                if shade is None:
                     raise ValueError(f"out= takes a contiguous float32 tensor{' and an int32 tensor' if segmentation else ''} of shape {shape} on {self.device}")
+                raise ValueError(f"out= takes contiguous tensors on {self.device} in the order of the result: " + ", ".join(f"{str(dt).split('.')[-1]} {shape + tail}" for _, tail, dt, _ in wanted))
+        it = iter(images)
+        depth, seg, rgba, normal = (next(it) if k[0] else None for k in kinds)
+        if rgba is not None and rgba.data_ptr() % 4:
+            raise ValueError("out=: the rgb tensor must start at a 4-byte boundary (a pixel is stored as one 32-bit word)")
         host = ((ctypes.c_float * n_cams)(*fovy), (ctypes.c_int * n_cams)(*exclude))
         b = _native.SimCamerasStruct(xpos=t["xpos"].data_ptr(), xquat=t["xquat"].data_ptr(), cam_fovy=ctypes.cast(host[0], ctypes.c_void_p), exclude_body=ctypes.cast(host[1], ctypes.c_void_p),
                                      mask=None if m is None else m.data_ptr(), depth=depth.data_ptr(), seg=None if seg is None else seg.data_ptr(), max_dist=float(max_dist),
                                      include_static=int(bool(include_static)), no_binning=int(not binning), tile_16x4=int(tile == "16x4"))
-        self._ray_keep = (fill(b, t), m, host)      # alive until the next ray or camera call has replaced them (the launch is only enqueued)
+        if shade is None:
+            self._ray_keep = (fill(b, t), m, host)      # alive until the next ray or camera call has replaced them (the launch is only enqueued)
+            with torch.cuda.device(self.device):
+                _native.check(self._L.grx_sim_render(self._h, ctypes.byref(b), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
+            return (depth, seg) if segmentation else depth
+        if colors is None and rgb:      # the compiler's table, uploaded once per simulation
+            if self.__dict__.get("_geom_rgb") is None:
+                self._geom_rgb = torch.tensor(np.asarray(self.model.info["geom_rgba"], dtype=np.float64).reshape(-1, 4)[:, :3], dtype=torch.float32, device=self.device).contiguous()
+            colors = self._geom_rgb
+        elif colors is not None:
+            colors = torch.as_tensor(colors, device=self.device).to(torch.float32).contiguous()
+        s = _native.SimShadeStruct(rgba=None if rgba is None else rgba.data_ptr(), normal=None if normal is None else normal.data_ptr(), colors=None if colors is None else colors.data_ptr(),
+                                   colors_per_world=int(colors is not None and colors.dim() == 3), ambient=shade["ambient"], diffuse=shade["diffuse"],
+                                   sun=(ctypes.c_float * 3)(*shade["sun"]), sun_diffuse=shade["sun_diffuse"], background=(ctypes.c_float * 3)(*shade["background"]))
+        self._ray_keep = (fill(b, t), m, host, colors)
         with torch.cuda.device(self.device):
-            _native.check(self._L.grx_sim_render(self._h, ctypes.byref(b), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
-        return (depth, seg) if segmentation else depth
+            _native.check(self._L.grx_sim_render_rgb(self._h, ctypes.byref(b), ctypes.byref(s), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
+        return tuple(images)
 
-    def render(self, cameras, height, width, segmentation=False, exclude_own_body=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None):
+    def render(self, cameras, height, width, segmentation=False, exclude_own_body=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None,
+               rgb=False, normals=False, colors=None, ambient=0.3, diffuse=0.7, sun=None, sun_diffuse=0.5, background=(0.0, 0.0, 0.0)):
         """Depth images of the MJCF's cameras: `cameras` a <camera> name or a sequence of K of them (at most 16 per call).  Returns depth [N, K, height, width] float32, the planar
         depth in metres along each camera's optical axis (module docstring, CAMERAS); with segmentation=True (depth, seg), seg int32 the id of the geom seen (sim.geom_id).  No
         hit, or one deeper than max_dist (when positive): -1.0 / -1.  exclude_own_body skips the geoms of each camera's body, exclude_body (one body or K, names or ids, -1:
         none) those of another; include_static=False the world body's.  mask: only the worlds with a non-zero entry are rendered; the images of the others read -1 in fresh
         tensors and keep their bits in out= (a depth tensor, or (depth, seg) with segmentation).  binning=False gives every screen tile every geom and tile="16x4" traces wide
         tiles instead of 8 x 8: the same image bit for bit, for A/B timing.  Sees the xpos / xquat of the LAST launch (exact after forward(), one substep stale after step()).  Enqueues on
-        torch's current stream; never synchronises."""
+        torch's current stream; never synchronises.
+        rgb=True adds a colour image, normals=True the surface normals: the result is then the tuple depth, [seg], [rgb], [normal] in that fixed order, and out= takes the same
+        tuple.  rgb is uint8 [N, K, height, width, 4], bytes R, G, B, A: PACKED RGBA8 and not planar RGB, because the kernel's lane is a pixel and a packed pixel is one 32-bit
+        store per lane (a tile row of 8 pixels one 32-byte segment), where planar or 3-byte pixels would be byte stores; slice [..., :3] for RGB.  A is 255 on a hit, 0 on a miss,
+        and a miss carries `background`.  normal is float32 [N, K, height, width, 3], the world-frame outward unit normal at the hit, 0 on a miss.  colors: a float32 device tensor
+        [ngeom, 3], or [N, ngeom, 3] for per-world colours, in 0 .. 1; None: the MJCF's (model.info["geom_rgba"], uploaded once).  The shading (module docstring, CAMERAS):
+        ambient + diffuse |n . v| towards the viewer, plus sun_diffuse max(0, n_f . -sun) for a directional light that travels along the world-frame `sun` (None: no sun).  In
+        fresh tensors the worlds `mask` leaves out read depth -1, the background with alpha 0 and normal 0."""
+        shade = self._shade("render()", rgb, normals, colors, ambient, diffuse, sun, sun_diffuse, background)
         names = [cameras] if isinstance(cameras, str) else list(cameras)
         rows = [self.model.info["camera"][self.camera_id(n)] for n in names]
         unserved = self.cameras_unserved
@@ -864,14 +938,17 @@ class BatchedSim:
             b.exclude_own_body = int(bool(exclude_own_body))
             return host
 
-        return self._render("render()", len(rows), height, width, [r["fovy"] for r in rows], segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill)
+        return self._render("render()", len(rows), height, width, [r["fovy"] for r in rows], segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill,
+                            rgb, normals, colors, shade)
 
-    def render_pose(self, pos, xmat, fovy, height, width, segmentation=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None):
+    def render_pose(self, pos, xmat, fovy, height, width, segmentation=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None,
+                    rgb=False, normals=False, colors=None, ambient=0.3, diffuse=0.7, sun=None, sun_diffuse=0.5, background=(0.0, 0.0, 0.0)):
         """render() for cameras the caller places: pos [N, K, 3] or [K, 3] (the same cameras in every world), xmat [N, K, 9] or [K, 9] the camera frames' rotations (camera ->
         world, row-major as site_xmat is: the columns are the camera's right, up and backward axes), fovy one angle or K in degrees.  The other arguments and the result are
         those of render(); there is no body of its own to exclude."""
         import torch
 
+        shade = self._shade("render_pose()", rgb, normals, colors, ambient, diffuse, sun, sun_diffuse, background)
         self._ray_need("render_pose()", ("xpos", "xquat"))
         self._ensure()
         p, x = (torch.as_tensor(v, device=self.device).to(torch.float32) for v in (pos, xmat))
@@ -887,7 +964,8 @@ class BatchedSim:
             b.pose_pos, b.pose_mat = p.data_ptr(), x.data_ptr()
             return (p, x)
 
-        return self._render("render_pose()", int(p.shape[1]), height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill)
+        return self._render("render_pose()", int(p.shape[1]), height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill,
+                            rgb, normals, colors, shade)
 
     # ------------------------------------------------------------------ status words (include/grx_capi.h grx_status_bits), as the env classes report them
     @property

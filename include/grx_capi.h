@@ -592,6 +592,33 @@ typedef struct grx_sim_cameras {
 int grx_sim_render(const grx_model* m, const grx_sim_cameras* c, int n_worlds, int n_cams, int height, int width, void* stream);
 /* host only: out[0] = sizeof(grx_sim_cameras), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (18) */
 int grx_sim_cameras_layout(long long* out, int cap);
+/* COLOUR AND SURFACE-NORMAL IMAGES of the same cameras: grx_sim_render_rgb takes the camera block above as it is (poses, filters, mask, depth, seg, the binning flags) and a
+ * shade block, and writes, next to depth (required) and seg (optional), which are bit for bit what grx_sim_render writes for the same block:
+ *   rgba    [N,K,H,W] packed RGBA8, one 32-bit word per pixel, bytes R, G, B, A in memory order.  A = 255 on a hit; a miss carries the background colour with A = 0.
+ *   normal  [N,K,H,W,3] the world-frame OUTWARD unit normal of the geom's surface at the hit (outward also when seen from inside); a miss: 0, 0, 0.  Where a surface has
+ *           faces, the face whose surface the hit point x (geom frame) lies nearest, the smaller index on a tie: plane +z; sphere x / |x|; capsule from the nearest point of
+ *           the segment |z| <= h; ellipsoid (x / a^2, y / b^2, z / c^2) normalised; cylinder cap or side by the smaller of ||z| - h| and |sqrt(x^2 + y^2) - r|; box the face
+ *           with the smallest ||x_i| - s_i|; mesh (its convex hull) the plane with the smallest |n . x - c|.
+ *   COLOUR  in fp32, with d the pixel's ray direction and n the normal: v = -d / |d|; s = ambient + diffuse |n . v|; when sun_diffuse > 0, with u = sun / |sun| (a world-frame
+ *           direction along which the light TRAVELS): s += sun_diffuse max(0, n_f . (-u)), n_f = n flipped to face the viewer; channel = floor(255 min(1, c s) + 0.5), c the
+ *           geom's colour clamped to [0, 1].  colors is [ngeom,3], or [N,ngeom,3] when colors_per_world != 0 (each world its own colours).  No shadows, no specular term, no
+ *           textures, no transparency: a self-contained shading model, not MuJoCo's OpenGL renderer.
+ * Either of rgba and normal may be NULL, not both.  Every pixel of an unmasked world is written; a masked-out world's images keep their bits.  One launch, enqueued only.
+ * Return -1 (grx_last_error) for everything grx_sim_render refuses, a NULL shade block, rgba and normal both NULL, rgba without colors, a negative or non-finite ambient,
+ * diffuse or sun_diffuse, a non-finite background, and, when sun_diffuse > 0, a zero or non-finite sun. */
+typedef struct grx_sim_shade {
+  unsigned int* rgba;                      /* [N,K,H,W] DEVICE or NULL */
+  float* normal;                           /* [N,K,H,W,3] DEVICE or NULL */
+  const float* colors;                     /* [ngeom,3] or [N,ngeom,3] DEVICE; NULL only without rgba */
+  int colors_per_world;                    /* != 0: colors is [N,ngeom,3] */
+  float ambient, diffuse;                  /* >= 0 */
+  float sun[3];                            /* world frame, any length; read when sun_diffuse > 0 */
+  float sun_diffuse;                       /* >= 0; 0: no sun */
+  float background[3];                     /* the colour of a miss, clamped to [0, 1] */
+} grx_sim_shade;
+int grx_sim_render_rgb(const grx_model* m, const grx_sim_cameras* c, const grx_sim_shade* s, int n_worlds, int n_cams, int height, int width, void* stream);
+/* host only: out[0] = sizeof(grx_sim_shade), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (10) */
+int grx_sim_shade_layout(long long* out, int cap);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)

@@ -3,7 +3,11 @@
   (b) render_pose(binning=False)    the same kernel, every tile testing every geom
   (c) ray() on the same pixel fan   one origin and one direction per pixel, the ray tensors built once outside the timed window
   (d) ray() and building the fan    the torch ops that turn the camera pose into [N, H W, 3] origins and directions, every frame
-(c) and (d) are the route to a depth image before the camera kernel existed.  The camera hangs above the mean body position of world 0, looks at it, fovy 60; it is placed
+(c) and (d) are the route to a depth image before the camera kernel existed.  With `--leg rgb` the jobs are instead
+  (e) render_pose()                 depth alone, the depth kernel
+  (f) render_pose(rgb=True)         colour and depth, the shading kernel with a sun
+  (g) render_pose(rgb=True, normals=True)
+so that (f) / (e) is what the SHADE phase and its stores cost.  The camera hangs above the mean body position of world 0, looks at it, fovy 60; it is placed
 with render_pose, which differs from render() only in where thread 0 of a workgroup takes the pose from.  Each figure is the median over `--runs` alternating runs of
 `--calls` back-to-back calls between two events, after a warm-up; the spread is (max - min) / median over the runs.  The images of (a) are compared with those of (b) (bits)
 and of (c) (hit geoms, depth) before anything is timed.
@@ -42,21 +46,32 @@ def probe(name, sim, a):
         def fan():
             return pos.expand(-1, h * w, -1).contiguous(), (mat.view(n, 1, 3, 3) @ local[None, :, :, None]).squeeze(-1).contiguous()
 
-        o, d = fan()
         out = (torch.empty((n, 1, h, w), device=sim.device), torch.empty((n, 1, h, w), dtype=torch.int32, device=sim.device))
-        rout = (torch.empty((n, h * w), device=sim.device), torch.empty((n, h * w), dtype=torch.int32, device=sim.device))
-        jobs = {"(a) render 16x4": lambda: sim.render_pose(pos, mat, 60.0, h, w, segmentation=True, out=out, tile="16x4"),
-                "(a) render 8x8": lambda: sim.render_pose(pos, mat, 60.0, h, w, segmentation=True, out=out, tile="8x8"),
-                "(b) no binning": lambda: sim.render_pose(pos, mat, 60.0, h, w, segmentation=True, out=out, binning=False),
-                "(c) ray, fan prebuilt": lambda: sim.ray(o, d, out=rout),
-                "(d) ray + fan": lambda: sim.ray(*fan(), out=rout)}
-        depth, seg = (x.clone() for x in jobs["(a) render 16x4"]())
-        same = all(torch.equal(x, y) for k in ("(a) render 8x8", "(b) no binning") for x, y in zip((depth, seg), jobs[k]()))
-        dist, geom = jobs["(c) ray, fan prebuilt"]()
-        agree = geom.view_as(seg) == seg
-        err = ((dist.view_as(depth) - depth).abs() / depth.abs().clamp(min=1.0))[agree]
-        print(f"  {h} x {w}: (a) 16x4, (a) 8x8 and (b) bit-identical: {same}; (a) vs (c): same geom in {float(agree.float().mean()):.4%} of the pixels, worst relative depth difference there "
-              f"{float(err.max()):.2e}; a geom in {float((seg >= 0).float().mean()):.0%} of the pixels")
+        if a.leg == "rgb":      # what SHADE costs: the shading kernel against the depth kernel alone, on the same poses in the same process
+            rgb, nrm = torch.empty((n, 1, h, w, 4), dtype=torch.uint8, device=sim.device), torch.empty((n, 1, h, w, 3), device=sim.device)
+            # a palette by geom id (the packaged models were saved without colours), and a sun
+            shade = dict(colors=torch.rand((sim.model.dim("ngeom"), 3), generator=torch.Generator().manual_seed(0)).to(sim.device), sun=(0.3, -0.5, -0.8))
+            jobs = {"(e) depth alone": lambda: sim.render_pose(pos, mat, 60.0, h, w, out=out[0]),
+                    "(f) rgb + depth": lambda: sim.render_pose(pos, mat, 60.0, h, w, rgb=True, out=(out[0], rgb), **shade),
+                    "(g) rgb, depth, normal": lambda: sim.render_pose(pos, mat, 60.0, h, w, rgb=True, normals=True, out=(out[0], rgb, nrm), **shade)}
+            depth = jobs["(e) depth alone"]().clone()
+            same = all(torch.equal(depth, jobs[k]()[0]) for k in ("(f) rgb + depth", "(g) rgb, depth, normal"))
+            print(f"  {h} x {w}: depth of (e), (f) and (g) bit-identical: {same}; alpha 255 in {float((rgb[..., 3] == 255).float().mean()):.0%} of the pixels")
+        else:
+            o, d = fan()
+            rout = (torch.empty((n, h * w), device=sim.device), torch.empty((n, h * w), dtype=torch.int32, device=sim.device))
+            jobs = {"(a) render 16x4": lambda: sim.render_pose(pos, mat, 60.0, h, w, segmentation=True, out=out, tile="16x4"),
+                    "(a) render 8x8": lambda: sim.render_pose(pos, mat, 60.0, h, w, segmentation=True, out=out, tile="8x8"),
+                    "(b) no binning": lambda: sim.render_pose(pos, mat, 60.0, h, w, segmentation=True, out=out, binning=False),
+                    "(c) ray, fan prebuilt": lambda: sim.ray(o, d, out=rout),
+                    "(d) ray + fan": lambda: sim.ray(*fan(), out=rout)}
+            depth, seg = (x.clone() for x in jobs["(a) render 16x4"]())
+            same = all(torch.equal(x, y) for k in ("(a) render 8x8", "(b) no binning") for x, y in zip((depth, seg), jobs[k]()))
+            dist, geom = jobs["(c) ray, fan prebuilt"]()
+            agree = geom.view_as(seg) == seg
+            err = ((dist.view_as(depth) - depth).abs() / depth.abs().clamp(min=1.0))[agree]
+            print(f"  {h} x {w}: (a) 16x4, (a) 8x8 and (b) bit-identical: {same}; (a) vs (c): same geom in {float(agree.float().mean()):.4%} of the pixels, worst relative depth difference there "
+                  f"{float(err.max()):.2e}; a geom in {float((seg >= 0).float().mean()):.0%} of the pixels")
         for fn in jobs.values():
             for _ in range(a.warmup):
                 fn()
@@ -79,11 +94,12 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--leg", choices=("depth", "rgb"), default="depth", help="depth: (a) - (d); rgb: (e) - (g), the colour kernel against the depth kernel")
     a = ap.parse_args()
     import gymnasium_robotics_amd as grx
     from gymnasium_robotics_amd import _native
 
-    print(f"command: python tools/camera_probe.py --worlds {a.worlds} --calls {a.calls} --runs {a.runs} --warmup {a.warmup}")
+    print(f"command: python tools/camera_probe.py --worlds {a.worlds} --calls {a.calls} --runs {a.runs} --warmup {a.warmup} --leg {a.leg}")
     print(f"build id: {_native.build_id()}   device: {torch.cuda.get_device_name(0)}   median of {a.runs} alternating runs of {a.calls} calls each")
     for env_id in ("AntMaze_UMaze-v5", "FrankaKitchen-v1"):
         env = grx.make_vec(env_id, num_envs=a.worlds)
