@@ -1396,6 +1396,9 @@ extern "C" int grx_tu_rays_launch(const GrxRayArgs* a, void* stream);   // csrc/
 extern "C" int grx_tu_camera_launch(const GrxCamArgs* a, void* stream);   // csrc/grx_camera.hip, likewise
 #include "grx_shade.h"
 extern "C" int grx_tu_camera_rgb_launch(const GrxCamRgbArgs* s, void* stream);   // csrc/grx_camera_rgb.hip, likewise
+#include "grx_trimesh.h"
+extern "C" int grx_tu_trimesh_rays_launch(const GrxRayArgs* a, const GrxTriArgs* m, void* stream);   // csrc/grx_trimesh.hip, likewise: the two kernels that see mesh triangles
+extern "C" int grx_tu_trimesh_render_launch(const GrxCamArgs* a, const GrxTriArgs* m, void* stream);
 
 struct grx_model {
   GrxPackedModel pm;
@@ -1730,6 +1733,7 @@ extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, con
 #include "grx_rays_api.h"
 #include "grx_camera_api.h"
 #include "grx_camera_rgb_api.h"
+#include "grx_trimesh_api.h"
 #include "grx_sensors_api.h"
 // sizeof(grx_sim_applied) and the byte offset of every member, in declaration order: what _native.SimAppliedStruct must mirror (host only)
 extern "C" int grx_sim_applied_layout(long long* out, int cap) {

@@ -273,6 +273,9 @@ class CompiledModel:
     tables: Dict[str, np.ndarray]
     names: Dict[str, Dict[str, int]]
     info: Dict[str, object]
+    # the triangles of the mesh geoms and a hierarchy over them (build_mesh_bvh below), for the rays and cameras that see triangles: nodes int32 [M, 8], tris float32 [T, 9],
+    # geom_adr int32 [ngeom, 2] = (first node, first triangle) of the geom's mesh, -1 for a geom that is no mesh.  BESIDE the tables: pack() does not see it.  None: no mesh geom.
+    mesh_bvh: Optional[Dict[str, np.ndarray]] = None
 
     def dim(self, key: str) -> int:
         return int(self.tables["dims"][DIMS.index(key)])
@@ -366,7 +369,8 @@ class CompiledModel:
 
     def copy(self) -> "CompiledModel":
         return CompiledModel({k: v.copy() for k, v in self.tables.items()},
-                             {k: dict(v) for k, v in self.names.items()}, dict(self.info))
+                             {k: dict(v) for k, v in self.names.items()}, dict(self.info),
+                             None if self.mesh_bvh is None else {k: v.copy() for k, v in self.mesh_bvh.items()})
 
 
 # ----------------------------------------------------------------------------
@@ -414,6 +418,70 @@ def pack_blob(tables: Dict[str, np.ndarray]):
     return H, np.ascontiguousarray(I, dtype=np.int32), np.ascontiguousarray(F, dtype=np.float64)
 
 
+# ----------------------------------------------------------------------------
+# triangles of a mesh and a bounding-volume hierarchy over them (csrc/grx_trimesh.h walks it)
+# ----------------------------------------------------------------------------
+BVH_LEAF = 4             # most triangles of a leaf
+BVH_MAX_TRIS = 1 << 20   # of one mesh: a leaf word holds first << 3 | count
+BVH_END = -1             # the skip link that ends a walk
+
+
+def build_mesh_bvh(tri):
+    """tri [n, 3, 3] fp64, the corners of a mesh's triangles -> (nodes int32 [M, 8], tris float32 [T, 9]).
+    Duplicate vertices are welded and the triangles with two equal corners or no area dropped.  A binary tree: a set of more than BVH_LEAF triangles is split at the median of
+    the centroids along the longest axis of the set's bounds; flattened depth-first, so a node's first child is the next node.  Node words: 0 .. 5 the fp32 BITS of the box (min 3,
+    max 3); 6 the SKIP LINK, the node to visit when this box is missed or its subtree is done (always a later node, or BVH_END); 7 is -1 for an inner node and first << 3 | count
+    for a leaf (count 1 .. BVH_LEAF triangles from `first`).  All indices are local to the mesh.  tris holds the triangles in leaf order as v0, e1 = v1 - v0, e2 = v2 - v0.
+    A box bounds the fp32 triangles as the device reads them (v0, v0 + e1, v0 + e2) and is then moved outward: to the next fp32 beyond the exact bound, by one fp32 ulp of the
+    box's extent, and one fp32 more -- every box is STRICTLY larger than what it holds, so neither rounding the box nor a ray that runs inside a face plane can cull a triangle."""
+    tri = np.asarray(tri, dtype=np.float64).reshape(-1, 3, 3)
+    vert, idx = np.unique(tri.reshape(-1, 3), axis=0, return_inverse=True)
+    face = idx.reshape(-1, 3)
+    area = np.linalg.norm(np.cross(vert[face[:, 1]] - vert[face[:, 0]], vert[face[:, 2]] - vert[face[:, 0]]), axis=1)
+    face = face[(face[:, 0] != face[:, 1]) & (face[:, 1] != face[:, 2]) & (face[:, 0] != face[:, 2]) & (area > 0.0)]
+    if not len(face):
+        raise ValueError("no triangle with an area")
+    if len(face) > BVH_MAX_TRIS:
+        raise ValueError(f"{len(face)} triangles; a mesh holds at most {BVH_MAX_TRIS}")
+    v0 = vert[face[:, 0]].astype(np.float32)
+    e1, e2 = (vert[face[:, 1]] - vert[face[:, 0]]).astype(np.float32), (vert[face[:, 2]] - vert[face[:, 0]]).astype(np.float32)
+    corner = np.stack([v0.astype(np.float64), v0.astype(np.float64) + e1, v0.astype(np.float64) + e2], axis=1)      # [n, 3, 3]: the device's triangles
+    lo_t, hi_t, mid = corner.min(axis=1), corner.max(axis=1), corner.mean(axis=1)
+    nodes, order = [], []
+
+    def rounded(lo, hi):
+        ext = (hi - lo) * 2.0 ** -23
+        lo32, hi32 = (lo - ext).astype(np.float32), (hi + ext).astype(np.float32)
+        lo32 = np.where(lo32 > lo - ext, np.nextafter(lo32, np.float32(-np.inf)), lo32)
+        hi32 = np.where(hi32 < hi + ext, np.nextafter(hi32, np.float32(np.inf)), hi32)
+        return np.nextafter(lo32, np.float32(-np.inf)), np.nextafter(hi32, np.float32(np.inf))
+
+    def grow(ids):      # appends the subtree of the triangles `ids`; the links that leave it stay BVH_END until the caller's frame knows where they go
+        at = len(nodes)
+        lo, hi = rounded(lo_t[ids].min(axis=0), hi_t[ids].max(axis=0))
+        nodes.append([lo, hi, BVH_END, -1])
+        if len(ids) <= BVH_LEAF:
+            nodes[at][3] = len(order) << 3 | len(ids)
+            order.extend(ids.tolist())
+            return
+        axis = int(np.argmax(hi_t[ids].max(axis=0) - lo_t[ids].min(axis=0)))
+        ids = ids[np.argsort(mid[ids, axis], kind="stable")]
+        half = len(ids) // 2
+        grow(ids[:half])
+        second = len(nodes)
+        grow(ids[half:])
+        for k in range(at + 1, second):      # whatever left the first child's subtree for the end goes on to the second child
+            if nodes[k][2] == BVH_END:
+                nodes[k][2] = second
+
+    grow(np.arange(len(face)))      # (halving: at most 21 frames deep)
+    out =np.zeros((len(nodes), 8), np.int32)
+    out[:, :6] = np.array([np.concatenate([n[0], n[1]]) for n in nodes], dtype=np.float32).view(np.int32)
+    out[:, 6], out[:, 7] = [n[2] for n in nodes], [n[3] for n in nodes]
+    order = np.asarray(order)
+    return out, np.ascontiguousarray(np.concatenate([v0[order], e1[order], e2[order]], axis=1), dtype=np.float32)
+
+
 def save_model(model: CompiledModel, path: str) -> None:
     import json
 
@@ -421,6 +489,7 @@ def save_model(model: CompiledModel, path: str) -> None:
         path,
         __names__=np.frombuffer(json.dumps(model.names).encode(), dtype=np.uint8),
         __info__=np.frombuffer(json.dumps(model.info, default=str).encode(), dtype=np.uint8),
+        **{f"__bvh_{k}__": v for k, v in (model.mesh_bvh or {}).items()},
         **model.tables,
     )
 
@@ -432,7 +501,8 @@ def load_model(path: str) -> CompiledModel:
     names = json.loads(bytes(z["__names__"]).decode())
     info = json.loads(bytes(z["__info__"]).decode())
     tables = {k: z[k] for k in z.files if not k.startswith("__")}
-    return CompiledModel(tables, names, info)
+    bvh = {k[len("__bvh_"):-2]: z[k] for k in z.files if k.startswith("__bvh_")}
+    return CompiledModel(tables, names, info, bvh or None)
 
 
 # ----------------------------------------------------------------------------
@@ -705,11 +775,9 @@ class MjcfCompiler:
                     mode=a.get("mode", "fixed"), target=a.get("target"), resolution=None if res is None else [int(x) for x in res.split()])
 
     # -- mesh hulls -----------------------------------------------------------------
-    def _load_mesh_hull(self, name: str):
-        """Returns (hull vertices (n,3), adjacency list) of the mesh's convex hull."""
+    def _load_mesh_soup(self, name: str):
+        """the corners of the mesh file's triangles, (3 ntri, 3) fp64 in the mesh frame with the mesh's scale applied: three consecutive rows are one triangle"""
         m = self.meshes[name]
-        if "hull" in m:
-            return m["hull"]
         path = os.path.join(self.dir, self.meshdir, m["file"])
         with open(path, "rb") as f:
             b = f.read()
@@ -717,8 +785,25 @@ class MjcfCompiler:
         if 84 + 50 * ntri != len(b):
             raise NotImplementedError(f"only binary STL supported: {path}")
         rec = np.frombuffer(b[84: 84 + 50 * ntri], dtype=np.uint8).reshape(ntri, 50)
-        v = rec[:, 12:48].copy().view("<f4").reshape(-1, 3).astype(np.float64) * m["scale"]
-        v = np.unique(v, axis=0)
+        return rec[:, 12:48].copy().view("<f4").reshape(-1, 3).astype(np.float64) * m["scale"]
+
+    def _load_mesh_bvh(self, name: str):
+        """(nodes, tris) of build_mesh_bvh over the mesh's triangles in the compiled geom frame (the mesh frame moved to the hull's centre, as the hull vertices are); made once
+        per mesh, so the geoms of one mesh share it"""
+        m = self.meshes[name]
+        if "bvh" not in m:
+            try:
+                m["bvh"] = build_mesh_bvh((self._load_mesh_soup(name) - self._mesh_center(name)).reshape(-1, 3, 3))
+            except ValueError as e:
+                raise ValueError(f"mesh {name!r}: {e}") from None
+        return m["bvh"]
+
+    def _load_mesh_hull(self, name: str):
+        """Returns (hull vertices (n,3), adjacency list) of the mesh's convex hull."""
+        m = self.meshes[name]
+        if "hull" in m:
+            return m["hull"]
+        v = np.unique(self._load_mesh_soup(name), axis=0)
         from scipy.spatial import ConvexHull
 
         hull = ConvexHull(v)
@@ -1193,6 +1278,17 @@ class _Lowering:
         geom_aabb = np.zeros((ng, 6))   # centre, half extents in the geom frame
         mesh_vert, mesh_adjadr, mesh_adjnum, mesh_adj = [], [], [], []
         mesh_cache = {}
+        # the triangles of every mesh geom (CompiledModel.mesh_bvh): one record per mesh, whether or not the geom keeps a hull
+        bvh_nodes, bvh_tris, bvh_at, bvh_adr = [], [], {}, -np.ones((ng, 2), np.int32)
+        for gi, (i, g) in enumerate(geoms):
+            if g.type == GEOM_MESH:
+                if g.mesh not in bvh_at:
+                    nodes_, tris_ = c._load_mesh_bvh(g.mesh)
+                    bvh_at[g.mesh] = (sum(len(x) for x in bvh_nodes), sum(len(x) for x in bvh_tris))
+                    bvh_nodes.append(nodes_)
+                    bvh_tris.append(tris_)
+                bvh_adr[gi] = bvh_at[g.mesh]
+        mesh_bvh = dict(nodes=np.concatenate(bvh_nodes), tris=np.concatenate(bvh_tris), geom_adr=bvh_adr) if bvh_nodes else None
         for gi, (i, g) in enumerate(geoms):
             k, p, q = anchor_of(i)
             names["geom"][g.name or f"_geom{gi}"] = gi
@@ -1852,7 +1948,7 @@ class _Lowering:
         info["nbody_full"] = nb
         info["unsupported_pairs"] = int(np.sum(pair_supported == 0))
         info["origin"] = c.origin.tolist()
-        return CompiledModel(T, names, info)
+        return CompiledModel(T, names, info, mesh_bvh)
 
 
 def compile_mjcf(xml_path: str, mutate=None, capacity=None, touch_filter=None, keep_sites=None, shift_body=None, shift_rotates=False, origin=None) -> CompiledModel:

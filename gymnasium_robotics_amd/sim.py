@@ -114,6 +114,11 @@ of any length -- and returns ``(dist [N, R] float32, geom [N, R] int32)``: the r
 the rays see the COMPILED model's geoms, i.e. the collidable ones (visual geoms do not exist there); a mesh geom is its CONVEX HULL, the shape the engine collides with; there are no
 geom groups.  A mesh geom whose only candidate pairs are with planes (or that has none) keeps no full hull in the compiled model: the ray calls raise a ``ValueError`` that names
 it rather than cast through it.  The calls run a kernel of their own (grx_sim_ray / grx_sim_ray_sites) on torch's current stream and never synchronise; rays are not state.
+``mesh="triangles"`` on ``ray``, ``ray_sites`` and ``rangefinder`` (default ``"hull"``) lifts the second deviation: a mesh geom is then the TRIANGLES of its file -- a ray passes the
+gap of a gripper, the hole of a torus, and inside a room mesh it meets the walls -- with the same hit rule, two-sided (entry from outside, exit from inside).  The compiler keeps
+every mesh geom's triangles and a bounding-volume hierarchy over them beside the packed model (``model.mesh_bvh``; ``save_model`` / ``load_model`` carry it), so a mesh needs no
+hull to be seen and the ``ValueError`` above does not apply; the first such call uploads them once (``close()`` frees them), and the launch is the triangle variant of the ray
+kernel (grx_sim_ray_tri, csrc/grx_trimesh.hip), in which a lane walks the hierarchy without a stack.  Any other value of ``mesh`` is a ``ValueError``.
 
     sim = grx.BatchedSim("maze_agent.xml", 4096, outputs=("xpos", "xquat", "site_xpos", "site_xmat"))
     fan = torch.stack([torch.cos(ang), torch.sin(ang), torch.zeros_like(ang)], dim=1)             # [64, 3] in the frame of the site "lidar"
@@ -132,7 +137,9 @@ fresh tensors and keep their bits in ``out=``).  A named camera sees the body po
 cameras are ``_camera{k}``); ``sim.cameras_unserved`` maps the cameras whose ``mode`` is not ``fixed`` (``track*``, ``target*``) to the reason.  A kernel of its own (grx_sim_render): one
 workgroup per image bins the geoms' bounding spheres to screen tiles once and each tile tests only what may touch it (``binning=False`` gives every tile every geom: the same image
 bit for bit).  Deviations from MuJoCo's renderer: collidable geoms only, meshes as their convex hulls, no geom groups, no near-plane clipping (a surface 1 mm in front of the camera
-is seen), no ``track`` / ``target`` modes.
+is seen), no ``track`` / ``target`` modes.  ``mesh="triangles"`` on both render calls renders mesh geoms as their triangles instead (depth and segmentation; with ``rgb`` or
+``normals`` it is a ``ValueError``: those shade hulls), through the render kernel's triangle variant (grx_sim_render_tri): the same stage, bin and trace, and at a mesh the 64
+lanes of a tile walk the hierarchy together, a wave-wide vote deciding which nodes anyone needs; small hierarchies are copied to LDS once per image.
 
 CAMERAS (colour and surface normals): ``rgb=True`` and ``normals=True`` of both render calls add a colour image and the surface normals; the result is then the tuple ``depth, [seg],
 [rgb], [normal]`` in that fixed order (``out=`` takes the same tuple), and depth and seg are bit for bit what they are without the two keywords.  ``rgb`` is uint8 [N, K, H, W, 4],
@@ -155,7 +162,7 @@ tile, so that the normal's type switch stays wave-uniform.  This is a self-conta
     depth, rgb = sim.render("head_cam", 64, 64, rgb=True, colors=my_rgb, sun=(0.3, -0.5, -0.8))    # rgb: uint8 [N, 1, 64, 64, 4]
 
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms or mesh triangles, geom groups, height fields, textures, shadows, specular light, transparency, visual-only geoms, tracking and targeting cameras.
+equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms, colour and normals on mesh triangles (mesh="triangles" serves rays, depth and segmentation), mesh files other than binary STL, geom groups, height fields, textures, shadows, specular light, transparency, visual-only geoms, tracking and targeting cameras.
 """
 import ctypes
 
@@ -654,10 +661,12 @@ class BatchedSim:
         self.forward(mask)
 
     # ------------------------------------------------------------------ rays (include/grx_capi.h grx_sim_ray / grx_sim_ray_sites; module docstring, RAYS)
-    def _ray_need(self, what, needed):
+    def _ray_need(self, what, needed, mesh="hull"):
         missing = [o for o in needed if o not in self.outputs]
         if missing:
             raise ValueError(f"{what} casts against the body poses of the last launch and needs the output(s) {missing}: BatchedSim(..., outputs={self.outputs + tuple(missing)})")
+        if mesh == "triangles":      # a mesh needs no hull to be seen as triangles
+            return
         tb = self.model.tables
         kind, hull = np.asarray(tb["geom_type"]).reshape(-1), np.asarray(tb["geom_hullnum"]).reshape(-1)
         bare = [int(g) for g in np.nonzero(kind == 7)[0] if g >= len(hull) or hull[g] < 4]
@@ -665,6 +674,33 @@ class BatchedSim:
             by_id = {i: name for name, i in self.model.names.get("geom", {}).items()}
             raise ValueError(f"{what}: mesh geom(s) {[by_id.get(g, g) for g in bare]} have no full hull in the compiled model (a mesh keeps it only when it has a candidate pair with a "
                              "sphere, capsule, ellipsoid, cylinder, box or mesh geom; these meet planes only, or nothing), so rays cannot see them")
+
+    @staticmethod
+    def _mesh_kind(what, mesh, rgb=False, normals=False):
+        """the mesh= keyword of the ray and render calls, checked without touching the device"""
+        if mesh not in ("hull", "triangles"):
+            raise ValueError(f'{what}: mesh is "hull" or "triangles", not {mesh!r}')
+        if mesh == "triangles" and (rgb or normals):
+            raise ValueError(f'{what}: mesh="triangles" serves depth and segmentation only; rgb=True and normals=True shade hulls (mesh="hull")')
+        return mesh
+
+    def _trimesh(self):
+        """the triangle handle of this simulation's model (grx_sim_trimesh_create): made on the first call with mesh="triangles", one blocking upload, freed by close()"""
+        from . import _native
+
+        if self.__dict__.get("_tri") is None:
+            self._ensure()
+            bvh = self.model.mesh_bvh
+            ngeom = int(self.model.dim("ngeom"))
+            if bvh is None:
+                if (np.asarray(self.model.tables["geom_type"]).reshape(-1) == 7).any():
+                    raise ValueError('mesh="triangles": the model has mesh geoms but carries no triangles (it was saved before the compiler kept them): compile it again')
+                bvh = dict(nodes=np.zeros((0, 8), np.int32), tris=np.zeros((0, 9), np.float32), geom_adr=-np.ones((ngeom, 2), np.int32))
+            nodes, tris, adr = (np.ascontiguousarray(bvh[k], dtype=dt) for k, dt in (("nodes", np.int32), ("tris", np.float32), ("geom_adr", np.int32)))
+            h = ctypes.c_void_p()
+            _native.check(self._L.grx_sim_trimesh_create(self._h, nodes.ctypes.data, len(nodes), tris.ctypes.data, len(tris), adr.ctypes.data, len(adr), ctypes.byref(h)))
+            self._tri = h
+        return self._tri
 
     def _ray_exclude(self, exclude_body, n_rays):
         """[R] int32 device tensor of compiled body ids (-1: none), or None"""
@@ -694,28 +730,31 @@ class BatchedSim:
                 raise ValueError(f"out= takes a contiguous float32 and an int32 tensor of shape ({self.num_worlds}, {n_rays}) on {self.device}")
         return dist, geom
 
-    def _ray_launch(self, fn, block, n_rays, keep):
+    def _ray_launch(self, fn, block, n_rays, keep, mesh="hull"):
+        """fn: "grx_sim_ray" or "grx_sim_ray_sites"; mesh="triangles" launches its _tri variant with the triangle handle"""
         import torch
 
         from . import _native
         from .core import stream_ptr
 
         self._ray_keep = keep      # the inputs stay alive until the next ray call has replaced them (the launch is only enqueued)
+        tri = (self._trimesh(),) if mesh == "triangles" else ()
         with torch.cuda.device(self.device):
-            _native.check(fn(self._h, ctypes.byref(block), self.num_worlds, int(n_rays), stream_ptr(self.device)))
+            _native.check(getattr(self._L, fn + ("_tri" if tri else ""))(self._h, ctypes.byref(block), *tri, self.num_worlds, int(n_rays), stream_ptr(self.device)))
 
-    def ray(self, origin, direction, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None):
+    def ray(self, origin, direction, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, mesh="hull"):
         """mj_ray for R rays in every world: origin, direction [N, R, 3] device tensors in world coordinates ([R, 3]: the same rays in every world); direction need not be unit.
         Returns (dist [N, R] float32, geom [N, R] int32): the parameter t of the nearest hit (metres for a unit direction) and the id of the geom hit (sim.geom_id), or -1.0 / -1
         for no hit, a hit beyond max_dist (when positive), a zero or non-finite direction.  exclude_body: a body name or compiled body id, or a list / tensor of R of them (-1:
         none): that body's geoms are skipped (mj_ray's bodyexclude).  include_static=False skips the geoms of the world body.  mask: only the worlds with a non-zero entry are
         written; the rows of the others read -1.0 / -1 in fresh tensors and keep their bits in out= tensors.  out=(dist, geom): write into these tensors.  Casts against the xpos / xquat of the LAST launch (exact after forward(), one substep stale after step()).
-        Enqueues on torch's current stream; never synchronises."""
+        Enqueues on torch's current stream; never synchronises.  mesh="triangles": a mesh geom is the triangles of its file and not its convex hull (module docstring, RAYS);
+        the first such call uploads them."""
         import torch
 
         from . import _native
 
-        self._ray_need("ray()", ("xpos", "xquat"))
+        self._ray_need("ray()", ("xpos", "xquat"), self._mesh_kind("ray()", mesh))
         t = self._ensure()
         o, d = (torch.as_tensor(x, device=self.device).to(torch.float32) for x in (origin, direction))
         if o.dim() == 2 and d.dim() == 3:
@@ -732,19 +771,19 @@ class BatchedSim:
         dist, geom = self._ray_out(out, n_rays)
         b = _native.SimRaysStruct(xpos=t["xpos"].data_ptr(), xquat=t["xquat"].data_ptr(), origin=o.data_ptr(), direction=d.data_ptr(), exclude_body=None if e is None else e.data_ptr(),
                                   mask=None if m is None else m.data_ptr(), dist=dist.data_ptr(), geom=geom.data_ptr(), max_dist=float(max_dist), include_static=int(bool(include_static)))
-        self._ray_launch(self._L.grx_sim_ray, b, n_rays, (o, d, e, m))
+        self._ray_launch("grx_sim_ray", b, n_rays, (o, d, e, m), mesh)
         return dist, geom
 
-    def ray_sites(self, sites, local_dir, exclude_own_body=True, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None):
+    def ray_sites(self, sites, local_dir, exclude_own_body=True, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, mesh="hull"):
         """R rays that start at sites: ray r starts at site sites[r] (a name or id; one name: every ray) and runs along local_dir[r] ([R, 3], in the site's frame), in every
         world.  exclude_own_body: the geoms of the site's body are skipped (the rangefinder rule); the other arguments and the result are those of ray().  Reads site_xpos /
         site_xmat of the last launch as well.  The first call with a list of sites the model handle has not seen uploads it (one blocking copy; the handle keeps the 64 most recent
-        lists); every later call with that list only enqueues."""
+        lists); every later call with that list only enqueues.  mesh: as in ray()."""
         import torch
 
         from . import _native
 
-        self._ray_need("ray_sites()", ("xpos", "xquat", "site_xpos", "site_xmat"))
+        self._ray_need("ray_sites()", ("xpos", "xquat", "site_xpos", "site_xmat"), self._mesh_kind("ray_sites()", mesh))
         t = self._ensure()
         l = torch.as_tensor(local_dir, device=self.device).to(torch.float32).contiguous()
         if l.dim() != 2 or l.shape[1] != 3 or l.shape[0] < 1:
@@ -765,7 +804,7 @@ class BatchedSim:
                                   ray_site=ctypes.cast(host, ctypes.c_void_p), local_dir=l.data_ptr(), exclude_body=None if e is None else e.data_ptr(),
                                   mask=None if m is None else m.data_ptr(), dist=dist.data_ptr(), geom=geom.data_ptr(), max_dist=float(max_dist), include_static=int(bool(include_static)),
                                   exclude_site_body=int(bool(exclude_own_body)))
-        self._ray_launch(self._L.grx_sim_ray_sites, b, n_rays, (l, e, m, host))
+        self._ray_launch("grx_sim_ray_sites", b, n_rays, (l, e, m, host), mesh)
         return dist, geom
 
     @property
@@ -776,24 +815,25 @@ class BatchedSim:
         """column of the <rangefinder> sensor `name` in rangefinder()"""
         return self._lookup("rangefinder", name)
 
-    def rangefinder(self, mask=None):
+    def rangefinder(self, mask=None, mesh="hull"):
         """[N, n_rangefinder] float32: the reading of every <rangefinder> sensor of the MJCF, in sensor order -- the distance along the +z axis of the sensor's site to the
         nearest geom that does not belong to the site's body, -1 for none or for one beyond the sensor's positive cutoff (mjSENS_RANGEFINDER, over the geoms ray() sees).
-        mask: the rows of the worlds it leaves out read -1."""
+        mask: the rows of the worlds it leaves out read -1.  mesh: as in ray()."""
         import torch
 
+        self._mesh_kind("rangefinder()", mesh)
         rows = self.model.info.get("rangefinder", ())
         if not rows:
             raise ValueError("the model has no <rangefinder> sensor")
         lost = [name for name, k in self.model.names["rangefinder"].items() if rows[k]["site"] not in self.model.names["site"]]
         if lost:
             raise ValueError(f"the site of rangefinder(s) {sorted(lost)} is not among the model's sites (the sensor names none, or keep_sites dropped it: compile_kwargs=dict(keep_sites=...))")
-        self._ray_need("rangefinder()", ("xpos", "xquat", "site_xpos", "site_xmat"))
+        self._ray_need("rangefinder()", ("xpos", "xquat", "site_xpos", "site_xmat"), mesh)
         self._ensure()
         if self.__dict__.get("_rf") is None:
             self._rf = (torch.tensor([[0.0, 0.0, 1.0]] * len(rows), device=self.device), torch.tensor([[max(float(r["cutoff"]), 0.0) for r in rows]], dtype=torch.float32, device=self.device))
         z, cut = self._rf
-        dist, _ = self.ray_sites([r["site"] for r in rows], z, exclude_own_body=True, mask=mask)
+        dist, _ = self.ray_sites([r["site"] for r in rows], z, exclude_own_body=True, mask=mask, mesh=mesh)
         beyond = (cut > 0) & (dist > cut)      # each sensor's own cutoff
         if mask is not None:
             beyond &= self._mask(mask).bool()[:, None]
@@ -834,7 +874,7 @@ class BatchedSim:
         return dict(ambient=terms[0], diffuse=terms[1], sun=sun or [0.0, 0.0, 0.0], sun_diffuse=terms[2] if sun is not None else 0.0, background=background,
                     word=int(level[0]) | int(level[1]) << 8 | int(level[2]) << 16)      # the packed pixel of a miss: bytes R, G, B and alpha 0
 
-    def _render(self, what, n_cams, height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill, rgb=False, normals=False, colors=None, shade=None):
+    def _render(self, what, n_cams, height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill, rgb=False, normals=False, colors=None, shade=None, mesh="hull"):
         """the checks and the launch both render calls share; fill(block, t) -> what to keep alive: sets the block's camera poses once the device tensors exist.  shade: what
         _shade() returned; with it the launch is grx_sim_render_rgb and the result the tuple depth, [seg], [rgb], [normal]"""
         import torch
@@ -861,7 +901,7 @@ class BatchedSim:
         exclude = [self.body_id(b) if isinstance(b, str) else int(b) for b in exclude]
         if len(exclude) != n_cams:
             raise ValueError(f"{what}: exclude_body must be one body or name {n_cams} of them (-1: none), not {len(exclude)}")
-        self._ray_need(what, ("xpos", "xquat"))
+        self._ray_need(what, ("xpos", "xquat"), mesh)
         t = self._ensure()
         m = self._mask(mask)
         shape = (self.num_worlds, n_cams, height, width)
@@ -891,7 +931,10 @@ class BatchedSim:
         if shade is None:
             self._ray_keep = (fill(b, t), m, host)      # alive until the next ray or camera call has replaced them (the launch is only enqueued)
             with torch.cuda.device(self.device):
-                _native.check(self._L.grx_sim_render(self._h, ctypes.byref(b), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
+                if mesh == "triangles":
+                    _native.check(self._L.grx_sim_render_tri(self._h, ctypes.byref(b), self._trimesh(), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
+                else:
+                    _native.check(self._L.grx_sim_render(self._h, ctypes.byref(b), self.num_worlds, n_cams, height, width, stream_ptr(self.device)))
             return (depth, seg) if segmentation else depth
         if colors is None and rgb:      # the compiler's table, uploaded once per simulation
             if self.__dict__.get("_geom_rgb") is None:
@@ -908,7 +951,7 @@ class BatchedSim:
         return tuple(images)
 
     def render(self, cameras, height, width, segmentation=False, exclude_own_body=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None,
-               rgb=False, normals=False, colors=None, ambient=0.3, diffuse=0.7, sun=None, sun_diffuse=0.5, background=(0.0, 0.0, 0.0)):
+               rgb=False, normals=False, colors=None, ambient=0.3, diffuse=0.7, sun=None, sun_diffuse=0.5, background=(0.0, 0.0, 0.0), mesh="hull"):
         """Depth images of the MJCF's cameras: `cameras` a <camera> name or a sequence of K of them (at most 16 per call).  Returns depth [N, K, height, width] float32, the planar
         depth in metres along each camera's optical axis (module docstring, CAMERAS); with segmentation=True (depth, seg), seg int32 the id of the geom seen (sim.geom_id).  No
         hit, or one deeper than max_dist (when positive): -1.0 / -1.  exclude_own_body skips the geoms of each camera's body, exclude_body (one body or K, names or ids, -1:
@@ -922,7 +965,9 @@ class BatchedSim:
         and a miss carries `background`.  normal is float32 [N, K, height, width, 3], the world-frame outward unit normal at the hit, 0 on a miss.  colors: a float32 device tensor
         [ngeom, 3], or [N, ngeom, 3] for per-world colours, in 0 .. 1; None: the MJCF's (model.info["geom_rgba"], uploaded once).  The shading (module docstring, CAMERAS):
         ambient + diffuse |n . v| towards the viewer, plus sun_diffuse max(0, n_f . -sun) for a directional light that travels along the world-frame `sun` (None: no sun).  In
-        fresh tensors the worlds `mask` leaves out read depth -1, the background with alpha 0 and normal 0."""
+        fresh tensors the worlds `mask` leaves out read depth -1, the background with alpha 0 and normal 0.
+        mesh="triangles": depth and segmentation see a mesh geom as the triangles of its file and not as its convex hull (module docstring, CAMERAS); not with rgb or normals."""
+        self._mesh_kind("render()", mesh, rgb, normals)
         shade = self._shade("render()", rgb, normals, colors, ambient, diffuse, sun, sun_diffuse, background)
         names = [cameras] if isinstance(cameras, str) else list(cameras)
         rows = [self.model.info["camera"][self.camera_id(n)] for n in names]
@@ -939,17 +984,18 @@ class BatchedSim:
             return host
 
         return self._render("render()", len(rows), height, width, [r["fovy"] for r in rows], segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill,
-                            rgb, normals, colors, shade)
+                            rgb, normals, colors, shade, mesh)
 
     def render_pose(self, pos, xmat, fovy, height, width, segmentation=False, exclude_body=None, max_dist=0.0, include_static=True, mask=None, out=None, binning=True, tile=None,
-                    rgb=False, normals=False, colors=None, ambient=0.3, diffuse=0.7, sun=None, sun_diffuse=0.5, background=(0.0, 0.0, 0.0)):
+                    rgb=False, normals=False, colors=None, ambient=0.3, diffuse=0.7, sun=None, sun_diffuse=0.5, background=(0.0, 0.0, 0.0), mesh="hull"):
         """render() for cameras the caller places: pos [N, K, 3] or [K, 3] (the same cameras in every world), xmat [N, K, 9] or [K, 9] the camera frames' rotations (camera ->
         world, row-major as site_xmat is: the columns are the camera's right, up and backward axes), fovy one angle or K in degrees.  The other arguments and the result are
         those of render(); there is no body of its own to exclude."""
         import torch
 
+        self._mesh_kind("render_pose()", mesh, rgb, normals)
         shade = self._shade("render_pose()", rgb, normals, colors, ambient, diffuse, sun, sun_diffuse, background)
-        self._ray_need("render_pose()", ("xpos", "xquat"))
+        self._ray_need("render_pose()", ("xpos", "xquat"), mesh)
         self._ensure()
         p, x = (torch.as_tensor(v, device=self.device).to(torch.float32) for v in (pos, xmat))
         if p.dim() == 2:
@@ -965,7 +1011,7 @@ class BatchedSim:
             return (p, x)
 
         return self._render("render_pose()", int(p.shape[1]), height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill,
-                            rgb, normals, colors, shade)
+                            rgb, normals, colors, shade, mesh)
 
     # ------------------------------------------------------------------ status words (include/grx_capi.h grx_status_bits), as the env classes report them
     @property
@@ -1048,6 +1094,9 @@ class BatchedSim:
             self._params = None
             self._L.grx_sim_params_destroy(self._p)
             self._p = None
+        if self.__dict__.get("_tri") is not None:
+            self._L.grx_sim_trimesh_destroy(self._tri)
+            self._tri = None
         self._entry = None      # (it holds the parameter object's pointer: no launch after close)
         release_models(self, ("_h", "_h_big"))
         self.lane = None

@@ -619,6 +619,29 @@ typedef struct grx_sim_shade {
 int grx_sim_render_rgb(const grx_model* m, const grx_sim_cameras* c, const grx_sim_shade* s, int n_worlds, int n_cams, int height, int width, void* stream);
 /* host only: out[0] = sizeof(grx_sim_shade), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (10) */
 int grx_sim_shade_layout(long long* out, int cap);
+/* MESH TRIANGLES for the rays and the depth / segmentation cameras above.  grx_sim_ray, grx_sim_ray_sites and grx_sim_render see a mesh geom as its convex hull; the three
+ * _tri calls below take the same argument blocks and a triangle handle, and see the mesh's TRIANGLES instead: a gap between two fingers, the hole of a torus, the inside of a
+ * room.  Everything else -- the hit rule (the smallest t >= 0 on the surface, two-sided: entry from outside, exit from inside), geoms that are no mesh, filters, tie rule,
+ * masks, what is written -- is that of the call without the suffix, and a model without mesh geoms gives the same bits.  A mesh needs no hull here: the refusal of a mesh
+ * geom without a full hull does not apply.  Not served with triangles: colour and normals (grx_sim_render_rgb shades hulls).
+ *   HIERARCHY  the caller (mjcf/compiler.py build_mesh_bvh) passes, in HOST memory: nodes [n_nodes, 8] 32-bit words -- box min 3, box max 3 as fp32, the skip link (the node
+ *           to visit when the box is missed or the subtree is done: a LATER node of the same mesh, or -1, the end), and -1 for an inner node, whose first child is the next
+ *           node, or first << 3 | count for a leaf of count = 1 .. 4 triangles; tris [n_tris, 9] fp32, v0, e1 = v1 - v0, e2 = v2 - v0 in the compiled geom frame, in leaf order;
+ *           geom_adr [n_geom, 2] = (first node, first triangle) of each geom's mesh, -1 -1 for a geom that is no mesh.  Node and triangle indices inside a mesh are local to it;
+ *           a mesh's nodes and triangles run up to the next mesh's.  At most 2^20 triangles per mesh.
+ * grx_sim_trimesh_create checks the tables on the host BEFORE anything else (so also without a device) -- every address inside its array, every skip link strictly forward or
+ * the end, every inner node followed by a child, every leaf range inside the mesh's triangles -- and refuses a table that fails (-1, grx_last_error names the geom, the node
+ * and the reason): no table it accepts can send a walk out of bounds or round in a circle.  Then: a NULL model or handle pointer, n_geom other than the model's geom count, a
+ * mesh geom without a hierarchy or a hierarchy on a geom that is no mesh.  It uploads the tables once (blocking); the handle belongs to that model and is freed with
+ * grx_sim_trimesh_destroy (NULL: nothing), by the caller, after the launches that read it have finished.
+ * The _tri calls return -1 for everything the call without the suffix refuses but the missing hull, for a NULL triangle handle and for one made for another model; each
+ * enqueues one launch and never waits (but for the upload of a ray_site list the model handle has not seen). */
+typedef struct grx_trimesh grx_trimesh;
+int grx_sim_trimesh_create(const grx_model* m, const int* nodes, int n_nodes, const float* tris, int n_tris, const int* geom_adr, int n_geom, grx_trimesh** out);
+void grx_sim_trimesh_destroy(grx_trimesh* h);
+int grx_sim_ray_tri(const grx_model* m, const grx_sim_rays* r, const grx_trimesh* h, int n_worlds, int n_rays, void* stream);
+int grx_sim_ray_sites_tri(const grx_model* m, const grx_sim_rays* r, const grx_trimesh* h, int n_worlds, int n_rays, void* stream);
+int grx_sim_render_tri(const grx_model* m, const grx_sim_cameras* c, const grx_trimesh* h, int n_worlds, int n_cams, int height, int width, void* stream);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)
