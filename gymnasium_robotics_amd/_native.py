@@ -105,6 +105,11 @@ class SimShadeStruct(ctypes.Structure):         # include/grx_capi.h, grx_sim_sh
                                                                                ("sun", ctypes.c_float * 3), ("sun_diffuse", ctypes.c_float), ("background", ctypes.c_float * 3)]
 
 
+class SimIkStruct(ctypes.Structure):            # include/grx_capi.h, grx_sim_ik_args (site, dof_mask: host arrays); checked against grx_sim_ik_layout when the library loads
+    _fields_ = [(n, ctypes.c_void_p) for n in ("qpos0", "mocap_pos", "mocap_quat", "target_pos", "target_quat", "mask", "qpos", "err", "iters", "site", "dof_mask")] + [
+        (n, ctypes.c_int) for n in ("n_sites", "max_iters", "clamp_limits")] + [(n, ctypes.c_float) for n in ("damping", "max_step", "tol", "rot_weight")]
+
+
 class KitchenBookStruct(ctypes.Structure):      # include/grx_capi.h, grx_kitchen_book
     _fields_ = [(n, ctypes.c_void_p) for n in ("completed", "stepped", "tasks_to_complete", "episode_completions", "elapsed", "step_completions", "reward", "terminated",
                                                "truncated", "needs_reset", "reset_now", "qpos", "qvel", "qacc_ws", "init_qpos")] + [
@@ -222,7 +227,10 @@ def lib():
         L.grx_sim_ray_tri.argtypes = [vp, vp, vp, ci, ci, vp]
         L.grx_sim_ray_sites_tri.argtypes = [vp, vp, vp, ci, ci, vp]
         L.grx_sim_render_tri.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
-        for struct, layout, name in ((SimCamerasStruct, L.grx_sim_cameras_layout, "grx_sim_cameras"), (SimShadeStruct, L.grx_sim_shade_layout, "grx_sim_shade")):
+        L.grx_sim_ik.argtypes = [vp, vp, ci, vp]
+        L.grx_sim_ik_layout.argtypes = [ctypes.POINTER(ctypes.c_longlong), ci]
+        for struct, layout, name in ((SimCamerasStruct, L.grx_sim_cameras_layout, "grx_sim_cameras"), (SimShadeStruct, L.grx_sim_shade_layout, "grx_sim_shade"),
+                                     (SimIkStruct, L.grx_sim_ik_layout, "grx_sim_ik_args")):
             want = [ctypes.sizeof(struct)] + [getattr(struct, f).offset for f, _ in struct._fields_]
             got = (ctypes.c_longlong * len(want))()
             if layout(got, len(want)) != len(want) or list(got) != want:
@@ -298,7 +306,7 @@ def check(rc: int):
 
 EXPORTED_SYMBOLS = [
     "grx_model_create", "grx_model_destroy", "grx_model_set_table", "grx_model_lds_bytes", "grx_model_hull_pair_records", "grx_model_dim",
-    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sim_step", "grx_sim_layout", "grx_sim_step_dyn", "grx_sim_dynamics_layout", "grx_sim_step_con", "grx_sim_contacts_layout", "grx_sim_step_frc", "grx_sim_applied_layout", "grx_sim_step_sns", "grx_sim_sensors_layout", "grx_sim_step_wrn", "grx_sim_wrenches_layout", "grx_sim_ray", "grx_sim_ray_sites", "grx_sim_rays_layout", "grx_sim_render", "grx_sim_cameras_layout", "grx_sim_render_rgb", "grx_sim_shade_layout", "grx_sim_trimesh_create", "grx_sim_trimesh_destroy", "grx_sim_ray_tri", "grx_sim_ray_sites_tri", "grx_sim_render_tri", "grx_sim_params_create", "grx_sim_params_destroy", "grx_sim_params_row", "grx_sim_params_commit", "grx_sim_step_params", "grx_sim_params_names", "grx_sim_params_records", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
+    "grx_fetch_step", "grx_fetch_forward", "grx_fetch_reset", "grx_fetch_compute_reward", "grx_her_relabel", "grx_her_sample", "grx_her_sample_final", "grx_her_mark_resets", "grx_her_sample_relabel", "grx_her_draw_relabel", "grx_her_append", "grx_her_archive", "grx_her_episode_sample", "grx_fetch_post_step", "grx_fetch_sample_resets", "grx_fetch_sample_resets_device", "grx_adroit_sample_resets_device", "grx_maze_sample_resets_device", "grx_point_step", "grx_maze_compute_reward", "grx_hand_step", "grx_hand_step_repeat", "grx_adroit_step", "grx_kitchen_step", "grx_sim_step", "grx_sim_layout", "grx_sim_step_dyn", "grx_sim_dynamics_layout", "grx_sim_step_con", "grx_sim_contacts_layout", "grx_sim_step_frc", "grx_sim_applied_layout", "grx_sim_step_sns", "grx_sim_sensors_layout", "grx_sim_step_wrn", "grx_sim_wrenches_layout", "grx_sim_ray", "grx_sim_ray_sites", "grx_sim_rays_layout", "grx_sim_render", "grx_sim_cameras_layout", "grx_sim_render_rgb", "grx_sim_shade_layout", "grx_sim_trimesh_create", "grx_sim_trimesh_destroy", "grx_sim_ray_tri", "grx_sim_ray_sites_tri", "grx_sim_render_tri", "grx_sim_ik", "grx_sim_ik_layout", "grx_sim_params_create", "grx_sim_params_destroy", "grx_sim_params_row", "grx_sim_params_commit", "grx_sim_step_params", "grx_sim_params_names", "grx_sim_params_records", "grx_sample_uniform_rows", "grx_uniform_rows_device", "grx_kitchen_bookkeeping", "grx_goal_compute_reward", "grx_manip_compute_reward", "grx_order_by_cost", "grx_order_by_cost_slots", "grx_maze_reset_rows", "grx_maze_reset_rows_list", "grx_maze_sample_resets_list", "grx_maze_episode_end", "grx_hand_commit_rows", "grx_fetch_commit_rows", "grx_adroit_commit_rows", "grx_last_error",
     "grx_normstat_geometry", "grx_normstat_layout", "grx_normstat_update", "grx_normstat_refresh", "grx_normstat_apply_batch", "grx_normstat_apply_packed",
 ]
 

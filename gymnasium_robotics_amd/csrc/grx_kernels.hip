@@ -1399,6 +1399,9 @@ extern "C" int grx_tu_camera_rgb_launch(const GrxCamRgbArgs* s, void* stream);  
 #include "grx_trimesh.h"
 extern "C" int grx_tu_trimesh_rays_launch(const GrxRayArgs* a, const GrxTriArgs* m, void* stream);   // csrc/grx_trimesh.hip, likewise: the two kernels that see mesh triangles
 extern "C" int grx_tu_trimesh_render_launch(const GrxCamArgs* a, const GrxTriArgs* m, void* stream);
+#include "grx_ik.h"
+extern "C" int grx_tu_ik_wpb(const GrxIkArgs* a, int* bytes);   // csrc/grx_ik.hip, likewise: the inverse-kinematics kernel
+extern "C" int grx_tu_ik_launch(const GrxIkArgs* a, void* stream);
 
 struct grx_model {
   GrxPackedModel pm;
@@ -1734,6 +1737,7 @@ extern "C" int grx_sim_step_frc(const grx_model* m, const grx_sim_params* p, con
 #include "grx_camera_api.h"
 #include "grx_camera_rgb_api.h"
 #include "grx_trimesh_api.h"
+#include "grx_ik_api.h"
 #include "grx_sensors_api.h"
 // sizeof(grx_sim_applied) and the byte offset of every member, in declaration order: what _native.SimAppliedStruct must mirror (host only)
 extern "C" int grx_sim_applied_layout(long long* out, int cap) {

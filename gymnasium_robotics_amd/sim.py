@@ -161,8 +161,28 @@ tile, so that the normal's type switch stays wave-uniform.  This is a self-conta
     depth = sim.render("head_cam", 64, 64, exclude_own_body=True, max_dist=10.0)                   # [N, 1, 64, 64]
     depth, rgb = sim.render("head_cam", 64, 64, rgb=True, colors=my_rgb, sun=(0.3, -0.5, -0.8))    # rgb: uint8 [N, 1, 64, 64, 4]
 
+INVERSE KINEMATICS: ``qpos, err, iters = sim.solve_ik(sites, target_pos, target_quat=None, qpos0=None, dofs=None, damping=1e-2, max_step=0.5, tol=1e-4, max_iters=32,
+rot_weight=1.0, clamp_limits=True, mask=None, out=None)`` puts K = 1 .. 4 sites where the caller wants them: damped least squares over ``mj_jacSite``, the whole loop of a world in
+one launch (grx_sim_ik: one wave per world, its own kinematics, so no output is needed and nothing of the step path is launched).  ``sim.qpos`` is never written; assign the
+result if you want it.  Per world, with q = ``qpos0`` (default ``sim.qpos``):
+  1. forward kinematics of the compiled tree at q (hinge, slide and free joints; free-joint quaternions normalised as ``mj_kinematics`` does; mocap bodies at ``sim.mocap_pos`` /
+     ``sim.mocap_quat``);
+  2. the error: ``e_pos,k = p*_k - p_k(q)`` and, with ``target_quat`` (w, x, y, z; need not be unit), ``d = r*_k (x) conj(r_k(q))``, negated if ``d.w < 0``, ``e_rot,k = rot_weight 2
+     atan2(|d.v|, d.w) d.v / |d.v|`` (0 for ``|d.v| = 0``), a world-frame rotation vector; e stacks these per site, position first (m = 6 K components, or 3 K);
+  3. stop if ``|e| < tol`` or ``max_iters`` updates have been made;
+  4. J [m, nv]: the rows ``jacp_k`` and ``rot_weight jacr_k``; the columns of the dofs outside ``dofs`` (joint names, or a bool array [nv]) are zero;
+  5. ``y = (J J' + damping^2 I)^-1 e`` by Cholesky, ``dq = J' y``, scaled to ``max_step`` if longer;
+  6. ``q <- mj_integratePos(q, dq, 1)``; with ``clamp_limits`` every limited hinge or slide joint is clamped into ``jnt_range``.  Only coordinates whose dof is in ``dofs`` are written:
+     the others come back bit for bit.  Go to 1.
+``err`` [N] is ``|e|`` at the returned ``qpos`` [N, nq], ``iters`` [N] int32 the number of updates.  A masked-out world returns ``qpos0``, -1, 0; a world whose ``qpos0`` or targets are
+not finite returns ``qpos0``, +inf, 0.  Wrong shapes, dtypes or parameters are a ``ValueError`` before the device is touched.
+
+    qpos, err, iters = sim.solve_ik("grip", goal_xyz.view(4096, 1, 3), dofs=arm_joint_names)      # goal_xyz: [N, 3] float32 on the device
+    sim.qpos.copy_(torch.where((err < 1e-3)[:, None], qpos, sim.qpos))
+    sim.forward()
+
 Not here: shape-specialised kernels for user models, split or cost-ordered launches, a handle in libgrx_env.so, keyframes, per-world geometry or poses,
-equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms, colour and normals on mesh triangles (mesh="triangles" serves rays, depth and segmentation), mesh files other than binary STL, geom groups, height fields, textures, shadows, specular light, transparency, visual-only geoms, tracking and targeting cameras.
+equality-constraint forces in cfrc_ext, sensor reference frames and noise, MuJoCo's contact order, elliptic cones, rays against visual geoms, colour and normals on mesh triangles (mesh="triangles" serves rays, depth and segmentation), mesh files other than binary STL, geom groups, height fields, textures, shadows, specular light, transparency, visual-only geoms, tracking and targeting cameras, ball joints, nullspace posture terms, collision avoidance and per-site weights in solve_ik.
 """
 import ctypes
 
@@ -1012,6 +1032,82 @@ class BatchedSim:
 
         return self._render("render_pose()", int(p.shape[1]), height, width, fovy, segmentation, exclude_body, max_dist, include_static, mask, out, binning, tile, fill,
                             rgb, normals, colors, shade, mesh)
+
+    # ------------------------------------------------------------------ inverse kinematics (include/grx_capi.h grx_sim_ik; module docstring, INVERSE KINEMATICS)
+    def _ik_dofs(self, dofs):
+        """[nv] uint8 host array of the dofs a solve_ik call may move, or None for all of them"""
+        if dofs is None:
+            return None
+        if isinstance(dofs, str):
+            dofs = (dofs,)
+        if len(dofs) and all(isinstance(d, str) for d in dofs):
+            sel = np.zeros(self.nv, np.uint8)
+            kind = np.asarray(self.model.tables["jnt_type"]).reshape(-1)
+            for name in dofs:
+                a = self.joint_dofadr(name)
+                sel[a: a + (6 if kind[self._lookup("joint", name)] == 0 else 1)] = 1
+            return sel
+        sel = np.asarray(dofs)
+        if sel.dtype != np.bool_ or sel.shape != (self.nv,):
+            raise ValueError(f"dofs is None, a sequence of joint names or a bool array of shape ({self.nv},)")
+        return np.ascontiguousarray(sel, dtype=np.uint8)
+
+    def solve_ik(self, sites, target_pos, target_quat=None, qpos0=None, dofs=None, damping=1e-2, max_step=0.5, tol=1e-4, max_iters=32, rot_weight=1.0, clamp_limits=True,
+                 mask=None, out=None):
+        """Damped-least-squares inverse kinematics for every world, the whole loop in one launch (module docstring, INVERSE KINEMATICS): moves the K = 1 .. 4 named sites
+        to target_pos [N, K, 3] ([K, 3]: the same targets in every world) and, when given, target_quat [N, K, 4] (w, x, y, z; need not be unit), starting at qpos0 [N, nq]
+        (default sim.qpos, which is never written).  dofs: the joints (names) or dofs (bool [nv]) the solve may move; the coordinates of the others come back bit for bit.
+        Returns (qpos [N, nq] float32, err [N] float32: the error norm at that qpos, iters [N] int32: the updates made).  A masked-out world returns qpos0, -1, 0; a world with a
+        non-finite qpos0 or target returns qpos0, +inf, 0.  out=(qpos, err, iters): write into these tensors.  Enqueues on torch's current stream; never synchronises."""
+        import torch
+
+        from . import _native
+        from .core import stream_ptr
+
+        if isinstance(sites, str):
+            sites = (sites,)
+        ids = [self.site_id(s) for s in sites]
+        K, N = len(ids), self.num_worlds
+        if not 1 <= K <= 4:
+            raise ValueError(f"solve_ik takes 1 .. 4 sites, not {K}")
+        if int(max_iters) < 0 or not float(damping) > 0.0 or not float(tol) >= 0.0 or not float(max_step) > 0.0:
+            raise ValueError("solve_ik needs max_iters >= 0, damping > 0, tol >= 0 and max_step > 0")
+        sel = self._ik_dofs(dofs)
+
+        def checked(x, what, shape):      # host only: a float32 tensor or array of shape [N, *shape], or [*shape]: the same rows in every world
+            if not torch.is_tensor(x):
+                x = np.asarray(x)
+            if str(x.dtype).split(".")[-1] != "float32" or tuple(x.shape) not in ((N,) + shape, shape):
+                raise ValueError(f"{what} must be float32 of shape {(N,) + shape} or {shape}, not {x.dtype} {tuple(x.shape)}")
+            return x
+
+        tp = checked(target_pos, "target_pos", (K, 3))
+        tq = None if target_quat is None else checked(target_quat, "target_quat", (K, 4))
+        q0 = None if qpos0 is None else checked(qpos0, "qpos0", (self.nq,))
+        if mask is not None and tuple(mask.shape if hasattr(mask, "shape") else np.asarray(mask).shape) != (N,):
+            raise ValueError(f"mask must have shape ({N},)")
+        if out is not None:
+            for x, shape, dt in zip(out, ((N, self.nq), (N,), (N,)), (torch.float32, torch.float32, torch.int32)):
+                if not torch.is_tensor(x) or tuple(x.shape) != shape or x.dtype != dt or not x.is_cuda or not x.is_contiguous():
+                    raise ValueError(f"out= takes contiguous device tensors: qpos float32 {(N, self.nq)}, err float32 {(N,)}, iters int32 {(N,)}")
+        t = self._ensure()      # from here on the device
+        if self._entry is None:
+            raise RuntimeError("this BatchedSim is closed: its model handles are gone")
+        rows = lambda x, shape: None if x is None else torch.as_tensor(x, device=self.device).expand((N,) + shape).contiguous()
+        tp, tq, q0, m = rows(tp, (K, 3)), rows(tq, (K, 4)), rows(q0, (self.nq,)), self._mask(mask)
+        if q0 is None:
+            q0 = t["qpos"]
+        qpos, err, iters = out if out is not None else (torch.empty((N, self.nq), dtype=torch.float32, device=self.device), torch.empty(N, dtype=torch.float32, device=self.device),
+                                                        torch.empty(N, dtype=torch.int32, device=self.device))
+        host = (ctypes.c_int * K)(*ids)
+        ptr = lambda x: None if x is None or not x.numel() else x.data_ptr()
+        b = _native.SimIkStruct(qpos0=q0.data_ptr(), mocap_pos=ptr(t["mocap_pos"]), mocap_quat=ptr(t["mocap_quat"]), target_pos=tp.data_ptr(), target_quat=ptr(tq), mask=ptr(m),
+                                qpos=qpos.data_ptr(), err=err.data_ptr(), iters=iters.data_ptr(), site=ctypes.cast(host, ctypes.c_void_p),
+                                dof_mask=None if sel is None else sel.ctypes.data, n_sites=K, max_iters=int(max_iters), clamp_limits=int(bool(clamp_limits)),
+                                damping=float(damping), max_step=float(max_step), tol=float(tol), rot_weight=float(rot_weight))
+        with torch.cuda.device(self.device):
+            _native.check(self._L.grx_sim_ik(self._h, ctypes.byref(b), N, stream_ptr(self.device)))
+        return qpos, err, iters
 
     # ------------------------------------------------------------------ status words (include/grx_capi.h grx_status_bits), as the env classes report them
     @property

@@ -642,6 +642,45 @@ void grx_sim_trimesh_destroy(grx_trimesh* h);
 int grx_sim_ray_tri(const grx_model* m, const grx_sim_rays* r, const grx_trimesh* h, int n_worlds, int n_rays, void* stream);
 int grx_sim_ray_sites_tri(const grx_model* m, const grx_sim_rays* r, const grx_trimesh* h, int n_worlds, int n_rays, void* stream);
 int grx_sim_render_tri(const grx_model* m, const grx_sim_cameras* c, const grx_trimesh* h, int n_worlds, int n_cams, int height, int width, void* stream);
+/* INVERSE KINEMATICS for the worlds of the task-free stepper: damped least squares on the poses of K = 1 .. 4 sites, the whole loop of a world in one launch (one wave per
+ * world).  Not a step and not state: the call reads qpos0, the mocap poses and the targets the caller passes in and the handle's kinematic tables, and writes qpos, err and
+ * iters; it does its own kinematics, so it needs no output of a step launch.  The error has m = 6 K components, or 3 K when target_quat is NULL.
+ * Per world, with q = qpos0:
+ *   1. KINEMATICS at q: forward kinematics of the compiled tree (body_pos, body_quat, jnt_type, jnt_pos, jnt_axis, jnt_qposadr, site_bodyid, site_pos, site_quat; hinge, slide
+ *      and free joints; a free joint's quaternion is normalised as mj_kinematics does; a mocap body takes its pose from mocap_pos / mocap_quat).
+ *   2. ERROR: e_pos,k = p*_k - p_k(q).  With target_quat (w, x, y, z; any positive length): d = r*_k (x) conj(r_k(q)), negated if d.w < 0, and
+ *      e_rot,k = rot_weight 2 atan2(|d.v|, d.w) d.v / |d.v| (0 for |d.v| = 0): a world-frame rotation vector.  e stacks these per site, position first.
+ *   3. If |e| < tol, or max_iters updates have been made, stop.
+ *   4. JACOBIAN: J [m, nv] has the rows jacp_k and rot_weight jacr_k, mj_jacSite's definition; the columns of the dofs dof_mask leaves out are zero.
+ *   5. SOLVE: y = (J J' + damping^2 I)^-1 e by Cholesky, dq = J' y; if |dq| > max_step, dq is scaled to that length.
+ *   6. UPDATE: q <- mj_integratePos(q, dq, 1): hinge and slide add; a free joint adds the position, multiplies the quaternion by the rotation of the body-frame vector
+ *      dq[3:6] and normalises.  With clamp_limits every jnt_limited hinge or slide joint is clamped into jnt_range.  Only coordinates whose dof the call may move are
+ *      written (a free joint: any of its six), so every other coordinate comes back bit for bit.  Go to 1.
+ * err = |e| of the last evaluation of 2, iters = the number of times 6 ran.  A masked-out world returns qpos0, err = -1, iters = 0; a world whose qpos0 or targets hold a
+ * non-finite value returns qpos0, err = +inf, iters = 0.  site and dof_mask are read from HOST memory during the call; everything else is device memory.  One launch, enqueued
+ * on `stream`; never waits.  A model handle has at most 64 bodies and 64 dofs (grx_model_create), which the kernel's lanes cover in one pass.
+ * Return -1 (grx_last_error), before any launch, for a NULL model, block, input or output pointer, n_worlds < 1, n_sites outside 1 .. 4, max_iters < 0, damping <= 0, tol < 0,
+ * max_step <= 0 (these are checked first and read nothing of the model), a model compiled with an origin other than 0 or with a per-world shift group, a site outside
+ * [0, nsite), and NULL mocap poses for a model with mocap bodies. */
+typedef struct grx_sim_ik_args {
+  const float* qpos0;                      /* [N,nq] the start */
+  const float *mocap_pos, *mocap_quat;     /* [N,nmocap,3] [N,nmocap,4]; NULL for a model without mocap bodies */
+  const float* target_pos;                 /* [N,K,3] world frame */
+  const float* target_quat;                /* [N,K,4] or NULL: positions only */
+  const unsigned char* mask;               /* [N] or NULL */
+  float* qpos;                             /* [N,nq] */
+  float* err;                              /* [N] */
+  int* iters;                              /* [N] */
+  const int* site;                         /* [K] HOST: site ids */
+  const unsigned char* dof_mask;           /* [nv] HOST: non-zero = the call may move the dof; NULL: every dof */
+  int n_sites;                             /* K */
+  int max_iters;
+  int clamp_limits;
+  float damping, max_step, tol, rot_weight;
+} grx_sim_ik_args;
+int grx_sim_ik(const grx_model* m, const grx_sim_ik_args* a, int n_worlds, void* stream);
+/* host only: out[0] = sizeof(grx_sim_ik_args), out[1 ...] = the byte offset of each member in declaration order; returns the number of values (19) */
+int grx_sim_ik_layout(long long* out, int cap);
 /* PER-WORLD MODEL PARAMETERS of the task-free stepper (domain randomization): a parameter object names a set of fp tables whose values differ from world to world.
  *   names: gravity (the three gravity words of the model's options), body_mass, body_inertia, dof_damping, dof_armature, dof_frictionloss, jnt_stiffness, jnt_springref,
  *          jnt_range, act_gear, act_gainprm, act_biasprm, act_ctrlrange, act_forcerange, pair_friction, pair_solref, pair_solimp   (include/grx_model_fields.def)
